@@ -2,7 +2,7 @@
 """Headline benchmark: images/s of one full SD1.5 LoRA train step (rank 4, batch 4/GPU, 512² → 64×64×4 latents,
 fp16 storage/compute with fp32 accumulate and fp32 master LoRA), synthetic latents, 1..8 GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -64,7 +64,16 @@ def parse():
     ap.add_argument("--stub-body", default=None, choices=["ok", "fail", "diverge"],
                     help="test hook: ranks only rendezvous over gloo on the CPU and rank 0 prints a stub JSON line "
                          "('fail': rank 1 exits non-zero) — exercises the launcher without a GPU")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline workload, rank 0 writes what the LAST timed step left its caller "
+                         "as DIR/<name>.npy (float32, at most 64 MB in all; see dump_outputs): the loss, the trained parameters "
+                         "and their gradients — for comparing two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.drop_in or args.exchange_probe or args.stub_body):
+        ap.error("--dump-outputs applies to the headline workload only")
+    return args
 
 
 def _free_port() -> int:
@@ -115,6 +124,21 @@ def replicas_identical(flat, dist, rank) -> bool:
     return True
 
 
+def rank_sync(dist, device="cpu"):
+    """Barrier of the ranks as a one-element all-reduce on `device`.  Not dist.barrier(): that one asks torch for the
+    accelerator, which initialises the HIP runtime and opens the GPU — in every rank of the CPU-only rehearsal too."""
+    dist.all_reduce(torch.zeros(1, device=device))
+
+
+def exit_diverged(dist, device="cpu"):
+    """Exit code 4 after a failed replicas_identical().  Every rank reaches this together (the check is collective), so they
+    leave the process group the way a finished run does: a rank that exits while its peers still hold the group open can
+    abort (SIGABRT) in the teardown, and the launcher then reports that abort instead of the divergence."""
+    rank_sync(dist, device)
+    dist.destroy_process_group()
+    sys.exit(4)
+
+
 def stub_body(args, rank, world):
     """Launcher rehearsal body (CPU only, gloo): the data-parallel skeleton of the real body without a GPU — every rank holds a
     replica of a small slab, takes `steps` steps on its own shard with the REAL exchange (trainer.SlabExchange: one SUM
@@ -146,7 +170,7 @@ def stub_body(args, rank, world):
             dist.all_reduce(grads.clone())
         slab -= 1e-2 * grads / world
     if world > 1 and not replicas_identical(slab, dist, rank):
-        sys.exit(4)
+        exit_diverged(dist)
     t = torch.tensor([float(rank + 1)])
     if world > 1:
         dist.all_reduce(t)
@@ -156,7 +180,7 @@ def stub_body(args, rank, world):
                           "config": {"parallelism": f"dp{world}", "rccl_ranks": dist.get_world_size() if world > 1 else 1,
                                      "backend": dist.get_backend() if world > 1 else None}}), flush=True)
     if world > 1:
-        dist.barrier()
+        rank_sync(dist)
         dist.destroy_process_group()
 
 
@@ -340,6 +364,27 @@ def usable_cpus() -> int:
 
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: writes each tensor of `arrays` (name -> tensor) as `out_dir/<name>.npy` in float32.  An array larger
+    than its even share of `budget` (config 5's 49408x1024 token table) is replaced by a fixed sample of that many elements
+    of its flattened form: indices drawn with a generator of fixed seed from the array's size alone, sorted — the same
+    elements on every run of the same workload."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // (4 * max(1, len(arrays)))  # elements per array
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(arrays)
 
 
 def cpu_model_name() -> str:
@@ -534,7 +579,7 @@ def run_workload(args, cfg_id, rank, world, device, dist, profile=True):
             trainer.capture_graph = mode
             run_step(0)
         if not replicas_identical(trainer.slab.params, dist, rank):  # LoRA region AND the dense tail (config 5: the token table)
-            sys.exit(4)
+            exit_diverged(dist, device)
     trainer.slab.params.copy_(snapshot[0]); trainer.opt.exp_avg.copy_(snapshot[1]); trainer.opt.exp_avg_sq.copy_(snapshot[2])
     trainer.opt.step_count = snapshot[3]
     trainer.opt.norm.copy_(snapshot[4])  # incl. the device-side count of applied steps
@@ -553,6 +598,15 @@ def run_workload(args, cfg_id, rank, world, device, dist, profile=True):
         losses.append(run_step(i))
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and cfg_id == args.config:
+        # what the last timed step left its caller, before the passes below take further steps: the loss it returned, the
+        # trained parameters (LoRA factors in file order) and their `.grad` — views of the trainer's fp32 slabs
+        slab = trainer.slab
+        outs = {"loss": losses[-1], "lora_params": slab.params[:slab.numel], "lora_grads": slab.grads[:slab.numel]}
+        for j, (a, b) in enumerate(slab.dense_ranges):  # (config 5: the trainable token-embedding table)
+            outs[f"dense{j}_params"], outs[f"dense{j}_grads"] = slab.params[a:b], slab.grads[a:b]
+        log(f"[{cfg['tag']}] outputs of timed step {args.steps} written to {args.dump_outputs}: "
+            f"{', '.join(dump_outputs(args.dump_outputs, outs))}")
     # What a step does OUTSIDE the recording, per rank: [RCCL all-reduce of the slab] → clip norm + AdamW → re-pack of the
     # compute-dtype factors (+ the token-table row sum of config 5).  Timed with events in a few extra replayed steps after the
     # timed region (not part of `value`); on one GPU the exchange is empty, so this is the floor the 8-GPU step adds its

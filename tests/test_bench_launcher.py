@@ -1,16 +1,20 @@
 """`python bench.py --gpus N` must start N ranks by itself (the driver's N=1 call and its torch.distributed.run call both
-keep working).  The rank body is stubbed (`--stub-body`): gloo on the CPU, no GPU, so this runs in the build container."""
+keep working).  The rank body is stubbed (`--stub-body`): gloo on the CPU, no GPU, so this runs in the build container.
+Also: what bench.py writes with --dump-outputs (the writer on the CPU, the real body's files on the GPU)."""
 import json
 import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*argv, env_drop=("WORLD_SIZE", "RANK", "LOCAL_RANK")):
+def _run(*argv, env_drop=("WORLD_SIZE", "RANK", "LOCAL_RANK"), env_set=None):
     env = {k: v for k, v in os.environ.items() if k not in env_drop}
     env["OMP_NUM_THREADS"] = "1"
+    env.update(env_set or {})
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], env=env, capture_output=True,
                           text=True, timeout=300)
 
@@ -59,14 +63,14 @@ def test_world_8_diverged_replica_ends_the_run_with_exit_code_4():
 def test_eight_ranks_refuse_to_share_the_visible_devices():
     """One process per GPU: on a node that shows fewer devices than local ranks (this container shows none) every rank of the
     REAL body exits with code 5 before anything touches a device — two ranks time-slicing one GPU must never be reported as
-    N GPUs; `--shared-gpu` is the explicit rehearsal switch."""
+    N GPUs; `--shared-gpu` is the explicit rehearsal switch.  The ranks are shown no device at all (an empty
+    HIP_VISIBLE_DEVICES: torch then counts none without opening one), so that on a GPU node, too, none of the eight opens it."""
     import torch
 
     if torch.cuda.device_count() >= 8:
-        import pytest
-
         pytest.skip("a full node: nothing to refuse")
-    res = _run("--gpus", "8", "--steps", "1", "--warmup", "0", "--no-extra", "--no-cpu-baseline")
+    res = _run("--gpus", "8", "--steps", "1", "--warmup", "0", "--no-extra", "--no-cpu-baseline",
+               env_set={"HIP_VISIBLE_DEVICES": ""})
     assert res.returncode != 0
     assert not _json_lines(res.stdout)
     assert "visible GPU(s) for 8 ranks" in res.stderr and "--shared-gpu" in res.stderr
@@ -162,3 +166,52 @@ def test_launch_floor_fields_of_the_roofline_object():
     assert abs(roof["fused_gemm_classes"][gemm]["launch_floor_us_per_launch"] - 5.0) < 1e-9
     bench.add_launch_floor(roof2 := {"step_level": {}}, {}, 4.0)  # no floor pass: nothing added, nothing raised
     assert roof2 == {"step_level": {}}
+
+
+def test_dump_outputs_writes_float32_within_the_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs' writer: float32 files named after the arrays, whole while an array fits its even share of the budget,
+    otherwise a fixed sample of that many elements (in index order) — the same on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    arrays = {"loss": torch.tensor([0.25]), "small": torch.randn(3, 5, generator=g, dtype=torch.float64),
+              "big": torch.arange(1000).half()}  # (each element is its own index)
+    budget = 3 * 4 * 100  # 100 elements per array
+    assert bench.dump_outputs(str(tmp_path / "a"), arrays, budget) == ["big", "loss", "small"]
+    bench.dump_outputs(str(tmp_path / "b"), arrays, budget)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= budget
+    assert got["loss"].tolist() == [0.25]
+    assert np.array_equal(got["small"], arrays["small"].float().numpy())
+    pos = got["big"].tolist()
+    assert got["big"].shape == (100,) and pos == sorted(set(pos))  # distinct elements, in index order
+    assert all(np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy")) for n in arrays)
+
+
+def test_bench_rejects_arguments_it_cannot_honour(tmp_path):
+    for argv in (("--steps", "0"), ("--warmup", "-1"), ("--dump-outputs", str(tmp_path), "--drop-in"),
+                 ("--dump-outputs", str(tmp_path), "--stub-body", "ok")):
+        res = _run(*argv)
+        assert res.returncode == 2 and not _json_lines(res.stdout), argv
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_headline_are_its_last_timed_step(tmp_path):
+    """bench.py --dump-outputs on the GPU: the loss of the last timed step (the line's final_loss), the LoRA factors and
+    their gradients of the whole headline workload, all float32 and finite."""
+    import numpy as np
+
+    res = _run("--gpus", "1", "--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--no-prof", "--no-graph",
+               "--dump-outputs", str(tmp_path))
+    assert res.returncode == 0, res.stderr[-2000:]
+    line = _json_lines(res.stdout)[-1]
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("loss", "lora_params", "lora_grads")}
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["lora_grads.npy", "lora_params.npy", "loss.npy"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert float(got["loss"].reshape(-1)[0]) == line["config"]["final_loss"]
+    assert got["lora_params"].shape == got["lora_grads"].shape == (line["config"]["lora_params"],)
+    assert np.abs(got["lora_grads"]).max() > 0
