@@ -16,6 +16,7 @@ import diffusion_finetuning_amd as dfa
 from diffusion_finetuning_amd import _native as nat
 from diffusion_finetuning_amd import trainer as tr
 from oracle import lora_oracle as orc
+from tests.attention_cases import attention_reference as _attention_reference
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -1058,17 +1059,8 @@ def test_sandwich_ops_geglu_and_head_layouts(relerr, dtype):
     assert torch.equal(merge_heads(view, d).cpu(), t[..., :d].reshape(B, N, H * d))
 
 
-def _attention_reference(q, k, v, heads):
-    """softmax(QKᵀ/√d)V per head in float64 on [B, T, H·d] tensors (the math of diffusers CrossAttention's core)."""
-    B, Tq, HD = q.shape
-    d = HD // heads
-    qh, kh, vh = (t.double().view(B, -1, heads, d).transpose(1, 2) for t in (q, k, v))
-    p = torch.softmax(qh @ kh.transpose(-1, -2) * d ** -0.5, dim=-1)
-    return (p @ vh).transpose(1, 2).reshape(B, Tq, HD)
-
-
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-def test_ctx_attention_core_against_float64_reference(relerr, dtype):
+def test_ctx_attention_core_against_float64_reference(close, dtype):
     """f-4 (second part): the short-context attention kernels (forward, dQ/dK/dV) on cross-attention shapes — the SD
     ones (77 text tokens; heads of 40 and 80), ragged query counts, 1 … 128 keys, every head-dim bucket — against
     float64 math on the same 16-bit inputs.  Tolerance: one output rounding of the dtype plus the 16-bit P·V operand."""
@@ -1092,11 +1084,11 @@ def test_ctx_attention_core_against_float64_reference(relerr, dtype):
         got = ctx_attention(qd, kd, vd, H)
         got.backward(go.to(DEV))
         for name, a, b in (("o", got, want), ("dq", qd.grad, qr.grad), ("dk", kd.grad, kr.grad), ("dv", vd.grad, vr.grad)):
-            assert relerr(a, b) < tol, (name, (B, Tq, Tk, H, d), relerr(a, b))
+            close(a, b, tol, (name, (B, Tq, Tk, H, d)))
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-def test_flash_attention_core_against_float64_reference(relerr, dtype):
+def test_flash_attention_core_against_float64_reference(close, dtype):
     """f-4 (third part): the long-context attention kernels (online softmax over 64-key tiles; forward, dQ, dK, dV) on the
     SD self-attention shapes (4096 tokens × heads of 40, 1024 × 80, 256 × 160), ragged query/key counts, cross shapes with
     more than 128 keys and every head-dim bucket — against float64 math on the same 16-bit inputs."""
@@ -1125,7 +1117,7 @@ def test_flash_attention_core_against_float64_reference(relerr, dtype):
             if float(b.abs().max()) == 0.0:
                 assert float(a.double().cpu().abs().max()) < 1e-6, (name, (B, Tq, Tk, H, d), float(a.abs().max()))
             else:
-                assert relerr(a, b) < tol, (name, (B, Tq, Tk, H, d), relerr(a, b))
+                close(a, b, tol, (name, (B, Tq, Tk, H, d)))
     # inference form (no gradient requested): no log-sum-exp buffer, same output
     with torch.no_grad():
         assert torch.equal(flash_attention(qd, kd, vd, H), got)
