@@ -299,9 +299,6 @@ def _splitk_workspace(M: int, Kc: int, Nc: int, like):
 
 def grad_blocks_for(M: int) -> int:
     """Row blocks for the factor-gradient kernel when the caller has no fixed layout (plain autograd mode)."""
-    forced = os.environ.get("LORA_GRAD_BLOCKS")  # tuning knob for tools/gemm_bench.py
-    if forced:
-        return int(forced)
     return max(1, min(128, M // 32))
 
 

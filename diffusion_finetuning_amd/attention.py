@@ -249,14 +249,11 @@ def set_use_hip_geglu(module: nn.Module, valid: bool = True) -> int:
     the forward that also folds the gate's BACKWARD into the following linear layer's backward GEMM.  The reference has no
     switch for this op; a trainer that wants it adds one line next to its `--use_xformers` line.  Returns the number of GEGLU
     modules touched."""
-    import os
-
-    ff_fusion = os.environ.get("DFA_NO_FF_FUSION", "0") != "1"  # dev knob (tools/ab_env.sh): forward-only gate fusion
     for m in module.modules():
         if not _is_geglu_feed_forward(m):
             continue
         has = _ORIG in m.__dict__
-        if valid and not has and ff_fusion:
+        if valid and not has:
             m.__dict__[_ORIG] = m.forward
             m.forward = functools.partial(_hip_feed_forward, m)
         elif not valid and has:

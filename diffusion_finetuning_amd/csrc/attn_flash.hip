@@ -617,10 +617,6 @@ bool plan_flash(int B, int Tq, int Tk, int H, int d, FlashPlan* pl) {
     else if (d <= 96) { pl->ks = 3; pl->df = 6; pl->rb = 2; pl->rb_dq = 2; pl->nkw = 2; }
     else if (d <= 128) { pl->ks = 4; pl->df = 8; pl->rb = 2; pl->rb_dq = 1; pl->nkw = 1; }
     else { pl->ks = 5; pl->df = 10; pl->rb = 1; pl->rb_dq = 1; pl->nkw = 1; }
-    static const int nkw_env = [] { const char* e = getenv("FLASH_NKW"); return e ? atoi(e) : 0; }();  // tools/flash_check.py
-    if (nkw_env == 2 && pl->nkw == 4) pl->nkw = 2;
-    static const int rb_env = [] { const char* e = getenv("FLASH_RB"); return e ? atoi(e) : 0; }();
-    if (rb_env == 2 && pl->rb == 4) pl->rb = 2;  // tuning knob for tools/flash_check.py
     return true;
 }
 
@@ -659,8 +655,7 @@ int launch_flash_fwd_v(const FlashArgs& a, hipStream_t stream) {
 
 template <typename T, int KS, int DF, int RB>
 int launch_flash_fwd(const FlashArgs& a, hipStream_t stream) {
-    static const int ones_env = [] { const char* e = getenv("FLASH_ONES"); return e ? atoi(e) : 1; }();  // tools/flash_check.py
-    if (ones_env && (a.d % 16) == 8 && a.d / 16 == DF - 1) return launch_flash_fwd_v<T, KS, DF, RB, true>(a, stream);
+    if ((a.d % 16) == 8 && a.d / 16 == DF - 1) return launch_flash_fwd_v<T, KS, DF, RB, true>(a, stream);
     return launch_flash_fwd_v<T, KS, DF, RB, false>(a, stream);
 }
 
@@ -668,7 +663,7 @@ template <typename T>
 int dispatch_flash_fwd(const FlashArgs& a, const FlashPlan& pl, hipStream_t stream) {
 #define FLASH_CASE(KS_, DF_, RB_) \
     if (pl.ks == KS_ && pl.df == DF_ && pl.rb == RB_) return launch_flash_fwd<T, KS_, DF_, RB_>(a, stream);
-    FLASH_CASE(2, 3, 4) FLASH_CASE(2, 4, 4) FLASH_CASE(2, 3, 2) FLASH_CASE(2, 4, 2) FLASH_CASE(3, 5, 2) FLASH_CASE(3, 6, 2) FLASH_CASE(4, 8, 2) FLASH_CASE(5, 10, 1)
+    FLASH_CASE(2, 3, 4) FLASH_CASE(2, 4, 4) FLASH_CASE(3, 5, 2) FLASH_CASE(3, 6, 2) FLASH_CASE(4, 8, 2) FLASH_CASE(5, 10, 1)
 #undef FLASH_CASE
     return LORA_E_BADARG;
 }
@@ -729,8 +724,8 @@ template <typename T>
 int dispatch_flash_bwd(const FlashBwdArgs& a, const FlashPlan& pl, hipStream_t stream) {
 #define FLASH_BCASE(KS_, DF_, RBQ_, NKW_) \
     if (pl.ks == KS_ && pl.df == DF_ && pl.nkw == NKW_) return launch_flash_bwd<T, KS_, DF_, RBQ_, NKW_>(a, stream);
-    FLASH_BCASE(2, 3, 2, 4) FLASH_BCASE(2, 4, 2, 4) FLASH_BCASE(2, 3, 2, 2) FLASH_BCASE(2, 4, 2, 2) FLASH_BCASE(3, 5, 2, 2) FLASH_BCASE(3, 6, 2, 2)
-    FLASH_BCASE(4, 8, 1, 1) FLASH_BCASE(5, 10, 1, 1)
+    FLASH_BCASE(2, 3, 2, 4) FLASH_BCASE(2, 4, 2, 2) FLASH_BCASE(3, 5, 2, 2) FLASH_BCASE(3, 6, 2, 2) FLASH_BCASE(4, 8, 1, 1)
+    FLASH_BCASE(5, 10, 1, 1)
 #undef FLASH_BCASE
     return LORA_E_BADARG;
 }

@@ -37,7 +37,6 @@
 // Workgroups are dealt to XCDs so that the column tiles of one row panel (or the row tiles of one column panel, whichever
 // re-fetches the smaller operand) share an L2 — or, for square-ish problems, so that each XCD owns a rectangle of the tile grid.
 // Tile / ring / split choice per shape: launch_pipe(), gate_tile_width(), plan_splitk() — all measured with cold weights.
-#include <cstdlib>
 
 #include "common.h"
 
@@ -82,7 +81,6 @@ struct GemmParams {
     // 0..S-1 in index order — whoever arrives last, the sum has one order: deterministic — and runs the normal epilogue
     // (rank-r term, bias, store) on the totals; it leaves the ticket at zero for the next launch.  splitk <= 1: off.
     int splitk, steps_per_slice;
-    int split_aff;      // 1: slice s of every tile runs on XCD s % S (S divides 8) — a byte of Am / Bm is fetched by ONE L2
     float* ws_c;
     float* ws_p;
     unsigned* tickets;  // one per output tile, zero on entry, zero again on exit
@@ -92,7 +90,6 @@ struct GemmParams {
     // epilogue writes C2[M, gateF] = h·gelu(g) next to C (C may be null: nothing is saved for a backward pass).
     void* C2;
     int gateF;
-    int dbg;  // tools/gemm_bench.py ablations (LORA_GEMM_DBG, timing only — results are wrong): 1 = no DMA after the prologue, 2 = no MFMA work
 };
 
 constexpr int kRowBytes = 128;  // one K-step of one tile row
@@ -136,6 +133,12 @@ __device__ unsigned long long g_stamps[8192 * 16];
 #else
 #define STAMP(i)
 #define STAMP_WALL(i)
+#endif
+
+// Diagnostic ablation of the pipelined main loop, timing only — the results are wrong (tools/skeleton_per_class.py builds it
+// as a variant library with -DLORA_GEMM_DBG=N): bit 1 = no DMA after the prologue, bit 2 = no MFMA work.
+#ifndef LORA_GEMM_DBG
+#define LORA_GEMM_DBG 0
 #endif
 
 // One stage of the ring / the single staging buffer: A rows, B rows, 16 factor rows.  Only the first two waves load the
@@ -204,8 +207,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void lora_gemm_kernel(Gem
     // Pull every kernel argument into SGPRs now: one scalar-load round trip instead of two dependent ones.
     asm volatile("" ::"s"(p.Am), "s"(p.Bm), "s"(p.bias), "s"(p.Fp), "s"(p.Qp), "s"(p.C), "s"(p.P), "s"(p.M), "s"(p.Kc),
                  "s"(p.Nc), "s"(p.scale), "s"(p.tiles_m), "s"(p.tiles_n), "s"(p.col_major), "s"(p.lda), "s"(p.tile_part),
-                 "s"(p.part_table), "s"(p.splitk), "s"(p.steps_per_slice), "s"(p.ws_c), "s"(p.ws_p), "s"(p.tickets), "s"(p.xcd_m),
-                 "s"(p.split_aff));
+                 "s"(p.part_table), "s"(p.splitk), "s"(p.steps_per_slice), "s"(p.ws_c), "s"(p.ws_p), "s"(p.tickets), "s"(p.xcd_m));
     int tile, slice = 0;
     {
         const int S = SPLITK ? p.splitk : 1;
@@ -214,17 +216,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void lora_gemm_kernel(Gem
         const int q = total >> 3, rem = total & 7;
         const int xcd = id & 7, slot = id >> 3;
         tile = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + slot;
-        if (SPLITK && p.split_aff) {
-            // Slice → XCD affinity (S divides 8): XCD x runs slice x % S of the tiles of sub-range g = x / S (8/S sub-ranges of
-            // the tile list).  A K-range of Am and Bm is then streamed by 8/S L2s instead of by all eight — with S = 8 every
-            // operand byte is fetched by exactly one XCD (round 3's run order made every XCD stream ALL of Bm: 3.5x the
-            // algorithmic bytes).  The block counts match the round-robin dispatch: XCD x holds total/8 (+1 if x < total % 8)
-            // blocks and total % 8 = S·(tiles % G), so exactly the XCDs of the sub-ranges g < tiles % G take one more tile.
-            const int G = 8 / S, tiles = p.tiles_m * p.tiles_n;
-            const int g = xcd / S, tq = tiles / G, tr = tiles % G;
-            slice = xcd % S;
-            tile = g * tq + (g < tr ? g : tr) + slot;
-        } else if (S > 1) {  // the slices of one tile are neighbours: they read the same operand rows, a K-range each
+        if (S > 1) {  // the slices of one tile are neighbours: they read the same operand rows, a K-range each
             slice = tile % S;
             tile = tile / S;
         }
@@ -507,7 +499,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void lora_gemm_kernel(Gem
             if (kt == 0) STAMP(3);
             char* const refill = smem + (buf >= 1 ? buf - 1 : kStages - 1) * STAGE;  // the buffer read last step
             if (kt + DIST < nk) {
-                if (!(p.dbg & 1)) issue(kt + DIST, buf >= 1 ? buf - 1 : kStages - 1);
+                if (!(LORA_GEMM_DBG & 1)) issue(kt + DIST, buf >= 1 ? buf - 1 : kStages - 1);
             } else if (MAIN && kt == nk - 1) {  // (every K-slice of a split tile: any of them may turn out to be the last arriver)
                 sQ = refill + QOFF;  // nothing left to prefetch: the epilogue's Q tile takes the free buffer
                 issue_q(sQ);
@@ -515,7 +507,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void lora_gemm_kernel(Gem
             // (round 3, measured: the refill's DMA instructions spread BETWEEN this step's MFMAs instead of issued as one burst
             //  here — same counted waits, same buffers — is slower on every shape: 4096×640×640 12.6 → 14.0 µs, 1024×1280×1280
             //  equal, and the 128-row tiles spill (address registers stay live across the MFMA stream): 35.7 → 51.6 µs)
-            if (!(p.dbg & 2)) compute(smem + buf * STAGE, kt);
+            if (!(LORA_GEMM_DBG & 2)) compute(smem + buf * STAGE, kt);
             buf = buf + 1 == kStages ? 0 : buf + 1;
         }
     } else {
@@ -1106,7 +1098,7 @@ __global__ __launch_bounds__(256) void pack_factors_batched_kernel(const int64_t
 
 // Split-K plan.  Splitting buys chip occupancy with a combine that costs the tile ≈ 5–6 µs (write-through slab stores, the
 // ticket's round trip, the last arriver's serial slab reads at the cross-XCD rate), so it pays only for LONG contractions on
-// under-filled grids: measured (tools/splitk_sweep.sh, weights cold) the 20-K-step 1280-wide projections LOSE 2–3 µs at
+// under-filled grids: measured (profiles/r03_splitk_sweep_*.log, weights cold) the 20-K-step 1280-wide projections LOSE 2–3 µs at
 // every slice count (1024×1280×1280: 15.7 → 18.5 µs), the 60-K-step grouped q/k/v backward gains 5–8 µs (35 → 30, 26 → 19),
 // the 80/160-K-step GEGLU `proj` backward 18–30 µs (66 → 48, 84 → 54, 62 → 31).  Returns the slice count (1 = off) and the
 // row-tile height of the split launch: ≈ 480 workgroups, 64-row tiles on the small grids (two per CU overlap each other's
@@ -1114,48 +1106,32 @@ __global__ __launch_bounds__(256) void pack_factors_batched_kernel(const int64_t
 struct SplitPlan {
     int S, bm;
 };
-// Slice → XCD affinity (LORA_SPLIT_AFFINITY=1; off by default).  Measured in round 4 (profiles/r04_splitk_xcd_affinity_ab.log,
-// weights cold): it cuts the operand fetch to |Am| + |Bm| as intended, but the S slices of a tile then sit on S different XCDs,
-// so the last arriver's slab reads cross the fabric instead of hitting the L2 that holds the neighbours' write-through
-// stores — 4096×5120→640 49.5 → 64.0 µs, 1024×10240→1280 57.7 → 71.4, 256×10240→1280 29.8 → 35.1, grouped q/k/v backward at
-// 1024 rows 30.6 → 39.7: these launches are paced by the combine and their fixed phases, not by operand traffic.
-bool split_affinity() {
-    static const int env = [] { const char* e = getenv("LORA_SPLIT_AFFINITY"); return e ? atoi(e) : 0; }();
-    return env != 0;
-}
+// The S slices of a tile run as neighbours on one XCD.  Round 4 measured slice s on XCD s % S instead
+// (profiles/r04_splitk_xcd_affinity_ab.log, weights cold): it cuts the operand fetch to |Am| + |Bm| as intended, but the last
+// arriver's slab reads then cross the fabric instead of hitting the L2 that holds the neighbours' write-through stores —
+// 4096×5120→640 49.5 → 64.0 µs, 1024×10240→1280 57.7 → 71.4, 256×10240→1280 29.8 → 35.1, grouped q/k/v backward at 1024 rows
+// 30.6 → 39.7: these launches are paced by the combine and their fixed phases, not by operand traffic.
 constexpr int kTicketBytes = LORA_GEMM_WS_TICKET_BYTES;  // ticket header of the workspace: one u32 per output tile
 SplitPlan plan_splitk(int64_t M, int Kc, int Nc, int esize) {
-    static const int env = [] { const char* e = getenv("LORA_SPLITK"); return e ? atoi(e) : -1; }();
-    static const int env_bm = [] { const char* e = getenv("LORA_SPLIT_BM"); return e ? atoi(e) : 0; }();
-    static const int env_min = [] { const char* e = getenv("LORA_SPLIT_MINSTEPS"); return e ? atoi(e) : 0; }();
     SplitPlan off{1, 128};
-    if (env == 0) return off;
     const int nk = (Kc * esize + kRowBytes - 1) / kRowBytes;
     const int64_t tiles128 = ((M + 127) / 128) * ((Nc + 127) / 128);
     const int64_t tiles64 = ((M + 63) / 64) * ((Nc + 127) / 128);
     if ((Nc & 7) != 0 || (Kc * esize) % kRowBytes != 0 || tiles128 >= 192) return off;
-    if (env <= 0 && nk < 48) return off;
+    if (nk < 48) return off;
     int bm = tiles128 <= 96 ? 64 : 128;
     // round 5 (profiles/r05_splitk_plan_sweep.log, weights cold): a split launch is paced by its MAIN LOOP — 74 % of the 48-µs
     // 1024×10240→1280 launch, 0.67 µs per K-step at two workgroups per CU: the L1-fill bound of the unsplit kernels — not by the
     // combine (slab store + ticket 2 µs, the last arriver's sum 3.7 µs).  So the longest contractions take the 128-row tile (0.65× the
     // L1 bytes per flop) with more slices where that still fills the chip: 80 tiles × 6 slices, 58.2 → 53.5 µs.
     if (tiles128 >= 64 && nk >= 128) bm = 128;
-    if (env_bm == 64 || env_bm == 128) bm = env_bm;
     const int64_t tiles = bm == 64 ? tiles64 : tiles128;
     if (tiles > kTicketBytes / 4) return off;
     int S = (int)((480 + tiles / 2) / tiles);
     if (S > 8) S = 8;
-    const int min_steps = env_min > 0 ? env_min : 10;
+    const int min_steps = 10;
     while (S > 1 && nk / S < min_steps) --S;
-    if (env > 1) S = env > 8 ? 8 : env;
     while (S > 1 && (S - 1) * ((nk + S - 1) / S) >= nk) --S;  // every slice owns at least one K-step
-    if (split_affinity() && env <= 1) {
-        // slice → XCD affinity needs S | 8: the nearest power of two that still leaves min_steps per slice (3 → 4, 6 → 8 / 4)
-        int S2 = S >= 6 ? 8 : (S >= 3 ? 4 : S);
-        while (S2 > 1 && nk / S2 < min_steps) S2 >>= 1;
-        S = S2;
-    }
     return SplitPlan{S, bm};
 }
 int64_t splitk_ws_bytes(int64_t M, int Nc, const SplitPlan& sp) {
@@ -1190,17 +1166,15 @@ int launch_tile(GemmParams p, hipStream_t stream) {
     p.tiles_m = (int)((p.M + BM - 1) / BM);
     p.tiles_n = MAIN ? (p.Nc + BN - 1) / BN : (p.part_table ? p.tiles_n : 1);  // skinny grouped: tiles_n = parts
     if (p.ldp == 0) p.ldp = p.r;
-    static const int order_env = [] { const char* e = getenv("LORA_FORCE_COLMAJOR"); return e ? atoi(e) : -1; }();
-    p.col_major = order_env >= 0 ? order_env : (MAIN && (int64_t)p.Nc > p.M ? 1 : 0);
+    p.col_major = MAIN && (int64_t)p.Nc > p.M ? 1 : 0;
     p.xcd_m = 1;
     if (MAIN && p.splitk <= 1 && p.tile_part == nullptr && p.n_parts == 0) {
         // Which XCD grid re-fetches the fewest operand bytes?  An xm × xn grid (xm·xn = 8) makes the eight L2s fetch
         // xn·|Am| + xm·|Bm| in total; (8,1) and (1,8) are the row- / column-major runs above (any tile counts), the 2-D
         // grids need exact splits.  Only square-ish problems (the 1280-wide layers at 1024 / 256 rows) pick one.
-        static const int x2d_env = [] { const char* e = getenv("LORA_XCD2D"); return e ? atoi(e) : 1; }();
         const double am = (double)p.M * p.Kc, bm = (double)p.Nc * p.Kc;
         double best = p.col_major ? 8.0 * am + bm : am + 8.0 * bm;
-        for (int xm = 2; xm <= 4 && x2d_env; xm *= 2) {
+        for (int xm = 2; xm <= 4; xm *= 2) {
             const int xn = 8 / xm;
             if (p.tiles_m % xm != 0 || p.tiles_n % xn != 0) continue;
             const double cost = xn * am + xm * bm;
@@ -1218,7 +1192,6 @@ int launch_tile(GemmParams p, hipStream_t stream) {
             static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             if (attr != hipSuccess) return LORA_E_LAUNCH;
-            p.split_aff = split_affinity() && (8 % p.splitk) == 0 ? 1 : 0;
             p.ws_c = reinterpret_cast<float*>(reinterpret_cast<char*>(p.tickets) + kTicketBytes);
             p.ws_p = p.ws_c + (int64_t)p.tiles_m * p.tiles_n * p.splitk * (BM * BN);
             LORA_LAUNCH(PK_GEMM_SPLITK, kern, dim3(p.tiles_m * p.tiles_n * p.splitk), dim3(NW * 64), lds, stream, p);
@@ -1248,26 +1221,17 @@ int launch_tile(GemmParams p, hipStream_t stream) {
 // 4096 rows 60.2 → 51.0, 1024 rows 57.0 → 39.1, 256 rows 27.1 → 29.6; backward: 53.1 → 53.6, 41.0 → 35.9, 40.4 → 36.8,
 // 30.1 → 34.7): 160 for grids of 257..2047 128-wide tiles.  Ungated launches use the round-count model only.
 int gate_tile_width(int64_t tiles_m, int cols, bool gated) {
-    static const int env = [] { const char* e = getenv("LORA_GATE_BN"); return e ? atoi(e) : 0; }();
     if (cols % 160 != 0) return 128;
-    if (env == 128 || env == 160) return env;
     const int64_t t128 = tiles_m * (cols / 128), t160 = tiles_m * (cols / 160);
     if (gated) return t128 > 256 && t128 < 2048 ? 160 : 128;
     const double c128 = (double)((t128 + 511) / 512), c160 = 1.25 * (double)((t160 + 511) / 512);
     return c160 < c128 ? 160 : 128;
 }
 
-// tools/gemm_bench.py / tools/skeleton_per_class.py ablations (GemmParams::dbg): read once, applied by every launcher
-static int gemm_dbg_env() {
-    static const int v = [] { const char* e = getenv("LORA_GEMM_DBG"); return e ? atoi(e) : 0; }();
-    return v;
-}
-
 // GEGLU-gated forward: the two-stage ring kernel, a tile = BN/2 h columns + their BN/2 g columns.
 template <typename T, int BN>
 int launch_gate_bn(GemmParams p, hipStream_t stream) {
     constexpr int BM = 128;
-    p.dbg = gemm_dbg_env();
     p.tiles_m = (int)((p.M + BM - 1) / BM);
     p.tiles_n = p.gateF / (BN / 2);
     p.ldp = p.r;
@@ -1292,7 +1256,6 @@ int launch_gate(GemmParams p, hipStream_t stream) {
 template <typename T, int BN>
 int launch_gate_bwd_bn(GemmParams p, hipStream_t stream) {
     constexpr int BM = 128;
-    p.dbg = gemm_dbg_env();
     p.tiles_m = (int)((p.M + BM - 1) / BM);
     p.tiles_n = p.Nc / BN;
     p.ldp = p.r;
@@ -1345,14 +1308,6 @@ int launch_kparts(const GemmParams& p, hipStream_t stream) {
     }
 }
 
-int forced_tile() {  // tuning knob for tools/gemm_bench.py only
-    static const int forced = [] {
-        const char* e = getenv("LORA_FORCE_TILE");
-        return e ? atoi(e) : -1;
-    }();
-    return forced;
-}
-
 // Tile and ring-depth choice, from tools/gemm_bench.py sweeps on MI355X — hot and with cold weights (--cold-read) — and from
 // the in-model launch-class table (tools/summarize_profile.py shapes; profiles/README.md):
 //  * occupancy beats prefetch depth: a 2-stage ring lets two 128-row workgroups share a CU (≤ 78 KB LDS each) and
@@ -1366,12 +1321,8 @@ int forced_tile() {  // tuning knob for tools/gemm_bench.py only
 //    slower than two independent 128-row workgroups per CU on every hot-path shape.  Not instantiated (the template
 //    still supports them).
 template <typename T, bool MAIN>
-int launch_pipe(const GemmParams& p_in, hipStream_t stream) {
-    GemmParams p = p_in;
-    static const int dbg_env = [] { const char* e = getenv("LORA_GEMM_DBG"); return e ? atoi(e) : 0; }();
-    p.dbg = dbg_env;
+int launch_pipe(const GemmParams& p, hipStream_t stream) {
     if (!MAIN) return launch_tile<T, 64, 64, false, 3>(p, stream);
-    static const int stg_env = [] { const char* e = getenv("LORA_FORCE_STAGES"); return e ? atoi(e) : 0; }();
     if (p.splitk > 1) {  // (tile height from plan_splitk: the workspace was sized for it)
         if (p.split_bm == 64) return launch_tile<T, 64, 128, true, 3, 4>(p, stream);
         return launch_tile<T, 128, 128, true, 2, 4>(p, stream);
@@ -1385,10 +1336,7 @@ int launch_pipe(const GemmParams& p_in, hipStream_t stream) {
     const int padded = (p.Nc + 127) / 128 * 128;
     // equal parts over the output columns: a column tile must lie inside one part
     const bool p128 = p.n_parts == 0 || (p.part_n % 128) == 0, p160 = p.n_parts == 0 || (p.part_n % 160) == 0;
-    bool big = tiles128 >= 128 && (padded - p.Nc) * 4 <= p.Nc && p128;
-    bool deep = tiles64 < 512;
-    if (forced_tile() == 0) big = true;
-    if (forced_tile() == 2) big = false;
+    const bool big = tiles128 >= 128 && (padded - p.Nc) * 4 <= p.Nc && p128;
     // (8-wave workgroups — 128×256 as 2×4 waves, 256×128 as 4×2 waves, one per CU, 26 % fewer L2→LDS bytes per flop —
     //  are supported by the template (WM parameter) and were measured: correct, 5–100 % slower on every hot-path shape,
     //  e.g. 16384×320×2560 54 vs 50 µs; not instantiated.)
@@ -1397,23 +1345,15 @@ int launch_pipe(const GemmParams& p_in, hipStream_t stream) {
         // level): 128×160 tiles waste no MFMA, LDS or L2→LDS traffic on padding columns (128-wide tiles pad 320 to 384)
         // and re-read the X panel twice instead of three times; two workgroups still share a CU (77.8 KB each)
         const int64_t tiles160 = ((p.M + 127) / 128) * (p.Nc / 160);
-        bool w160 = (p.Nc % 160) == 0 && ((p.Nc % 128) != 0 || !p128) && tiles160 >= 128 && p160;
-        if (forced_tile() == 7) w160 = (p.Nc % 160) == 0;
-        if (forced_tile() == 0 || forced_tile() == 2 || forced_tile() == 1) w160 = false;  // 1: the 128|64-square rules only
+        const bool w160 = (p.Nc % 160) == 0 && ((p.Nc % 128) != 0 || !p128) && tiles160 >= 128 && p160;
         // ... and when that grid has fewer than 384 tiles (the 320-wide projections at 16384 rows: 256 tiles, one per CU),
         // 64×160 tiles double the count — two workgroups per CU overlap each other's fixed phases: 16384×320×320
         // 12.1 → 11.4 µs, 16384×1280→320 27.9 → 27.0 (round 3; wider outputs lose: 16384×320→1280 26.4 → 30.6)
-        bool half160 = w160 && tiles160 < 384;
-        if (forced_tile() == 8) half160 = (p.Nc % 160) == 0;
-        if (forced_tile() == 7) half160 = false;
-        if (half160) return launch_tile<T, 64, 160, true, 2, 4>(p, stream);
+        if (w160 && tiles160 < 384) return launch_tile<T, 64, 160, true, 2, 4>(p, stream);
         if (w160) return launch_tile<T, 128, 160, true, 2, 4>(p, stream);
         // 128×128 grids of 128..255 tiles leave a third of the CUs idle (4096×640×640: 160 tiles): 64×128 tiles double the
         // count at 3/4 of the flops per staged byte — 12.5 → 11.0 µs there, 32.8 → 28.2 µs at K = 2560
-        bool mid = big && tiles128 < 256;
-        if (forced_tile() == 9) mid = true;
-        if (forced_tile() == 0 || forced_tile() == 2 || forced_tile() == 1) mid = false;
-        if (mid) return launch_tile<T, 64, 128, true, 2, 4>(p, stream);
+        if (big && tiles128 < 256) return launch_tile<T, 64, 128, true, 2, 4>(p, stream);
         // grids too small for 128-row tiles, measured with the weights COLD (tools/gemm_bench.py --cold-read: in the model every
         // frozen weight comes from HBM): 64×128 tiles behind a 3-stage ring (two workgroups per CU, two K-steps in flight)
         // for 64..127-tile grids — 1024×1280×1280: 17.3 → 15.0 µs, the grouped q/k/v backward at 1024 rows 39 → 34 µs
@@ -1421,28 +1361,20 @@ int launch_pipe(const GemmParams& p_in, hipStream_t stream) {
         //  is SLOWER, 15.4 → 16.0 → 16.3 µs: a lone workgroup is not waiting on prefetch depth)
         // (also measured on this grid, round 3: the same tile as ONE 8-wave workgroup — 4×2 waves, two per SIMD instead of
         //  one — 15.1 vs 15.2 µs behind 3 stages, 19.2 behind 2: neither the wave count nor a ring deeper than 3 moves it)
-        if (!big && tiles128 >= 64 && (p.Nc % 128) == 0 && p128 && stg_env == 0 && forced_tile() < 0)
-            return launch_tile<T, 64, 128, true, 3, 4>(p, stream);
-    }
-    if constexpr (sizeof(T) == 2) {
+        if (!big && tiles128 >= 64 && (p.Nc % 128) == 0 && p128) return launch_tile<T, 64, 128, true, 3, 4>(p, stream);
         // chip-filling grids whose width divides by 128 AND 160: the tile whose grid wastes less of its last round
-        if (big && p160 && tiles128 >= 256 && forced_tile() < 0 && stg_env == 0 && gate_tile_width((p.M + 127) / 128, p.Nc, false) == 160)
+        if (big && p160 && tiles128 >= 256 && gate_tile_width((p.M + 127) / 128, p.Nc, false) == 160)
             return launch_tile<T, 128, 160, true, 2, 4>(p, stream);
     }
-    if (big) {
-        // (a 3-stage ring on grids of <= 256 tiles — one workgroup per CU anyway — was measured: no gain, 12.8 → 13.6 µs on
-        //  4096×640×640; a lone workgroup is paced by the CU's vector-memory path issuing its own DMAs, not by latency)
-        if (stg_env == 3) return launch_tile<T, 128, 128, true, 3>(p, stream);
-        return launch_tile<T, 128, 128, true, 2, 4>(p, stream);
-    }
-    if (stg_env == 2) deep = false;
-    if (stg_env == 3) deep = true;
+    // (a 3-stage ring on grids of <= 256 tiles — one workgroup per CU anyway — was measured: no gain, 12.8 → 13.6 µs on
+    //  4096×640×640; a lone workgroup is paced by the CU's vector-memory path issuing its own DMAs, not by latency)
+    if (big) return launch_tile<T, 128, 128, true, 2, 4>(p, stream);
     // long contractions on grids that leave at most ~1 workgroup per CU: only prefetch depth hides the L2/HBM latency
     // of each K-step there (4 stages = 2 workgroups per CU, 6 stages = 1)
+    const bool deep = tiles64 < 512;
     const int nk = (p.Kc * (int)sizeof(T) + kRowBytes - 1) / kRowBytes;
     int ring = deep ? 3 : 2;
     if (deep && nk >= 8) ring = 4;  // (6 stages at one workgroup per CU lost to 4 stages at two once the weights are cold)
-    if (stg_env == 4) ring = stg_env;
     switch (ring) {
         case 4: return launch_tile<T, 64, 64, true, 4>(p, stream);
         case 3: return launch_tile<T, 64, 64, true, 3>(p, stream);

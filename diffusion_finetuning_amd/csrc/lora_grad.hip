@@ -18,7 +18,6 @@
 // latency-bound ones.  Operands may be strided views (a slice of a grouped projection's output) and the
 // rank columns of one problem may belong to several layers (grouped q/k/v: U is [M, 3r], three gA outputs).
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -473,9 +472,10 @@ __global__ __launch_bounds__(256) void fold_partials_kernel(const int64_t* range
 // profiles/README.md): 512 rows per block (at most 64 blocks) and strips of 32 chunks (256 columns in 16-bit types) —
 // many narrow workgroups balance the chip better than few wide ones (541 µs at 256 rows × 256 chunks, 397 µs here, 5.0 TB/s)
 // and halve the partial sums the fold has to read.
+constexpr int kGradRows = 512;    // rows per block
+constexpr int kGradStrip = 32;    // chunks per strip (<= 256)
 int plan_row_blocks(int64_t M) {
-    static const int rows = [] { const char* e = getenv("LORA_GRAD_ROWS"); return e ? atoi(e) : 512; }();  // tuning knob
-    int64_t nb = M / rows;
+    int64_t nb = M / kGradRows;
     if (nb < 1) nb = 1;
     if (nb > LORA_GRAD_MAX_BLOCKS) nb = LORA_GRAD_MAX_BLOCKS;
     return (int)nb;
@@ -486,8 +486,7 @@ bool plan_item(GradItem& q, int nb) {
     constexpr int VEC = ElemTraits<T>::kVec;
     if (q.C % VEC != 0 || !aligned16(q.S) || (q.s_stride % VEC) != 0) return false;
     const int chunks = q.C / VEC;
-    static const int cl_cap = [] { const char* e = getenv("LORA_GRAD_STRIP"); return e ? atoi(e) : 32; }();  // tuning knob, <= 256
-    q.strips = (chunks + cl_cap - 1) / cl_cap;  // smallest strip count that respects the cap, then even widths
+    q.strips = (chunks + kGradStrip - 1) / kGradStrip;  // smallest strip count that respects the cap, then even widths
     q.CL = (chunks + q.strips - 1) / q.strips;
     q.nb = nb;
     q.rows_per_block = (int)((q.M + nb - 1) / nb);
@@ -495,32 +494,24 @@ bool plan_item(GradItem& q, int nb) {
     return true;
 }
 
-// smallest rank class that goes to the matrix-core kernel (16-bit operands only).  All of them by default: on the 288
-// problems of an SD1.5 step (tools/gemm_bench.py --grads, GB_RANK) it takes 372 / 403 / 417 µs at rank 4 / 8 / 16 where
-// the VALU kernel takes 396 / 657 / 1626.  LORA_GRAD_MFMA=99 sends everything back to the VALU kernel (A/B knob).
-int mfma_min_rank() {
-    static const int v = [] { const char* e = getenv("LORA_GRAD_MFMA"); return e ? atoi(e) : 4; }();
-    return v;
-}
-
+// 16-bit operands go to the matrix-core kernel at every rank class: on the 288 problems of an SD1.5 step
+// (tools/gemm_bench.py --grads, GB_RANK) it takes 372 / 403 / 417 µs at rank 4 / 8 / 16 where the VALU kernel takes
+// 396 / 657 / 1626.  fp32 operands take the VALU kernel.
 template <typename T>
 int launch_batch(const GradBatch& b, int rp, hipStream_t stream) {
-    constexpr int VEC = ElemTraits<T>::kVec;
-    const int lds = 256 * 4 * VEC * 4 + kChunkRows * rp * 4;  // reduction image + the staged P rows
     const dim3 grid((unsigned)b.first_block[b.n]);
     if constexpr (sizeof(T) == 2) {
-        if (rp >= mfma_min_rank()) {
-            const int id = rp == 4 ? PK_GRAD_R4 : (rp == 8 ? PK_GRAD_R8 : PK_GRAD_R16);
-            LORA_LAUNCH(id, (lora_grad_mfma_kernel<T>), grid, dim3(256), 0, stream, b);
-            LORA_LAUNCH_CHECK();
-            return LORA_OK;
+        const int id = rp == 4 ? PK_GRAD_R4 : (rp == 8 ? PK_GRAD_R8 : PK_GRAD_R16);
+        LORA_LAUNCH(id, (lora_grad_mfma_kernel<T>), grid, dim3(256), 0, stream, b);
+    } else {
+        constexpr int VEC = ElemTraits<T>::kVec;
+        const int lds = 256 * 4 * VEC * 4 + kChunkRows * rp * 4;  // reduction image + the staged P rows
+        switch (rp) {
+            case 4: LORA_LAUNCH(PK_GRAD_R4, (lora_grad_kernel<T, 4>), grid, dim3(256), lds, stream, b); break;
+            case 8: LORA_LAUNCH(PK_GRAD_R8, (lora_grad_kernel<T, 8>), grid, dim3(256), lds, stream, b); break;
+            case 12: LORA_LAUNCH(PK_GRAD_R16, (lora_grad_kernel<T, 12>), grid, dim3(256), lds, stream, b); break;
+            default: LORA_LAUNCH(PK_GRAD_R16, (lora_grad_kernel<T, 16>), grid, dim3(256), lds, stream, b); break;
         }
-    }
-    switch (rp) {
-        case 4: LORA_LAUNCH(PK_GRAD_R4, (lora_grad_kernel<T, 4>), grid, dim3(256), lds, stream, b); break;
-        case 8: LORA_LAUNCH(PK_GRAD_R8, (lora_grad_kernel<T, 8>), grid, dim3(256), lds, stream, b); break;
-        case 12: LORA_LAUNCH(PK_GRAD_R16, (lora_grad_kernel<T, 12>), grid, dim3(256), lds, stream, b); break;
-        default: LORA_LAUNCH(PK_GRAD_R16, (lora_grad_kernel<T, 16>), grid, dim3(256), lds, stream, b); break;
     }
     LORA_LAUNCH_CHECK();
     return LORA_OK;
@@ -692,7 +683,6 @@ extern "C" int64_t lora_grad_plan_bytes(const lora_grad_problem* problems, int n
 extern "C" int lora_grad_plan(const lora_grad_problem* problems, int n, int dtype, void* plan_host, int64_t plan_bytes,
                               int* n_items, int* n_blocks) {
     if (!problems || n < 1 || !plan_host || !n_items || !n_blocks) return LORA_E_BADARG;
-    if (mfma_min_rank() > 4) return LORA_E_UNSUPPORTED;  // (A/B knob: the VALU kernels only exist in the table-in-arguments form)
     for (int i = 0; i < n; ++i) {
         const int st = check_problem(problems[i]);
         if (st != LORA_OK) return st;

@@ -15,7 +15,6 @@ and the optimizer is two launches over the slab.  Data parallelism is one proces
 `torch.distributed` (backend "nccl" = RCCL over xGMI); only the LoRA gradients (≈5 MB at rank 4) ever cross GPUs.
 """
 import math
-import os
 from typing import Iterable, List, Optional, Sequence, Tuple
 
 import torch
@@ -181,8 +180,6 @@ class LoraSlab:
         self.offsets = []
         self._pending, self._keep, self._ran = {}, [], {}
         self._range_tables = {}
-        # factor gradients of a pass in one launch (lora_grad_planned); off: <= 28 problems per launch (DFA_ONE_LAUNCH_GRADS=0: A/B knob)
-        self.one_launch_grads = os.environ.get("DFA_ONE_LAUNCH_GRADS", "1") != "0"
         self._plan_need, self._recording_plans, self._recorded_plans = {}, {}, []
         self.layer_rows = {}  # layer index -> (rows M, dX produced) of its last backward (accounting: survey_work)
         # layers whose input is the text encoder's output (diffusers names the cross-attention of a transformer block attn2):
@@ -384,8 +381,6 @@ class LoraSlab:
         return plans
 
     def _launch_planned(self, problems, dt) -> bool:
-        if not self.one_launch_grads:
-            return False
         host = None
         if torch.cuda.is_current_stream_capturing():
             host = self._recording_plans.pop(dt, None)  # one buffer per (recording, dtype): a second flush of the pass declines

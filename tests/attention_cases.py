@@ -2,15 +2,15 @@
 
 No GPU and no library: tests/test_gpu_attention_cores.py runs every entry against float64 math;
 tests/test_attention_coverage_host.py checks on the CPU that the keys are exactly the dispatch-table instantiations of
-csrc/attn_flash.hip and csrc/attn_ctx.hip that the default `plan_flash` / `plan_ctx` can select, so a new instantiation
-with no test shape fails the CPU suite.
+csrc/attn_flash.hip and csrc/attn_ctx.hip, and that `plan_flash` / `plan_ctx` select every one of them, so a new
+instantiation with no test shape, or one no plan selects, fails the CPU suite.
 
 Keys name the kernel's template arguments (the element type aside — every entry runs in f16 and bf16):
   ("flash_fwd", KS, DF, RB, ONES)   attn_flash_fwd_kernel
   ("flash_bwd", KS, DF, RBQ, NKW)   attn_flash_dq_kernel<KS, DF, RBQ> + attn_flash_dkdv_kernel<KS, DF, NKW, …>
   ("ctx_fwd", KS, DF, NKF)          attn_ctx_fwd_kernel
   ("ctx_bwd", KS, DF, NKF)          attn_ctx_bwd_kernel (+ attn_ctx_reduce_kernel)
-Values are (B, Tq, Tk, H, d) shapes.  The FLASH_NKW / FLASH_RB / FLASH_ONES environment knobs stay unset.
+Values are (B, Tq, Tk, H, d) shapes.
 """
 
 FLASH_FWD, FLASH_BWD, CTX_FWD, CTX_BWD = "flash_fwd", "flash_bwd", "ctx_fwd", "ctx_bwd"
@@ -58,17 +58,8 @@ INSTANTIATIONS = {
     (CTX_BWD, 5, 5, 6): (2, 90, 96, 2, 160),
 }
 
-# Compiled but unreachable under the default plan (the coverage test subtracts these from what it parses):
-UNREACHABLE = {
-    (FLASH_FWD, 2, 3, 2, False), (FLASH_FWD, 2, 3, 2, True),  # only with FLASH_RB=2 (tools/flash_check.py)
-    (FLASH_FWD, 2, 4, 2, False), (FLASH_FWD, 2, 4, 2, True),  # only with FLASH_RB=2
-    (FLASH_BWD, 2, 3, 2, 2),  # only with FLASH_NKW=2
-    (FLASH_BWD, 2, 4, 2, 4),  # no plan selects it: heads of 56 … 64 always take NKW = 2
-}
-
-
 def flash_keys(d):
-    """(forward key, backward key) that the default plan_flash / launch_flash_fwd pick for head dim d (8 … 160, d % 8 == 0)."""
+    """(forward key, backward key) that plan_flash / launch_flash_fwd pick for head dim d (8 … 160, d % 8 == 0)."""
     if d <= 48:
         ks, df, rb, rbq, nkw = 2, 3, 4, 2, 4
     elif d <= 64:
@@ -86,7 +77,7 @@ def flash_keys(d):
 
 
 def ctx_keys(Tk, d):
-    """(forward key, backward key) that the default plan_ctx picks, or None where attn_ctx_supported refuses."""
+    """(forward key, backward key) that plan_ctx picks, or None where attn_ctx_supported refuses."""
     if not (1 <= Tk <= 128 and 8 <= d <= 160 and d % 8 == 0) or (d > 96 and Tk > 96):
         return None
     nkf = 6 if Tk <= 96 else 8

@@ -50,6 +50,15 @@ def test_product_does_not_import_the_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), f
 
 
+def test_native_library_reads_no_environment():
+    """What kernel a shape gets, and what it computes, follows from the call alone: no environment variable changes either
+    in the shipped library.  Diagnostic kernels are compile-time variants (-D flags, build_native --variant)."""
+    csrc = os.path.join(ROOT, "diffusion_finetuning_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        src = open(os.path.join(csrc, f)).read()
+        assert "getenv" not in src, f
+
+
 def test_no_mfma_result_is_read_early_across_a_branch(tmp_path):
     """hipcc pads the distance between an MFMA and the first vector instruction that reads its destination registers along
     the LAYOUT order of the blocks only: a conditional branch that skips the padded block can land on a reader that comes

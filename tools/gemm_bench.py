@@ -1,5 +1,5 @@
 """Dev tool: per-shape device time of the hot-path kernels (dispatch-attached events).
-usage: [LORA_FORCE_TILE=0|2] [LORA_FORCE_STAGES=2|3|4|6] python tools/gemm_bench.py [--grouped] [--grads] [--ref]"""
+usage: python tools/gemm_bench.py [--grouped] [--grads] [--ref]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -35,7 +35,6 @@ def run(fn, iters=20, warm=None):
     return 1e3 * tot / iters, n / iters, keys
 def per_shape():
     dtype = torch.float16
-    print("tile", os.environ.get("LORA_FORCE_TILE"), "stages", os.environ.get("LORA_FORCE_STAGES"))
     sel = os.environ.get("GB_SHAPES")
     for (M,K,N) in ([SHAPES[int(i)] for i in sel.split(",")] if sel else SHAPES):
         x = torch.randn(M,K,device=dev).to(dtype); w = (torch.randn(N,K,device=dev)/K**0.5).to(dtype); wt = w.t().contiguous()

@@ -34,7 +34,7 @@ def main():
     lib.lora_debug_stamps.argtypes = [vp, ci]
     lib.lora_linear_geglu_fwd.argtypes = [vp] * 8 + [i64, ci, ci, ci, cf, ci, vp]
     gated = "--geglu" in sys.argv  # N = 2·F: the `proj` forward with the gate in its epilogue
-    splitk = "--splitk" in sys.argv  # long contractions: the launch cuts K into slices (workspace handed over); LORA_SPLIT_AFFINITY=0|1
+    splitk = "--splitk" in sys.argv  # long contractions: the launch cuts K into slices (workspace handed over)
     lib.lora_linear_fwd_ws.argtypes = [vp] * 9 + [i64, ci, ci, ci, cf, ci, vp, i64, vp]
     lib.lora_gemm_workspace_bytes.restype = i64
     lib.lora_gemm_workspace_bytes.argtypes = [i64, ci, ci, ci]
@@ -95,7 +95,7 @@ def main():
             life = (s[:, 9] - s[:, 0]) / 100.0
             kk = np.median((s[:, 8] - s[:, 1])[life > 0] / life[life > 0])
             def med(v): return f"median {np.median(v):6.2f} p90 {np.percentile(v, 90):6.2f} max {v.max():6.2f}"
-            print(f"--- split-K {M}x{K}x{N} (affinity {os.environ.get('LORA_SPLIT_AFFINITY', '0')}): {len(s)} workgroups, {int(last.sum())} last "
+            print(f"--- split-K {M}x{K}x{N}: {len(s)} workgroups, {int(last.sum())} last "
                   f"arrivers; kernel span {((s[:, 9] - wall0) / 100.0).max():.2f} us; starts up to {((s[:, 0] - wall0) / 100.0).max():.2f} us")
             print(f"    to first stage landed   {med((s[:, 3] - s[:, 1]) / kk)}")
             print(f"    main loop               {med((s[:, 4] - s[:, 3]) / kk)}")
