@@ -85,6 +85,9 @@ SIGNATURES = {
     "embed_rows_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "embed_rows_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp]),
     "lora_adamw_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
+    "ti_rows_grad": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _vp]),
+    "ti_rows_adamw_decay": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32,
+                                   _vp]),
     "geglu_linear_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "geglu_gate_fwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "geglu_gate_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
@@ -617,6 +620,35 @@ def lora_adamw_rows(param, grad, exp_avg, exp_avg_sq, active, norm_in, grad_mul,
     _check(lib().lora_adamw_rows(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(active), V, D, _ptr(norm_in),
                                  float(grad_mul), float(max_norm), float(lr), float(beta1), float(beta2), float(eps),
                                  float(weight_decay), int(step), _stream(param)), "lora_adamw_rows")
+
+
+TI_MAX_ROWS = 64  # LORA_TI_MAX_ROWS
+
+
+def ti_rows_grad(d_rows, ids, slot_ids, grad, accumulate: bool = True) -> None:
+    """grad [P, D] fp32 (+)= for each slot s the sum of the rows d_rows[p] with ids[p] == slot_ids[s], positions in ascending
+    order (include/lora_hip.h: ti_rows_grad)."""
+    _require_device(d_rows, ids, slot_ids, grad)
+    P, D = grad.shape
+    assert grad.dtype == torch.float32 and grad.is_contiguous() and slot_ids.dtype == torch.int64 and slot_ids.numel() == P
+    assert d_rows.is_contiguous() and ids.is_contiguous() and ids.dtype == torch.int64 and d_rows.numel() == ids.numel() * D
+    _check(lib().ti_rows_grad(_ptr(d_rows), _ptr(ids), ids.numel(), D, _ptr(slot_ids), P, _ptr(grad), dtype_code(d_rows.dtype),
+                              int(accumulate), _stream(grad)), "ti_rows_grad")
+
+
+def ti_rows_adamw_decay(table, slot_ids, grad, exp_avg, exp_avg_sq, grad_mul, lr, beta1, beta2, eps, weight_decay, step: int,
+                        decay_lambda: float, target_norm: float = 0.4) -> None:
+    """AdamW + clip_ti_decay (decay_lambda < 0: no decay) on the rows table[slot_ids] in place (include/lora_hip.h:
+    ti_rows_adamw_decay)."""
+    _require_device(table, slot_ids, grad, exp_avg, exp_avg_sq)
+    V, D = table.shape
+    P = slot_ids.numel()
+    assert table.dtype == torch.float32 and table.is_contiguous() and slot_ids.dtype == torch.int64
+    for t in (grad, exp_avg, exp_avg_sq):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (P, D)
+    _check(lib().ti_rows_adamw_decay(_ptr(table), V, D, _ptr(slot_ids), P, _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                     float(grad_mul), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                     int(step), float(decay_lambda), float(target_norm), _stream(table)), "ti_rows_adamw_decay")
 
 
 def geglu_gate_fwd(y2):

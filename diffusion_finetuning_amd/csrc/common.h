@@ -76,6 +76,19 @@ template <typename T> __device__ __forceinline__ float gelu_grad_f(float g) {  /
     }
 }
 
+// torch.optim.AdamW (single-tensor path) on one element, in torch's order:
+//   p *= 1 - lr·wd ; m = lerp(m, g, 1-β1) ; v = β2·v + (1-β2)·g² ; denom = sqrt(v)/sqrt(1-β2^t) + eps ; p -= (lr/(1-β1^t)) · m/denom
+// decay = 1 - lr·wd, step_size = lr/(1-β1^t), bc2_sqrt = sqrt(1-β2^t).  The one copy of this arithmetic: optim.hip (slab, table)
+// and embed.hip (placeholder rows of textual inversion).
+__device__ __forceinline__ void adamw_element(float& p, float& m, float& v, float g, float decay, float step_size, float beta1,
+                                              float beta2, float bc2_sqrt, float eps) {
+    p = p * decay;
+    m = m + (g - m) * (1.f - beta1);
+    v = beta2 * v + (1.f - beta2) * g * g;
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    p = p - step_size * (m / denom);
+}
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // Zeroes the 16-byte ticket header of a reduction workspace with a KERNEL, not hipMemsetAsync: inside a captured

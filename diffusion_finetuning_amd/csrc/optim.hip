@@ -91,9 +91,7 @@ struct AdamParams {
     float bc1, bc2_sqrt;  // 1-β1^t, sqrt(1-β2^t); bc1 <= 0: compute them from the device step counter norm_in[2]
 };
 
-// torch.optim.AdamW (single-tensor path) per element, in this order:
-//   p *= 1 - lr·wd ; m = lerp(m, g, 1-β1) ; v = β2·v + (1-β2)·g² ;
-//   denom = sqrt(v)/sqrt(1-β2^t) + eps ; p -= (lr/(1-β1^t)) · m/denom
+// torch.optim.AdamW (single-tensor path) per element: adamw_element (common.h)
 __global__ __launch_bounds__(256) void adamw_kernel(AdamParams a) {
     float clip = 1.f;
     if (a.norm_in) {
@@ -114,12 +112,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamParams a) {
     const float decay = 1.f - a.lr * a.wd;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
         const float g = a.g[i] * gm;
-        float p = a.p[i] * decay;
-        float m = a.m[i];
-        m = m + (g - m) * (1.f - a.beta1);
-        const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
-        const float denom = sqrtf(v) / bc2_sqrt + a.eps;
-        p = p - step_size * (m / denom);
+        float p = a.p[i], m = a.m[i], v = a.v[i];
+        adamw_element(p, m, v, g, decay, step_size, a.beta1, a.beta2, bc2_sqrt, a.eps);
         a.p[i] = p;
         a.m[i] = m;
         a.v[i] = v;
@@ -169,12 +163,8 @@ __global__ __launch_bounds__(256) void adamw_rows_kernel(AdamParams a, const uns
         for (int c = threadIdx.x; c < D; c += 256) {
             const int64_t i = base + c;
             const float g = a.g[i] * gm;
-            float p = a.p[i] * decay;
-            float m = a.m[i];
-            m = m + (g - m) * (1.f - a.beta1);
-            const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
-            const float denom = sqrtf(v) / bc2_sqrt + a.eps;
-            p = p - step_size * (m / denom);
+            float p = a.p[i], m = a.m[i], v = a.v[i];
+            adamw_element(p, m, v, g, decay, step_size, a.beta1, a.beta2, bc2_sqrt, a.eps);
             a.p[i] = p;
             a.m[i] = m;
             a.v[i] = v;

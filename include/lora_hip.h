@@ -406,6 +406,28 @@ int lora_adamw_rows(float* param, const float* grad, float* exp_avg, float* exp_
                     float weight_decay, int step, void* stream);
 
 /*
+ * Placeholder rows of textual inversion — train_inversion of lora_diffusion/cli_lora_pti.py (:290-346), the first phase of
+ * train() (:651-687): only the P placeholder rows `slot_ids` [P] (int64, device) of the fp32 token table ever change, because
+ * every other row is restored from a clone after each optimizer step (:280,344-346).  P <= LORA_TI_MAX_ROWS.
+ *   ti_rows_grad        : grad[s, :] (+)= Σ_{p : ids[p] == slot_ids[s]} dE[p, :], p < n, positions added in ascending order by ONE
+ *                         owner workgroup per (slot, column chunk): no atomics, bit-reproducible.  dE [n, D] in `dtype`; grad
+ *                         [P, D] fp32; accumulate = 0 writes the sum (zero for a slot whose token does not occur).  Replaces the
+ *                         dense backward of `get_input_embeddings()` (:299-307): the [V, D] table gradient is never formed.
+ *   ti_rows_adamw_decay : for each slot s, on w = table[slot_ids[s], :] in place — torch.optim.AdamW (lora_adamw_step's
+ *                         arithmetic, g = grad_mul·grad[s], bias correction with `step` >= 1; :311-313, created at :651-657),
+ *                         then, when decay_lambda >= 0, clip_ti_decay (:318-336):
+ *                             pre = ‖w‖ ;  w ← w / max(pre, 1e-12) · (pre + decay_lambda·(target_norm − pre))
+ *                         (the reference: target_norm 0.4, decay_lambda = min(1, 100·lr)).  exp_avg / exp_avg_sq [P, D] fp32.
+ *                         Rows not named in slot_ids are neither read nor written (the reference's restore of :344-346).
+ */
+#define LORA_TI_MAX_ROWS 64
+int ti_rows_grad(const void* dE, const int64_t* ids, int64_t n, int D, const int64_t* slot_ids, int P, float* grad, int dtype,
+                 int accumulate, void* stream);
+int ti_rows_adamw_decay(float* table, int64_t V, int D, const int64_t* slot_ids, int P, const float* grad, float* exp_avg,
+                        float* exp_avg_sq, float grad_mul, float lr, float beta1, float beta2, float eps, float weight_decay,
+                        int step, float decay_lambda, float target_norm, void* stream);
+
+/*
  * Short-context attention core  O = softmax(Q·Kᵀ·scale)·V  per head, for at most 128 keys: the cross-attention
  * (`attn2`) between the to_q/to_k/to_v and to_out LoRA linears (diffusers CrossAttention.forward, the
  * caller of the layers wrapped by lora_diffusion/lora.py:137-183).  Tensors keep the layout those linears produce
