@@ -2,9 +2,13 @@
 """Headline benchmark: images/s of one full SD1.5 LoRA train step (rank 4, batch 4/GPU, 512² → 64×64×4 latents,
 fp16 storage/compute with fp32 accumulate and fp32 master LoRA), synthetic latents, 1..8 GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  `--full` adds what takes runs
+of its own: the event-timed roofline pass and launch floor, the replayed step's tail time, configs 3-5, the unchanged-trainer
+route, the exchange probe and the CPU baseline.
 
 A step = add_noise → UNet forward (144 fused LoRA linears) → fused MSE → backward (fused dX + factor-grad
 kernels) → [RCCL all-reduce of the 5 MB LoRA gradient slab] → fused clip + AdamW.  Inputs for every step are
@@ -31,29 +35,34 @@ HBM_ACHIEVABLE_GBS = 6290.0  # "fraction = /8.0 TB/s (also show /
 MFMA_PEAK_TFLOPS = {"f16": 2500.0, "bf16": 2500.0, "f32": 157.3}  # dense peaks, same guide
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS),
-                    help="BASELINE.json config to time as the headline (2 = the metric's own; the default run appends 3, 4, 5 "
+                    help="BASELINE.json config to time as the headline (2 = the metric's own; --full appends 3, 4, 5 "
                          "as `extra_configs`)")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step (train_batch_size); default: the config's")
     ap.add_argument("--rank-r", type=int, default=None)
     ap.add_argument("--latent", type=int, default=None, help="latent height=width (512² images → 64)")
-    ap.add_argument("--no-extra", action="store_true", help="headline only: no extra_configs, no drop-in route")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline pass, launch floor, tail time, "
+                         "extra_configs, drop-in route, exchange probe, CPU baseline (the --no-* switches below leave parts out)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no extra_configs, no drop-in route, no exchange probe")
     ap.add_argument("--drop-in", action="store_true",
                     help="time ONLY the unchanged reference trainer loop (no LoraTrainer): what extra.drop_in reports")
     ap.add_argument("--mask", action="store_true", help="masked loss (cli_lora_pti.py:222-247) on a random binary mask")
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16", "f32"])
     ap.add_argument("--no-conv-autotune", action="store_true",
                     help="caller side: leave MIOpen in immediate mode for the UNet's convolutions (see conv_autotune)")
-    ap.add_argument("--no-prof", action="store_true", help="do not attach kernel events in the timed region")
-    ap.add_argument("--no-floor", action="store_true", help="skip the launch-floor pass (empty kernels at every hot-path launch site)")
+    ap.add_argument("--no-prof", action="store_true",
+                    help="with --full: no roofline pass (kernel events on a second pass over the K steps), hence no launch floor")
+    ap.add_argument("--no-floor", action="store_true",
+                    help="with --full: skip the launch-floor pass (empty kernels at every hot-path launch site)")
     ap.add_argument("--no-graph", action="store_true",
                     help="launch every kernel from the host each step instead of replaying the recorded hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
     ap.add_argument("--host-noise", action="store_true",
                     help="feed pre-drawn noise / timesteps instead of drawing them on the device inside the step")
     ap.add_argument("--cpu-steps", type=int, default=3,
@@ -68,7 +77,7 @@ def parse():
                     help="after the timed steps of the headline workload, rank 0 writes what the LAST timed step left its caller "
                          "as DIR/<name>.npy (float32, at most 64 MB in all; see dump_outputs): the loss, the trained parameters "
                          "and their gradients — for comparing two builds output for output")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and (args.drop_in or args.exchange_probe or args.stub_body):
@@ -472,7 +481,8 @@ def _is_lora_kind(name):
 
 
 def run_workload(args, cfg_id, rank, world, device, dist, profile=True):
-    """Build the workload of BASELINE config `cfg_id`, time args.steps steps of it, optionally run the event pass."""
+    """Build the workload of BASELINE config `cfg_id`, time args.steps steps of it; with --full also time the replayed step's
+    tail and, if `profile`, run the event pass and the launch floor."""
     from diffusion_finetuning_amd import _native as nat
     from diffusion_finetuning_amd.trainer import LoraTrainer
 
@@ -610,9 +620,9 @@ def run_workload(args, cfg_id, rank, world, device, dist, profile=True):
     # What a step does OUTSIDE the recording, per rank: [RCCL all-reduce of the slab] → clip norm + AdamW → re-pack of the
     # compute-dtype factors (+ the token-table row sum of config 5).  Timed with events in a few extra replayed steps after the
     # timed region (not part of `value`); on one GPU the exchange is empty, so this is the floor the 8-GPU step adds its
-    # all-reduce to.
+    # all-reduce to.  --full only.
     tail_ms = None
-    if trainer.capture_graph and trainer._graph is not None:
+    if args.full and trainer.capture_graph and trainer._graph is not None:
         trainer.tail_events = []
         for i in range(args.warmup, args.warmup + min(5, args.steps)):
             run_step(i)
@@ -648,8 +658,8 @@ def run_workload(args, cfg_id, rank, world, device, dist, profile=True):
         nat.prof_null_mode(True)
         try:
             nat.prof_enable(FLOOR_STEPS * 900)
-            for i in range(args.warmup, args.warmup + FLOOR_STEPS):
-                run_step(i)
+            for i in range(FLOOR_STEPS):  # (the timed steps' batches again, cycled: --steps may be fewer than FLOOR_STEPS)
+                run_step(args.warmup + i % args.steps)
             torch.cuda.synchronize()
             floor = {k: {"launches": v["launches"] / FLOOR_STEPS, "ms": v["ms"] / FLOOR_STEPS} for k, v in nat.prof_collect().items()}
         finally:
@@ -845,7 +855,7 @@ def main():
                               **{("value" if k == "images_s" else k): v for k, v in drop_in_route(args, device).items()}}), flush=True)
         return
 
-    head = run_workload(args, args.config, rank, world, device, dist, profile=not args.no_prof)
+    head = run_workload(args, args.config, rank, world, device, dist, profile=args.full and not args.no_prof)
     cfg, elapsed, prof, elapsed_prof = head["cfg"], head["elapsed"], head["prof"], head["elapsed_prof"]
 
     if rank == 0:
@@ -955,7 +965,7 @@ def main():
             add_launch_floor(roof, head.get("launch_floor") or {}, tot_ms)
             result["roofline"] = roof
             result["hot_path"] = hot_path_summary(prof, args.steps, elapsed_prof)
-        if world == 1 and not args.no_extra and args.config == 2:
+        if world == 1 and args.full and not args.no_extra and args.config == 2:
             extras = []
             for cid in (3, 4, 5):
                 try:
@@ -1004,13 +1014,13 @@ def main():
                     result["extra"] = {"drop_in": drop_in_route(args, device)}
                 except Exception as exc2:
                     result["extra"] = {"drop_in": {"error": repr(exc2)}}
-        if world == 1 and not args.no_extra and args.config == 2:
+        if world == 1 and args.full and not args.no_extra and args.config == 2:
             try:
                 result.setdefault("extra", {})["exchange_probe"] = exchange_probe(args, device)
             except Exception as exc:  # (never at the headline's expense)
                 log(f"exchange probe failed: {exc!r}")
                 result.setdefault("extra", {})["exchange_probe"] = {"error": repr(exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             torch.cuda.empty_cache()
             result["cpu_baseline"] = cpu_baseline(CONFIGS[2]["rank"], CONFIGS[2]["latent"], args.cpu_steps)
         print(json.dumps(result), flush=True)

@@ -1,6 +1,7 @@
 """`python bench.py --gpus N` must start N ranks by itself (the driver's N=1 call and its torch.distributed.run call both
 keep working).  The rank body is stubbed (`--stub-body`): gloo on the CPU, no GPU, so this runs in the build container.
-Also: what bench.py writes with --dump-outputs (the writer on the CPU, the real body's files on the GPU)."""
+Also: what bench.py writes with --dump-outputs (the writer on the CPU, the real body's files on the GPU), and what a plain run
+leaves to --full."""
 import json
 import os
 import subprocess
@@ -192,6 +193,14 @@ def test_dump_outputs_writes_float32_within_the_budget_with_a_fixed_sample(tmp_p
     assert all(np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy")) for n in arrays)
 
 
+def test_extra_measurements_are_opt_in():
+    """A plain run is the headline figure alone; the passes that take runs of their own wait for --full."""
+    import bench
+
+    assert not bench.parse([]).full and not bench.parse(["--gpus", "1", "--steps", "4", "--warmup", "2"]).full
+    assert bench.parse(["--full"]).full
+
+
 def test_bench_rejects_arguments_it_cannot_honour(tmp_path):
     for argv in (("--steps", "0"), ("--warmup", "-1"), ("--dump-outputs", str(tmp_path), "--drop-in"),
                  ("--dump-outputs", str(tmp_path), "--stub-body", "ok")):
@@ -215,3 +224,34 @@ def test_dump_outputs_of_the_headline_are_its_last_timed_step(tmp_path):
     assert float(got["loss"].reshape(-1)[0]) == line["config"]["final_loss"]
     assert got["lora_params"].shape == got["lora_grads"].shape == (line["config"]["lora_params"],)
     assert np.abs(got["lora_grads"]).max() > 0
+
+
+# what only --full adds to the line; the contract keys are in both
+FULL_ONLY_KEYS = {"roofline", "hot_path", "extra_configs", "extra", "cpu_baseline"}
+CONTRACT_KEYS = {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"}
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_and_full_adds_the_passes():
+    """A plain run prints the contract's keys and none of the --full figures; `--full` (here without the extra configs and the
+    CPU baseline) adds the tail time, the roofline pass and the launch floor to the same headline."""
+    plain = _run("--gpus", "1", "--steps", "2", "--warmup", "1")
+    assert plain.returncode == 0, plain.stderr[-2000:]
+    lines = _json_lines(plain.stdout)
+    assert len(lines) == 1, plain.stdout
+    line = lines[0]
+    assert CONTRACT_KEYS <= set(line) and not FULL_ONLY_KEYS & set(line)
+    assert line["metric"] == "images/s SD1.5 LoRA rank-4 512^2 train step" and line["unit"] == "images/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f16"
+    assert abs(line["value"] - 4 * 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]  # batch 4, one GPU
+    assert line["config"]["tail_ms_per_step"] is None
+    assert "[cfg-3]" not in plain.stderr and "cpu_baseline" not in plain.stderr and "exchange probe" not in plain.stderr
+
+    full = _run("--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline")
+    assert full.returncode == 0, full.stderr[-2000:]
+    fline = _json_lines(full.stdout)[-1]
+    assert CONTRACT_KEYS <= set(fline) and {"roofline", "hot_path"} <= set(fline)
+    assert fline["metric"] == line["metric"] and fline["config"]["lora_params"] == line["config"]["lora_params"]
+    assert fline["roofline"]["step_level"]["launch_floor_ms"] > 0
+    if fline["config"]["hipgraph"]:  # (the tail is timed on replayed steps only)
+        assert fline["config"]["tail_ms_per_step"] > 0

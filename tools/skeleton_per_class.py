@@ -15,8 +15,8 @@ for mode in (0, 1, 2, 3):
         subprocess.run([sys.executable, "-m", "diffusion_finetuning_amd.build_native", "--variant", f"dbg{mode}",
                         f"-DLORA_GEMM_DBG={mode}"], cwd=ROOT, stdout=subprocess.DEVNULL, check=True)
         env["DFA_LIB_PATH"] = os.path.join(ROOT, "diffusion_finetuning_amd", "lib", f"liblora_hip_dbg{mode}.so")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-extra", "--no-cpu-baseline",
-                          "--no-graph"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-extra",
+                          "--no-cpu-baseline", "--no-graph"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, timeout=900)
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
     if not lines:
         print(f"== LORA_GEMM_DBG={mode}: no bench line (exit code {out.returncode})")

@@ -5,7 +5,7 @@ tag=${1:-shapes}
 out=gpurun_out/trace_$tag
 rm -rf "$out"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d "$out/trace" -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-prof > "$out/run.log" 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d "$out/trace" -- python3 bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-prof > "$out/run.log" 2>&1
 t=$(ls "$out"/trace/*/*_kernel_trace.csv | head -1)
 python3 tools/summarize_profile.py shapes "$t" 3 > "$out/shapes.txt"
 rm -rf "$out/trace"
