@@ -106,6 +106,12 @@ SIGNATURES = {
     "attn_flash_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "attn_flash_bwd_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "attn_flash_bwd": (_i32, [_vp] * 10 + [_i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "lora_distill_workspace_bytes": (_i64, [_i64, _i64]),
+    "lora_distill_start": (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _vp]),
+    "lora_distill_diff": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp]),
+    "lora_distill_rayleigh_ritz": (_i32, [_vp, _i32, _i32, _i32, ctypes.c_double, _i32, _vp, _vp]),
+    "lora_distill_finalize": (_i32, [_vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
+    "lora_quantile_clamp": (_i32, [_vp, _i64, _f32, _vp, _vp]),
     "lora_prof_enable": (_i32, [_i32]),
     "lora_prof_collect": (_i32, [ctypes.POINTER(ProfTotals)]),
     "lora_prof_null_mode": (_i32, [_i32]),
@@ -649,6 +655,39 @@ def ti_rows_adamw_decay(table, slot_ids, grad, exp_avg, exp_avg_sq, grad_mul, lr
     _check(lib().ti_rows_adamw_decay(_ptr(table), V, D, _ptr(slot_ids), P, _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
                                      float(grad_mul), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
                                      int(step), float(decay_lambda), float(target_norm), _stream(table)), "ti_rows_adamw_decay")
+
+
+def distill_workspace_bytes(N: int, K: int) -> int:
+    """Bytes of the per-layer workspace of the svd_distill kernels (include/lora_hip.h: lora_distill_*)."""
+    return int(lib().lora_distill_workspace_bytes(N, K))
+
+
+def distill_start(table, n_layers: int, min_nk: int, r: int, seed: int, ws) -> None:
+    _check(lib().lora_distill_start(_ptr(table), n_layers, min_nk, r, seed, _ptr(ws), _stream(ws)), "lora_distill_start")
+
+
+def distill_diff(table, n_layers: int, max_rows: int, transpose: bool, dtype: torch.dtype, ws) -> None:
+    _check(lib().lora_distill_diff(_ptr(table), n_layers, max_rows, int(transpose), dtype_code(dtype), _ptr(ws), _stream(ws)),
+           "lora_distill_diff")
+
+
+def distill_rayleigh_ritz(table, n_layers: int, side: int, r: int, tol: float, last: bool, ws) -> None:
+    _check(lib().lora_distill_rayleigh_ritz(_ptr(table), n_layers, side, r, float(tol), int(last), _ptr(ws), _stream(ws)),
+           "lora_distill_rayleigh_ritz")
+
+
+def distill_finalize(table, n_layers: int, r: int, q, ws, out) -> None:
+    """q = None: no quantile clamp."""
+    _check(lib().lora_distill_finalize(_ptr(table), n_layers, r, 0.0 if q is None else float(q), int(q is not None), _ptr(ws),
+                                       _ptr(out), _stream(ws)), "lora_distill_finalize")
+
+
+def quantile_clamp_(x, q: float, hi_out=None) -> None:
+    """x (fp32, contiguous, device) ← clamp(x, −hi, hi) with hi = torch.quantile(x, q); hi_out [1] fp32 receives hi."""
+    _require_device(x, hi_out)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise RuntimeError("quantile_clamp_: x must be a contiguous float32 tensor")
+    _check(lib().lora_quantile_clamp(_ptr(x), x.numel(), float(q), _ptr(hi_out), _stream(x)), "lora_quantile_clamp")
 
 
 def geglu_gate_fwd(y2):

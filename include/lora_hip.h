@@ -479,6 +479,39 @@ int attn_flash_bwd(const void* Q, const void* K, const void* V, const void* O, c
                    int dtype, void* stream);
 
 /*
+ * svd_distill — lora_diffusion/cli_svd.py:29-111: a fully fine-tuned model → rank-r LoRA factors, per target linear
+ *     D = float(T(W1 − W0))  (:59-69);  U, S, Vh = svd(D);  up = U_r·diag(S_r) [N,r], down = Vh_r [r,K]  (:71-77)
+ *     hi = quantile(cat(up, down), q) (linear interpolation);  up, down ← clamp(·, −hi, hi)  (:79-84)
+ * by batched block subspace iteration (width 32) with Rayleigh–Ritz, every phase ONE launch for all layers.
+ * table: device memory, int64 [n_layers][8] = {W1 ptr, W0 ptr (dtype, [N,K]), N, K, workspace byte offset (256-aligned),
+ * output float offset, layer index (keys the start block), 0}.  Each layer owns lora_distill_workspace_bytes(N, K) bytes of
+ * `workspace` from its offset; its factors go to out[off ..] as up [N,r] then down [r,K], fp32.  r <= 16
+ * (LORA_E_UNSUPPORTED above), r <= min(N,K) (LORA_E_RANK).  Sign convention (the SVD fixes none): the largest-magnitude
+ * entry of each down row is positive, ties to the lowest index.
+ *   lora_distill_start          : resets the per-layer state, V ← orth(V₀), V₀ pseudo-random from (seed, layer index).
+ *                                 min_nk = min over the table of min(N,K).
+ *   lora_distill_diff           : transpose = 0: Y = D·V [N,32]; 1: Z = Dᵀ·U [K,32].  D formed on load in `dtype`'s
+ *                                 rounding and never stored; max_rows = max over the table of N (0) resp. K (1).
+ *   lora_distill_rayleigh_ritz  : side 1: Y = U·Σ·Ũᵀ → U (Ritz pairs kept); side 2: residual max_{i<r} ‖Dᵀu_i − σ_i v_i‖/σ_1,
+ *                                 converged (<= tol) or `last` → V ← V·Ũ and the layer freezes, else V ← orth(Z).
+ *                                 Per-layer int32 state at the layer's workspace offset: [0] = 0 running, 1 converged,
+ *                                 2 stopped by `last`, 3 non-finite; [1] = iterations; double at +8 = residual.
+ *   lora_distill_finalize       : factors with the sign convention, then (clamp != 0) the quantile clamp at q.
+ *   lora_quantile_clamp         : torch.quantile(x, q) (linear) and x ← clamp(x, −hi, hi) in place over n fp32 values, one
+ *                                 workgroup; hi_out (nullable, device) receives hi.  Bit-identical to torch on the CPU.
+ */
+int64_t lora_distill_workspace_bytes(int64_t N, int64_t K);
+int lora_distill_start(const int64_t* table, int n_layers, int64_t min_nk, int r, int64_t seed, void* workspace,
+                       void* stream);
+int lora_distill_diff(const int64_t* table, int n_layers, int64_t max_rows, int transpose, int dtype, void* workspace,
+                      void* stream);
+int lora_distill_rayleigh_ritz(const int64_t* table, int n_layers, int side, int r, double tol, int last, void* workspace,
+                               void* stream);
+int lora_distill_finalize(const int64_t* table, int n_layers, int r, float q, int clamp, void* workspace, float* out,
+                          void* stream);
+int lora_quantile_clamp(float* x, int64_t n, float q, float* hi_out, void* stream);
+
+/*
  * Launch profiler (measurement only; off by default).  When enabled, the hot-path kernels are launched
  * with start/stop events attached to the dispatch itself, so each record is that kernel's own duration on
  * the caller's stream, together with the ALGORITHMIC bytes and flops of the call (formulas: DESIGN.md §5).
