@@ -19,13 +19,13 @@ After `close()` the same text encoder goes to `trainer.LoraTrainer` for perform_
 TokenTable starts from the module's weight, which holds the learned rows.
 """
 import functools
-import warnings
 from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
 
 from . import _native as nat
+from . import step as stp
 from .trainer import ddpm_tables, lr_lambda
 
 TARGET_NORM = 0.4  # clip_ti_decay's target row norm (cli_lora_pti.py:333)
@@ -100,7 +100,7 @@ class InversionTrainer:
             raise ValueError(f"placeholder ids out of range for the {V}-row token table: {ids}")
         if len(set(ids)) != len(ids):
             raise ValueError(f"placeholder ids repeat: {ids}")
-        self.dtype = next(p for p in unet.parameters() if p.dim() == 4).dtype  # conv weight dtype = compute dtype (trainer.py)
+        self.dtype = stp.compute_dtype(unet)
         if self.dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"compute dtype {self.dtype}: fp32 (the reference's) or bf16 only — the reference's inversion "
                              "phase has no loss scaler for f16")
@@ -125,7 +125,7 @@ class InversionTrainer:
         self.global_step = 0      # micro-steps taken (train_inversion's global_step)
         self.optimizer_steps = 0  # AdamW steps taken (its bias-correction count)
         self.scheduler_epoch = 0  # LambdaLR.last_epoch
-        self._graph = None
+        self._recorder = stp.StepRecorder("InversionTrainer")
         self._prev_forward = emb.__dict__.get("forward")
         emb.forward = functools.partial(self._embed_forward, emb)  # (instance attribute: the class is untouched)
 
@@ -142,7 +142,8 @@ class InversionTrainer:
         self.module.__dict__.pop("forward", None)
         if self._prev_forward is not None:
             self.module.forward = self._prev_forward
-        self.module, self._graph = None, None
+        self.module = None
+        self._recorder.drop()
 
     def get_last_lr(self) -> List[float]:
         """`lr_scheduler.get_last_lr()`: the rate of the last micro-step."""
@@ -164,14 +165,15 @@ class InversionTrainer:
             if int(input_ids.min()) < 0 or int(input_ids.max()) >= self.V:
                 raise IndexError(f"token id out of range for the {self.V}-row embedding table")
         ids = input_ids.to(self.device, torch.int64)
-        n_timesteps = max(1, int(self.sqrt_acp.numel() * float(t_multiplier)))
+        nz = stp.Noising(self.sqrt_acp, self.sqrt_1macp, self.dtype, self.v_prediction,
+                         max(1, int(self.sqrt_acp.numel() * float(t_multiplier))))
         g = self.global_step
         self.scheduler_epoch += 1  # lr_scheduler.step() comes first (:293)
         lr_g = self.lr * float(self.lr_lambda(self.scheduler_epoch))
         if self.capture_graph:
-            loss = self._step_graph(latents, noise, timesteps, ids, mask, seed, g, n_timesteps)
+            loss = self._step_graph(latents, noise, timesteps, ids, mask, seed, g, nz)
         else:
-            loss = self._step_eager(latents, noise, timesteps, ids, mask, seed, g, n_timesteps)
+            loss = self._step_eager(latents, noise, timesteps, ids, mask, seed, g, nz)
         if optimizer_steps_at(g, self.accum_iter):
             self.optimizer_steps += 1
             nat.ti_rows_adamw_decay(self.module.weight.data, self.slot_ids, self.grad, self.exp_avg, self.exp_avg_sq, 1.0, lr_g,
@@ -181,102 +183,36 @@ class InversionTrainer:
         self.global_step += 1
         return loss
 
-    def _prologue(self, latents, noise, timesteps, seed, g, n_timesteps):
-        if noise is None:
-            return nat.ddpm_noise_prologue(latents, self.sqrt_acp, self.sqrt_1macp, self.dtype, seed, g, self.v_prediction,
-                                           n_timesteps)
-        noisy, target = nat.ddpm_add_noise(latents, noise, timesteps, self.sqrt_acp, self.sqrt_1macp, self.dtype,
-                                           self.v_prediction)
-        return noisy, target, timesteps
-
-    def _raw_mask(self, mask, latents):
-        if mask is None:
-            return None
-        rows, h, w = latents.shape[0], latents.shape[2], latents.shape[3]
-        return mask.to(self.device).reshape(rows, 1, h * 8, w * 8).float().contiguous()
-
     def _forward_backward(self, noisy, target, timesteps, ids, raw_mask):
         """text encoder → UNet → fused MSE (gradient scaled by 1/accum_iter) → backward, which ends in ti_rows_grad.
         Returns the unscaled loss."""
         ehs = self.text_encoder(ids)[0].to(self.dtype)
         pred = self.unet(noisy, timesteps, ehs).sample
-        m = nat.lora_mask_prepare(raw_mask, pred.shape[2], pred.shape[3]) if raw_mask is not None else None
-        pred_c = pred if pred.is_contiguous() else pred.contiguous()
-        loss, dpred = nat.ddpm_mse_fwd_bwd(pred_c, target, m, pred.shape[0], 0, 1.0, 1.0 / self.accum_iter)
-        pred_c.backward(dpred)
-        return loss
+        return stp.loss_backward(pred, target, raw_mask, pred.shape[0], 0, 1.0, 1.0 / self.accum_iter)
 
-    def _step_eager(self, latents, noise, timesteps, ids, mask, seed, g, n_timesteps):
-        noisy, target, t = self._prologue(latents, noise, timesteps, seed, g, n_timesteps)
-        loss = self._forward_backward(noisy, target, t, ids, self._raw_mask(mask, latents))
+    def _step_eager(self, latents, noise, timesteps, ids, mask, seed, g, nz):
+        noisy, target, t = stp.noise_prologue(nz, latents, noise, timesteps, seed, g)
+        loss = self._forward_backward(noisy, target, t, ids, stp.raw_mask(mask, latents))
         return loss / self.accum_iter
 
     # -- the same micro-step replayed from a hipGraph ---------------------------------------------------
+    @property
+    def _graph(self):
+        """The live recording; None exactly when there is none."""
+        return self._recorder if self._recorder.graph is not None else None
+
     def _fingerprint(self):
-        """What a recording bakes in besides the shapes (trainer.LoraTrainer._fingerprint's rule): scalars passed as kernel
-        arguments and the address of the table the gather reads."""
+        """What a recording bakes in besides the shapes: scalars passed as kernel arguments and the address of the table the
+        gather reads."""
         return (self.v_prediction, self.accum_iter, self.module.weight.data_ptr())
 
-    def _graph_body(self, st):
-        if st["draw"]:
-            noisy, target = st["noisy"], st["target"]
-        else:
-            noisy, target = nat.ddpm_add_noise(st["latents"], st["noise"], st["timesteps"], self.sqrt_acp, self.sqrt_1macp,
-                                               self.dtype, self.v_prediction)
-        st["loss"] = self._forward_backward(noisy, target, st["timesteps"], st["ids"], st["mask"])
-
-    def _graph_inputs(self, st, latents, noise, timesteps, ids, mask, seed, g, n_timesteps):
-        if st["draw"]:
-            noisy, target, t = nat.ddpm_noise_prologue(latents, self.sqrt_acp, self.sqrt_1macp, self.dtype, seed, g,
-                                                       self.v_prediction, n_timesteps)
-            st["noisy"].copy_(noisy)
-            st["target"].copy_(target)
-            st["timesteps"].copy_(t)
-        else:
-            st["latents"].copy_(latents)
-            st["noise"].copy_(noise)
-            st["timesteps"].copy_(timesteps)
-        st["ids"].copy_(ids)
-        if mask is not None:
-            st["mask"].copy_(self._raw_mask(mask, latents))
-
-    def _step_graph(self, latents, noise, timesteps, ids, mask, seed, g, n_timesteps):
+    def _step_graph(self, latents, noise, timesteps, ids, mask, seed, g, nz):
         key = (tuple(latents.shape), tuple(ids.shape), noise is None, mask is not None)
-        fp = self._fingerprint()
-        st = self._graph
-        if st is None or st["key"] != key or st["fp"] != fp:
-            self._graph = st = None  # drop the old recording (and the buffers it pins) before making a new one
-            rows, h, w = latents.shape[0], latents.shape[2], latents.shape[3]
-            st = {"key": key, "fp": fp, "draw": noise is None,
-                  "latents": torch.empty_like(latents, dtype=torch.float32),
-                  "noise": torch.empty_like(latents, dtype=torch.float32),
-                  "timesteps": torch.empty(rows, dtype=torch.int64, device=self.device),
-                  "noisy": torch.empty_like(latents, dtype=self.dtype), "target": torch.empty_like(latents, dtype=self.dtype),
-                  "ids": torch.empty_like(ids),
-                  "mask": None if mask is None else torch.empty((rows, 1, h * 8, w * 8), dtype=torch.float32,
-                                                                device=self.device),
-                  "graph": None}
-            self._graph_inputs(st, latents, noise, timesteps, ids, mask, seed, g, n_timesteps)
+        rec = self._recorder
+        if rec.load(key, self._fingerprint(), nz, latents, noise, timesteps, seed, g, ids, None, mask):
             saved = self.grad.clone()  # the warm-up passes accumulate into the buffer: what the window holds so far is kept
-            try:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        self._graph_body(st)
-                torch.cuda.current_stream().wait_stream(side)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    self._graph_body(st)
-                st["graph"] = graph
-            except Exception as exc:  # keep training: host-launched micro-steps from here on
-                warnings.warn(f"InversionTrainer: hipGraph capture failed ({exc!r}); continuing with host-launched steps")
-                self.capture_graph, self._graph = False, None
-                self.grad.copy_(saved)
-                return self._step_eager(latents, noise, timesteps, ids, mask, seed, g, n_timesteps)
-            self._graph = st
-            self.grad.copy_(saved)
-        else:
-            self._graph_inputs(st, latents, noise, timesteps, ids, mask, seed, g, n_timesteps)
-        st["graph"].replay()
-        return st["loss"] / self.accum_iter
+            if not rec.record(self._forward_backward, undo=lambda: self.grad.copy_(saved)):
+                self.capture_graph = False  # keep training: host-launched micro-steps from here on
+                return self._step_eager(latents, noise, timesteps, ids, mask, seed, g, nz)
+        rec.replay()
+        return rec.loss / self.accum_iter

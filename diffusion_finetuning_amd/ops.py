@@ -20,6 +20,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from ._fastattr import factor_weights, frozen_linear, linear_params
+from .step import raw_mask
 
 _warned_trainable_base = False
 
@@ -729,8 +730,5 @@ def ddpm_mse_loss(pred, target, *, with_prior_preservation=False, prior_loss_wei
         n_inst = n_prior = rows // 2
     else:
         n_inst, n_prior = rows, 0
-    m = None
-    if mask is not None:
-        raw = mask.to(pred.device).reshape(rows, 1, pred.shape[2] * 8, pred.shape[3] * 8).float().contiguous()
-        m = nat.lora_mask_prepare(raw, pred.shape[2], pred.shape[3])
+    m = None if mask is None else nat.lora_mask_prepare(raw_mask(mask, pred), pred.shape[2], pred.shape[3])
     return _DDPMLossFn.apply(pred, target, m, n_inst, n_prior, float(prior_loss_weight))

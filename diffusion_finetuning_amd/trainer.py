@@ -14,7 +14,9 @@ slab, which is also the RCCL send/receive buffer — no packing, one or two coll
 and the optimizer is two launches over the slab.  Data parallelism is one process per GPU over
 `torch.distributed` (backend "nccl" = RCCL over xGMI); only the LoRA gradients (≈5 MB at rank 4) ever cross GPUs.
 """
+import functools
 import math
+import warnings
 from typing import Iterable, List, Optional, Sequence, Tuple
 
 import torch
@@ -22,6 +24,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import _native as nat
+from . import step as stp
 from .core import LoraInjectedLinear
 
 
@@ -601,8 +604,6 @@ class TokenTable:
     200-MB table gradient) cross the GPUs."""
 
     def __init__(self, slab: "LoraSlab", text_encoder: nn.Module, index: int, out_dtype: torch.dtype):
-        import functools
-
         self.module = text_encoder.get_input_embeddings()
         w = self.module.weight
         self.V, self.D = w.shape
@@ -696,7 +697,7 @@ class LoraTrainer:
         if self.scheduler_steps_per_call < 1:
             raise ValueError("scheduler_steps_per_call must be >= 1")
         self.capture_graph = bool(capture_graph)
-        self._graph = None
+        self._recorder = stp.StepRecorder("LoraTrainer")
         models = [unet] + ([text_encoder] if text_encoder is not None and lora_layers(text_encoder) else [])
         emb = text_encoder.get_input_embeddings() if (text_encoder is not None and hasattr(text_encoder, "get_input_embeddings")) \
             else None
@@ -717,7 +718,7 @@ class LoraTrainer:
                            "weight_decay": weight_decay if weight_decay_embed is None else weight_decay_embed})
         self.opt = FusedClipAdamW(self.slab, groups, betas, eps, max_grad_norm)
         self.device = self.slab.params.device
-        self.dtype = next(p for p in unet.parameters() if p.dim() == 4).dtype  # conv weight dtype = compute dtype
+        self.dtype = stp.compute_dtype(unet)
         self.tail_events = None  # a list switches on the timing of the host-launched tail of every replayed step
         self.token_table = None
         if train_emb:
@@ -817,8 +818,6 @@ class LoraTrainer:
         before = self.scaler.scale
         if self.scaler.begin_step() and self.scaler.scale < before and not self._warned_overflow:
             self._warned_overflow = True
-            import warnings
-
             warnings.warn(f"LoraTrainer: non-finite fp16 gradients — the step was skipped and the loss scale "
                           f"lowered to {self.scaler.scale:g} (GradScaler semantics)")
 
@@ -859,11 +858,14 @@ class LoraTrainer:
         pass None for both and a `seed`: the step then draws them on the device (Philox keyed by (seed, optimizer step),
         identical on every rank) inside the prologue kernel, timesteps uniform on [0, int(1000·t_multiplier)) — the PTI loop's
         `t_mutliplier` (cli_lora_pti.py:176,190-195).  `mask`: raw [B,1,8h,8w] mask of cli_lora_pti.py:222-247."""
-        self._n_timesteps = max(1, int(self.sqrt_acp.numel() * float(t_multiplier)))
+        self._noising = stp.Noising(self.sqrt_acp, self.sqrt_1macp, self.dtype, self.v_prediction,
+                                    max(1, int(self.sqrt_acp.numel() * float(t_multiplier))))
         if (encoder_hidden_states is None) == (input_ids is None):
             raise ValueError("pass exactly one of encoder_hidden_states and input_ids")
         if input_ids is not None and self.text_encoder is None:
             raise ValueError("input_ids given but the trainer has no text encoder")
+        if noise is None and seed is None:
+            raise ValueError("pass noise and timesteps, or a seed for the on-device draw")
         if self.token_table is not None and input_ids is not None and input_ids.device.type == "cpu":
             self.token_table.check_ids(input_ids)  # (free on the host; a replayed step cannot check device-resident ids)
         self._poll_overflow()
@@ -887,20 +889,27 @@ class LoraTrainer:
         pred = self.unet(noisy, timesteps, ehs).sample
         rows = pred.shape[0]
         n_inst, n_prior = (rows // 2, rows // 2) if prior else (rows, 0)
-        m = None
-        if raw_mask is not None:
-            m = nat.lora_mask_prepare(raw_mask, pred.shape[2], pred.shape[3])
-        pred_c = pred if pred.is_contiguous() else pred.contiguous()
-        loss, dpred = nat.ddpm_mse_fwd_bwd(pred_c, target, m, n_inst, n_prior, prior_weight, self.loss_scale)
-        pred_c.backward(dpred)
+        loss = stp.loss_backward(pred, target, raw_mask, n_inst, n_prior, prior_weight, self.loss_scale)
         self.slab.flush()  # factor gradients of every layer that ran: batched launch + ordered fold into the slab
         return loss
 
-    def _raw_mask(self, mask, latents):
-        if mask is None:
-            return None
-        rows, h, w = latents.shape[0], latents.shape[2], latents.shape[3]
-        return mask.to(self.device).reshape(rows, 1, h * 8, w * 8).float().contiguous()
+    def _finish_step(self, recorded_rows=None):
+        """What follows backward, host-launched on both routes: exchange, token-table gradient, clip + AdamW, re-pack.
+        `recorded_rows`: the (ids, gradient rows) buffers a replayed recording has just written."""
+        tail = self.tail_events
+        if tail is not None:  # (bench.py: device time of this tail — with an early bucket its all-reduce is behind us)
+            tail.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+            tail[-1][0].record()
+        self.exchange.finish()
+        if self.token_table is not None:
+            if recorded_rows is not None:
+                self.token_table._pending = list(recorded_rows)
+            self.token_table.collect(self.pg, self.world if self.exchange.active else 1)
+        self.opt.step(grad_mul=1.0 / (self.world * self.loss_scale), lr_mul=self._scheduled_lr_factor())
+        self._watch_overflow()
+        self.slab.repack()  # forwards outside step() (sampling, evaluation, saving merged weights) see the new factors
+        if tail is not None:
+            tail[-1][1].record()
 
     def _step_eager(self, latents, noise, timesteps, encoder_hidden_states, input_ids, with_prior_preservation,
                     prior_loss_weight, mask, seed):
@@ -908,137 +917,58 @@ class LoraTrainer:
         (SlabExchange / _install_bucket_hook) — unless a recorded step was asked for (exchange.single)."""
         self.slab.zero_grad()
         self.slab.repack()  # packed compute-dtype factors follow the fp32 masters (also after external edits)
-        if noise is None:
-            if seed is None:
-                raise ValueError("pass noise and timesteps, or a seed for the on-device draw")
-            noisy, target, timesteps = nat.ddpm_noise_prologue(latents, self.sqrt_acp, self.sqrt_1macp, self.dtype, seed,
-                                                               self.opt.step_count, self.v_prediction, self._n_timesteps)
-        else:
-            noisy, target = nat.ddpm_add_noise(latents, noise, timesteps, self.sqrt_acp, self.sqrt_1macp, self.dtype,
-                                               self.v_prediction)
+        noisy, target, timesteps = stp.noise_prologue(self._noising, latents, noise, timesteps, seed, self.opt.step_count)
         self.exchange.arm()
         if self.token_table is not None:
             self.token_table.begin_pass()
         ehs = self._conditioning(encoder_hidden_states, input_ids)
         loss = self._forward_backward(noisy, target, timesteps, ehs, with_prior_preservation, prior_loss_weight,
-                                      self._raw_mask(mask, latents))
-        tail = self.tail_events
-        if tail is not None:  # (bench.py: what the step still has to do once backward has finished — with an early bucket its
-            tail.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))  # all-reduce is behind us)
-            tail[-1][0].record()
-        self.exchange.finish()
-        if self.token_table is not None:
-            self.token_table.collect(self.pg, self.world if self.exchange.active else 1)
-        self.opt.step(grad_mul=1.0 / (self.world * self.loss_scale), lr_mul=self._scheduled_lr_factor())
-        self._watch_overflow()
-        self.slab.repack()  # forwards outside step() (sampling, evaluation, saving merged weights) see the new factors
-        if tail is not None:
-            tail[-1][1].record()
+                                      stp.raw_mask(mask, latents))
+        self._finish_step()
         return loss
 
     # -- the same step with forward+backward replayed from a hipGraph -----------------------------------
-    def _graph_body(self, st):
-        """What is captured: reads only static buffers, leaves the gradient slab and the loss behind."""
-        if st["draw"]:
-            noisy, target = st["noisy"], st["target"]
-        else:
-            noisy, target = nat.ddpm_add_noise(st["latents"], st["noise"], st["timesteps"], self.sqrt_acp,
-                                               self.sqrt_1macp, self.dtype, self.v_prediction)
+    @property
+    def _graph(self):
+        """The live recording; None exactly when there is none."""
+        return self._recorder if self._recorder.graph is not None else None
+
+    def _graph_body(self, by_ids, prior, prior_weight, noisy, target, timesteps, cond, raw_mask):
+        """What is captured: reads only the recorder's static buffers, leaves the gradient slab behind, returns the loss."""
         if self.token_table is not None:
             self.token_table.begin_pass()  # (runs while recording: the rows buffer it ends up holding is the recording's own)
-        ehs = self._conditioning(st["ehs"], st["ids"])
-        st["loss"] = self._forward_backward(noisy, target, st["timesteps"], ehs, st["prior"], st["prior_weight"], st["mask"])
+        ehs = self._conditioning(None, cond) if by_ids else self._conditioning(cond, None)
+        return self._forward_backward(noisy, target, timesteps, ehs, prior, prior_weight, raw_mask)
 
-    def _graph_inputs(self, st, latents, noise, timesteps, ehs, ids, mask, seed):
-        if st["draw"]:
-            if seed is None:
-                raise ValueError("pass noise and timesteps, or a seed for the on-device draw")
-            noisy, target, t = nat.ddpm_noise_prologue(latents, self.sqrt_acp, self.sqrt_1macp, self.dtype, seed,
-                                                       self.opt.step_count, self.v_prediction, self._n_timesteps)
-            st["noisy"].copy_(noisy)
-            st["target"].copy_(target)
-            st["timesteps"].copy_(t)
-        else:
-            st["latents"].copy_(latents)
-            st["noise"].copy_(noise)
-            st["timesteps"].copy_(timesteps)
-        if ids is None:
-            st["ehs"].copy_(ehs)  # casts to the compute dtype
-        else:
-            st["ids"].copy_(ids)
-        if mask is not None:
-            st["mask"].copy_(self._raw_mask(mask, latents))
-        self.slab.zero_grad()
-        self.slab.repack()
+    def _recording_owns(self):
+        """The host + device plans of a fresh recording's one-launch factor gradients, and the (ids, gradient rows) buffers it
+        writes on every replay: they belong to the recording, not to the table — an eager step in between resets the table's
+        list (begin_pass), a replay cannot refill it."""
+        return self.slab.take_recording_plans(), (list(self.token_table._pending) if self.token_table is not None else None)
 
     def _step_graph(self, latents, noise, timesteps, ehs, ids, mask, prior, prior_weight, seed):
         cond_shape = tuple(ehs.shape) if ids is None else ("ids",) + tuple(ids.shape)
         key = (tuple(latents.shape), cond_shape, bool(prior), float(prior_weight), noise is None, mask is not None)
-        fp = self._fingerprint()
-        st = self._graph
-        if st is None or st["key"] != key or st["fp"] != fp:
-            self._graph = st = None  # drop the old recording (and the operand buffers it pins) before making a new one
-            rows, h, w = latents.shape[0], latents.shape[2], latents.shape[3]
-            st = {"key": key, "fp": fp, "draw": noise is None, "prior": bool(prior), "prior_weight": float(prior_weight),
-                  "latents": torch.empty_like(latents, dtype=torch.float32),
-                  "noise": torch.empty_like(latents, dtype=torch.float32),
-                  "timesteps": torch.empty(latents.shape[0], dtype=torch.int64, device=self.device),
-                  "noisy": torch.empty_like(latents, dtype=self.dtype), "target": torch.empty_like(latents, dtype=self.dtype),
-                  "ehs": None if ids is not None else torch.empty_like(ehs, dtype=self.dtype),
-                  "ids": None if ids is None else torch.empty_like(ids, device=self.device),
-                  "mask": None if mask is None else torch.empty((rows, 1, h * 8, w * 8), dtype=torch.float32,
-                                                                device=self.device),
-                  "graph": None}
-            self._graph_inputs(st, latents, noise, timesteps, ehs, ids, mask, seed)
-            try:
-                # warm up on a side stream (solver searches, lazy initialisation, allocator), then record
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        self._graph_body(st)
-                torch.cuda.current_stream().wait_stream(side)
-                self.slab.prepare_recording()  # pinned plan buffers the recording will own (never allocated inside it)
-                g = torch.cuda.CUDAGraph()
-                # With a process group alive, its watchdog thread polls HIP events every now and then; under the default
-                # "global" capture mode such a call from ANOTHER thread invalidates the recording (a race that shows up
-                # in a few percent of the captures).  "thread_local" keeps the check for this thread only.
-                mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-                with torch.cuda.graph(g, capture_error_mode=mode):
-                    self._graph_body(st)
-                st["graph"] = g
-                st["grad_plans"] = self.slab.take_recording_plans()  # host + device plan of the one-launch factor gradients
-                # the (ids, gradient rows) buffers the RECORDING writes on every replay belong to the recording, not to the
-                # table: an eager step in between resets the table's list (begin_pass), a replay cannot refill it
-                st["token_pending"] = list(self.token_table._pending) if self.token_table is not None else None
-            except Exception as exc:  # keep training: this trainer falls back to host-launched steps for good
-                import warnings
-
-                warnings.warn(f"LoraTrainer: hipGraph capture failed ({exc!r}); continuing with host-launched steps")
-                self.capture_graph, self._graph = False, None
-                # exchange.single stays set: this rank keeps issuing the one whole-slab all-reduce its peers' replays issue
-                return self._step_eager(latents, noise, timesteps, ehs, ids, prior, prior_weight, mask, seed)
-            self._graph = st
-            # the warm-up passes each folded this step's gradients into the slab: clear it, then replay once so that
-            # every step (including the first) is produced by the same recorded kernels
-            self.slab.zero_grad()
-        else:
-            self._graph_inputs(st, latents, noise, timesteps, ehs, ids, mask, seed)
-        st["graph"].replay()
-        tail = self.tail_events
-        if tail is not None:  # (bench.py: device time of the host-launched tail — exchange, clip + AdamW, re-pack)
-            tail.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
-            tail[-1][0].record()
-        self.exchange.finish()
-        if self.token_table is not None:
-            self.token_table._pending = list(st["token_pending"])
-            self.token_table.collect(self.pg, self.world if self.exchange.active else 1)
-        self.opt.step(grad_mul=1.0 / (self.world * self.loss_scale), lr_mul=self._scheduled_lr_factor())
-        self._watch_overflow()
+        rec = self._recorder
+        cond, cond_dtype = (ehs, self.dtype) if ids is None else (ids, None)
+        fresh = rec.load(key, self._fingerprint(), self._noising, latents, noise, timesteps, seed, self.opt.step_count,
+                         cond, cond_dtype, mask)
+        self.slab.zero_grad()
         self.slab.repack()
-        if tail is not None:
-            tail[-1][1].record()
-        return st["loss"].clone()
+        if fresh:
+            body = functools.partial(self._graph_body, ids is not None, bool(prior), float(prior_weight))
+            # before the capture: the pinned plan buffers the recording will own (never allocated inside it).  Afterwards: the
+            # warm-up passes each folded this step's gradients into the slab — clear it, then replay once so that every step
+            # (including the first) is produced by the same recorded kernels
+            if not rec.record(body, before_capture=self.slab.prepare_recording, keep=self._recording_owns,
+                              undo=self.slab.zero_grad):
+                # keep training: this trainer falls back to host-launched steps for good.  exchange.single stays set: this
+                # rank keeps issuing the one whole-slab all-reduce its peers' replays issue
+                self.capture_graph = False
+                return self._step_eager(latents, noise, timesteps, ehs, ids, prior, prior_weight, mask, seed)
+        rec.replay()
+        self._finish_step(recorded_rows=rec.held[1])
+        return rec.loss.clone()
 
 
 def flat_lora_state(model: nn.Module, targets=None) -> torch.Tensor:

@@ -152,8 +152,8 @@ def test_replay_after_a_host_launched_step_still_sums_the_recordings_gradient_ro
                                                 t_max=int(1000 * cfg["t_multiplier"]))
         losses.append(trainer.step(lat.to(DEV), noise.to(DEV), ts.to(DEV), input_ids=t["ids"][s].to(DEV)))
         if s == 1:
-            recording = trainer._graph["graph"]
-    assert trainer._graph["graph"] is recording  # not re-recorded: the replay after the eager step is the old recording
+            recording = trainer._graph.graph
+    assert trainer._graph.graph is recording  # not re-recorded: the replay after the eager step is the old recording
     losses = torch.stack(losses).reshape(-1).cpu()
     assert relerr(losses, want_losses) < 1e-5, relerr(losses, want_losses)
     got, want = te.get_input_embeddings().weight.detach(), want_te.get_input_embeddings().weight.detach()

@@ -8,6 +8,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from diffusion_finetuning_amd.step import Noising, StepRecorder
 from diffusion_finetuning_amd.trainer import SCHEDULER_NAMES, LoraTrainer, LossScaler, SlabExchange, lr_lambda
 
 
@@ -99,7 +100,9 @@ def _free_port():
 
 
 class _FakeTrainer:
-    """The exchange calls of LoraTrainer._step_eager / _step_graph, nothing else (trainer.py)."""
+    """The exchange calls of LoraTrainer._step_eager / _step_graph, nothing else (trainer.py): `arm` and the backward hook's
+    `launch_early` on the host-launched route, then `finish` — the first collective call of `_finish_step` — on both; a
+    failed `step.StepRecorder.record` clears `capture_graph` and finishes the step host-launched."""
 
     def __init__(self, n, capture_graph, early_range, capture_ok=True):
         self.grads = torch.ones(n)
@@ -120,6 +123,72 @@ class _FakeTrainer:
         self.exchange.arm()
         self.exchange.launch_early()                  # the mid-block backward hook
         self.exchange.finish()
+
+
+class _FakeCapture(StepRecorder):
+    """StepRecorder without the device part (side-stream warm-up + hipGraph capture): its bookkeeping alone."""
+
+    def __init__(self, owner, events):
+        self.events, self.fail, self.replays = events, False, 0
+        super().__init__(owner)
+
+    def drop(self):
+        self.events.append(("drop", getattr(self, "graph", None) is not None))
+        super().drop()
+
+    def _capture(self, body, before_capture):
+        before_capture()
+        if self.fail:
+            raise RuntimeError("capture refused")
+        self.loss = body(*self.inputs, self.cond, self.mask)
+        return self  # (stands in for the hipGraph: `replay` below)
+
+    def replay(self):
+        assert self.graph is self
+        self.replays += 1
+
+
+def test_step_recorder_records_once_per_key_and_fingerprint_and_cleans_up_after_a_failed_capture():
+    """What both trainers' `_step_graph` rely on, with caller-drawn noise on host tensors: the same key and fingerprint replay
+    the recording; a changed fingerprint drops the old recording BEFORE the new buffers exist; only the buffers of the
+    step's noise mode are allocated; `keep`'s value lives with the recording; a failed capture warns, leaves nothing
+    recorded, and `undo` has run in either case."""
+    nz = Noising(torch.ones(1000), torch.zeros(1000), torch.bfloat16, False, 1000)
+    lat, noise, ts = torch.randn(2, 4, 3, 3), torch.randn(2, 4, 3, 3), torch.tensor([5, 900])
+    ids, mask = torch.arange(10).reshape(2, 5), torch.ones(2, 24 * 24)
+    events = []
+    rec = _FakeCapture("FakeTrainer", events)
+    assert rec.graph is None and events == [("drop", False)]
+    state = {"capture_graph": True}
+
+    def step(key, fp):
+        if not state["capture_graph"]:
+            return "host-launched"
+        fresh = rec.load(key, fp, nz, lat, noise, ts, None, 0, ids, None, mask)
+        if fresh and not rec.record(lambda latents, noise, timesteps, cond, mask: latents.sum(), before_capture=lambda: events.append("before capture"),
+                                    keep=lambda: "the recording's own", undo=lambda: events.append("undo")):
+            state["capture_graph"] = False
+            return "host-launched"
+        rec.replay()
+        return rec.loss
+
+    del events[:]
+    assert torch.equal(step("shapes", "fp0"), lat.sum())
+    assert events == [("drop", False), "before capture", "undo"] and rec.held == "the recording's own"
+    assert len(rec.inputs) == 3 and not rec.drawn                         # caller's noise: no buffers for a device draw
+    assert all(torch.equal(a, b) and a.dtype == b.dtype for a, b in zip(rec.inputs, (lat, noise, ts)))
+    assert torch.equal(rec.cond, ids) and rec.mask.shape == (2, 1, 24, 24) and rec.mask.dtype == torch.float32
+    step("shapes", "fp0")
+    assert len(events) == 3 and rec.replays == 2                          # replayed, not re-recorded
+    step("shapes", "fp1")
+    assert events[3:] == [("drop", True), "before capture", "undo"] and rec.fp == "fp1" and rec.replays == 3
+    rec.fail = True
+    with pytest.warns(UserWarning, match=r"FakeTrainer: hipGraph capture failed \(RuntimeError\('capture refused'\)\); "
+                                         "continuing with host-launched steps"):
+        assert step("other shapes", "fp1") == "host-launched"
+    assert events[6:] == [("drop", True), "before capture", ("drop", False), "undo"]
+    assert rec.graph is None and rec.held is None and rec.inputs is None and rec.loss is None
+    assert step("shapes", "fp1") == "host-launched" and len(events) == 10  # for good: the recorder is not asked again
 
 
 def _sequence_worker(rank, world, port, out):
