@@ -94,6 +94,9 @@ SIGNATURES = {
     "attn_split_heads": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "attn_merge_heads": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "attn_merge_heads_strided": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
+    "group_norm_act_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "group_norm_act_fwd": (_i32, [_vp] * 8 + [_i32, _i32, _i32, _i32, _f32, _i32, _i32, _i32, _vp]),
+    "group_norm_act_bwd": (_i32, [_vp] * 10 + [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "attn_ctx_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "attn_ctx_fwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "attn_ctx_bwd_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
@@ -773,6 +776,53 @@ def attn_merge_heads(x4, d: int):
 
 
 _attn_supported = {}  # (core, shape, dtype) → bool: a pure function of the library, asked 2–3 times per attention call
+
+
+def group_norm_act_layout(x):
+    """0 for an NCHW-contiguous [N,C,H,W] tensor, 1 for a channels-last one, None for any other strides (a tensor that is
+    both, C == 1 or H·W == 1, counts as NCHW)."""
+    if x.dim() != 4:
+        return None
+    if x.is_contiguous():
+        return 0
+    return 1 if x.is_contiguous(memory_format=torch.channels_last) else None
+
+
+def group_norm_act_supported(x, groups: int, layout) -> bool:
+    N, C, H, W = x.shape
+    return layout is not None and C % groups == 0 and lib().group_norm_act_workspace_bytes(N, C, H * W, groups, layout, 0) > 0
+
+
+def _norm_workspace(x, groups: int, layout: int, want_da: bool):
+    N, C, H, W = x.shape
+    nbytes = lib().group_norm_act_workspace_bytes(N, C, H * W, groups, layout, int(want_da))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+
+
+def group_norm_act_fwd(x, addend, gamma, beta, groups: int, eps: float, act: bool, layout: int):
+    """y (x's layout), mean, rstd ([N, groups] fp32) of act(GroupNorm(x + addend[:, :, None, None]))."""
+    _require_device(x, addend, gamma, beta)
+    N, C, H, W = x.shape
+    y = torch.empty_like(x)  # preserve_format: dense NCHW / channels-last strides are kept
+    mean = torch.empty((N, groups), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    ws = _norm_workspace(x, groups, layout, False)
+    _check(lib().group_norm_act_fwd(_ptr(x), _ptr(addend), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(ws),
+                                    N, C, H * W, groups, float(eps), int(act), layout, dtype_code(x.dtype), _stream(x)),
+           "group_norm_act_fwd")
+    return y, mean, rstd
+
+
+def group_norm_act_bwd(dy, x, addend, gamma, beta, mean, rstd, groups: int, act: bool, layout: int, want_da: bool):
+    """dx (x's layout) and da [N, C] (None unless want_da); dy must have x's layout."""
+    N, C, H, W = x.shape
+    dx = torch.empty_like(x)
+    da = torch.empty((N, C), dtype=x.dtype, device=x.device) if want_da else None
+    ws = _norm_workspace(x, groups, layout, want_da)
+    _check(lib().group_norm_act_bwd(_ptr(dy), _ptr(x), _ptr(addend), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd), _ptr(dx),
+                                    _ptr(da), _ptr(ws), N, C, H * W, groups, int(act), layout, dtype_code(x.dtype), _stream(x)),
+           "group_norm_act_bwd")
+    return dx, da
 
 
 def attn_ctx_supported(B: int, Tq: int, Tk: int, H: int, d: int, dtype) -> bool:

@@ -1,0 +1,590 @@
+// GroupNorm of the UNet's convolution trunk with what surrounds it folded in: y = act(GroupNorm(x + a)), x [N,C,H,W],
+// a an optional per-(n,c) addend (the time embedding and the preceding convolution's bias), act = SiLU or identity.
+// Stock PyTorch runs moments → normalise → SiLU as three kernels forward and three more backward, about 13 passes over the
+// activation; here it is a statistics pass and an apply pass each way (5 passes through HBM), and the backward recomputes
+// the normalised value and SiLU' from x, so only x is kept alive.
+//
+// Two layouts, both with 16-byte accesses:
+//   * NCHW: one wave per (n,c) row of H·W elements in the statistics kernels, so the partials are per channel; the apply
+//     kernels work on a slice of one (n,group) slab per workgroup and fold that group's ≤ cpg channel partials first.
+//   * channels-last (NHWC): a thread owns 8 fixed consecutive channels (which may straddle groups: the group width need not be
+//     a multiple of 8) over a block of rows; a workgroup reduces its rows × all channels through LDS to one partial per group,
+//     S partials per (n,group) in all, and the apply kernels fold them.
+// Every fold runs in a fixed order and there are no float atomics: two runs are bit-identical.  Statistics, the normalised
+// value and the activation are fp32 up to the single rounding of the output.  Sums of squares are taken about a shift (an
+// element of the group / channel), so a mean that is large against the deviation costs no digits.
+#include "common.h"
+
+namespace {
+
+constexpr int kNhwcThreads = 512;   // NHWC kernels: rows-per-pass RP = 512 / (C/8) row lanes × C/8 channel columns
+constexpr int kNhwcLds = 4096;      // RP·C ≤ 4096 floats per reduction array
+constexpr int kMaxGroups = 256;
+constexpr int kMaxSplit = 64;       // S: statistics partials per (n,group) in NHWC
+
+template <typename T> __device__ __forceinline__ Chunk<T> load_chunk(const T* p) { return *reinterpret_cast<const Chunk<T>*>(p); }
+
+__device__ __forceinline__ float sigmoid_f(float z) { return __builtin_amdgcn_rcpf(1.f + __expf(-z)); }
+template <bool SILU> __device__ __forceinline__ float act_f(float z) { return SILU ? z * sigmoid_f(z) : z; }
+template <bool SILU> __device__ __forceinline__ float act_grad_f(float z) {
+    if (!SILU) return 1.f;
+    const float s = sigmoid_f(z);
+    return s * fmaf(z, 1.f - s, 1.f);
+}
+
+// ---------------------------------------------------------------------------------------------------------- NCHW
+// part[(n·C + c)·3 + {0,1}] = mean and centred sum of squares of row (n,c) of x + a
+template <typename T>
+__global__ __launch_bounds__(256) void nchw_stats_fwd_kernel(const T* x, const T* a, float* part, int rows, int HW) {
+    constexpr int VEC = ElemTraits<T>::kVec;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const T* xr = x + (int64_t)row * HW;
+    const float x0 = to_f32<T>(xr[0]);
+    float s = 0.f, ss = 0.f;
+    const int chunks = HW / VEC;
+#pragma unroll 4
+    for (int i = lane; i < chunks; i += 64) {
+        const Chunk<T> v = load_chunk(xr + i * VEC);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const float d = to_f32<T>(v.v[e]) - x0;
+            s += d;
+            ss = fmaf(d, d, ss);
+        }
+    }
+    s = wave_sum(s);
+    ss = wave_sum(ss);
+    if (lane == 0) {
+        const float m = s / (float)HW;
+        part[(int64_t)row * 3 + 0] = x0 + (a ? to_f32<T>(a[row]) : 0.f) + m;
+        part[(int64_t)row * 3 + 1] = fmaxf(ss - s * m, 0.f);
+    }
+}
+
+// mean / rstd of group (n,g) from its cpg channel partials (equal counts), by wave 0 in a fixed order → LDS
+__device__ __forceinline__ void nchw_fold_group(const float* part, int64_t row0, int cpg, int HW, float eps, float* out2) {
+    if (threadIdx.x < 64) {
+        float sm = 0.f;
+        for (int c = threadIdx.x; c < cpg; c += 64) sm += part[(row0 + c) * 3];
+        const float mean = wave_sum(sm) / (float)cpg;
+        float m2 = 0.f;
+        for (int c = threadIdx.x; c < cpg; c += 64) {
+            const float d = part[(row0 + c) * 3] - mean;
+            m2 += fmaf((float)HW * d, d, part[(row0 + c) * 3 + 1]);
+        }
+        const float var = wave_sum(m2) / ((float)cpg * (float)HW);
+        if (threadIdx.x == 0) {
+            out2[0] = mean;
+            out2[1] = rsqrtf(var + eps);
+        }
+    }
+    __syncthreads();
+}
+
+template <typename T, bool SILU>
+__global__ __launch_bounds__(256) void nchw_apply_fwd_kernel(const T* x, const T* a, const T* gamma, const T* beta, T* y,
+                                                             float* mean_out, float* rstd_out, const float* part, int C, int HW,
+                                                             int G, float eps) {
+    constexpr int VEC = ElemTraits<T>::kVec;
+    __shared__ float st[2];
+    const int ng = blockIdx.y, n = ng / G, g = ng - n * G, cpg = C / G;
+    const int64_t row0 = (int64_t)n * C + (int64_t)g * cpg;
+    nchw_fold_group(part, row0, cpg, HW, eps, st);
+    const float mean = st[0], rstd = st[1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        mean_out[ng] = mean;
+        rstd_out[ng] = rstd;
+    }
+    const int cpr = HW / VEC, total = cpg * cpr;
+    const int per = (total + gridDim.x - 1) / gridDim.x;
+    const int end = min(total, (int)(blockIdx.x + 1) * per);
+    for (int i = blockIdx.x * per + threadIdx.x; i < end; i += 256) {
+        const int cl = i / cpr, c = g * cpg + cl;
+        const float sc = rstd * to_f32<T>(gamma[c]), b = to_f32<T>(beta[c]);
+        const float d = (a ? to_f32<T>(a[row0 + cl]) : 0.f) - mean;
+        const int64_t off = row0 * HW + (int64_t)i * VEC;
+        const Chunk<T> v = load_chunk(x + off);
+        Chunk<T> o;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) o.v[e] = from_f32<T>(act_f<SILU>(fmaf(to_f32<T>(v.v[e]) + d, sc, b)));
+        *reinterpret_cast<Chunk<T>*>(y + off) = o;
+    }
+}
+
+// part[(n·C + c)·3 + {0,1,2}] = Σ dz, Σ dz·x̂, Σ x̂ over row (n,c);  dz = dy·act'(x̂γ+β)
+template <typename T, bool SILU>
+__global__ __launch_bounds__(256) void nchw_stats_bwd_kernel(const T* dy, const T* x, const T* a, const T* gamma, const T* beta,
+                                                             const float* mean, const float* rstd, float* part, int rows, int C,
+                                                             int HW, int G) {
+    constexpr int VEC = ElemTraits<T>::kVec;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int n = row / C, c = row - n * C, ng = n * G + c / (C / G);
+    const float rs = rstd[ng], d = (a ? to_f32<T>(a[row]) : 0.f) - mean[ng];
+    const float gm = to_f32<T>(gamma[c]), b = to_f32<T>(beta[c]);
+    const T* xr = x + (int64_t)row * HW;
+    const T* dr = dy + (int64_t)row * HW;
+    float p = 0.f, q = 0.f, sx = 0.f;
+    const int chunks = HW / VEC;
+#pragma unroll 2
+    for (int i = lane; i < chunks; i += 64) {
+        const Chunk<T> v = load_chunk(xr + i * VEC), w = load_chunk(dr + i * VEC);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const float xh = (to_f32<T>(v.v[e]) + d) * rs;
+            const float dz = to_f32<T>(w.v[e]) * act_grad_f<SILU>(fmaf(xh, gm, b));
+            p += dz;
+            q = fmaf(dz, xh, q);
+            sx += xh;
+        }
+    }
+    p = wave_sum(p);
+    q = wave_sum(q);
+    sx = wave_sum(sx);
+    if (lane == 0) {
+        part[(int64_t)row * 3 + 0] = p;
+        part[(int64_t)row * 3 + 1] = q;
+        part[(int64_t)row * 3 + 2] = sx;
+    }
+}
+
+template <typename T, bool SILU>
+__global__ __launch_bounds__(256) void nchw_apply_bwd_kernel(const T* dy, const T* x, const T* a, const T* gamma, const T* beta,
+                                                             const float* mean_in, const float* rstd_in, T* dx, T* da,
+                                                             const float* part, int C, int HW, int G) {
+    constexpr int VEC = ElemTraits<T>::kVec;
+    __shared__ float st[2];
+    const int ng = blockIdx.y, n = ng / G, g = ng - n * G, cpg = C / G;
+    const int64_t row0 = (int64_t)n * C + (int64_t)g * cpg;
+    if (threadIdx.x < 64) {  // c2 = Σ γ·Σdz, c1 = Σ γ·Σdz·x̂ over the group's channels, fixed order
+        float c2 = 0.f, c1 = 0.f;
+        for (int c = threadIdx.x; c < cpg; c += 64) {
+            const float gm = to_f32<T>(gamma[g * cpg + c]);
+            c2 = fmaf(gm, part[(row0 + c) * 3 + 0], c2);
+            c1 = fmaf(gm, part[(row0 + c) * 3 + 1], c1);
+        }
+        c2 = wave_sum(c2);
+        c1 = wave_sum(c1);
+        if (threadIdx.x == 0) {
+            const float inv = 1.f / ((float)cpg * (float)HW);
+            st[0] = c1 * inv;
+            st[1] = c2 * inv;
+        }
+    }
+    __syncthreads();
+    const float k1 = st[0], k2 = st[1], mean = mean_in[ng], rs = rstd_in[ng];
+    if (da && blockIdx.x == 0 && (int)threadIdx.x < cpg) {  // Σ_hw dx of each channel, from the same channel sums
+        for (int c = threadIdx.x; c < cpg; c += 256) {
+            const float* pc = part + (row0 + c) * 3;
+            da[row0 + c] = from_f32<T>(rs * (to_f32<T>(gamma[g * cpg + c]) * pc[0] - (float)HW * k2 - k1 * pc[2]));
+        }
+    }
+    const int cpr = HW / VEC, total = cpg * cpr;
+    const int per = (total + gridDim.x - 1) / gridDim.x;
+    const int end = min(total, (int)(blockIdx.x + 1) * per);
+    for (int i = blockIdx.x * per + threadIdx.x; i < end; i += 256) {
+        const int cl = i / cpr, c = g * cpg + cl;
+        const float gm = to_f32<T>(gamma[c]), b = to_f32<T>(beta[c]);
+        const float d = (a ? to_f32<T>(a[row0 + cl]) : 0.f) - mean;
+        const int64_t off = row0 * HW + (int64_t)i * VEC;
+        const Chunk<T> v = load_chunk(x + off), w = load_chunk(dy + off);
+        Chunk<T> o;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const float xh = (to_f32<T>(v.v[e]) + d) * rs;
+            const float dz = to_f32<T>(w.v[e]) * act_grad_f<SILU>(fmaf(xh, gm, b));
+            o.v[e] = from_f32<T>(rs * (fmaf(dz, gm, -k2) - xh * k1));
+        }
+        *reinterpret_cast<Chunk<T>*>(dx + off) = o;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- NHWC
+// Geometry shared by the four NHWC kernels: thread t owns channels [8·cx, 8·cx+8) of rows ry, ry+RP, … of its workgroup's
+// row block; threads with ry ≥ RP (512 is not a multiple of C/8) idle.
+struct NhwcThread {
+    int cx, ry, RP;
+    bool active;
+    __device__ NhwcThread(int C) {
+        const int CH = C / 8;
+        RP = kNhwcThreads / CH;
+        ry = threadIdx.x / CH;
+        cx = threadIdx.x - ry * CH;
+        active = ry < RP;
+    }
+};
+
+__device__ __forceinline__ void lds_put8(float* dst, const float* v) {
+    *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
+}
+
+// the shift of group g of sample n: its first element of row 0 (plus the addend), the same in every workgroup
+template <typename T> __device__ __forceinline__ float nhwc_shift(const T* xn, const T* an, int c_first) {
+    return to_f32<T>(xn[c_first]) + (an ? to_f32<T>(an[c_first]) : 0.f);
+}
+
+// gpart[((n·G + g)·S + s)·2 + {0,1}] = Σ v, Σ v² over the row block, v = x + a − shift(n,g)
+template <typename T>
+__global__ __launch_bounds__(kNhwcThreads) void nhwc_stats_fwd_kernel(const T* x, const T* a, float* gpart, int C, int HW, int G,
+                                                                      int rpb) {
+    __shared__ float red[2][kNhwcLds];
+    const NhwcThread th(C);
+    const int n = blockIdx.y, S = gridDim.x, cpg = C / G, c0 = th.cx * 8;
+    const T* xn = x + (int64_t)n * HW * C;
+    const T* an = a ? a + (int64_t)n * C : nullptr;
+    if (th.active) {
+        float d[8], s[8], ss[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int c = c0 + e;
+            d[e] = (an ? to_f32<T>(an[c]) : 0.f) - nhwc_shift(xn, an, (c / cpg) * cpg);
+            s[e] = ss[e] = 0.f;
+        }
+        const int r1 = min(HW, (int)(blockIdx.x + 1) * rpb);
+#pragma unroll 4
+        for (int r = blockIdx.x * rpb + th.ry; r < r1; r += th.RP) {
+            const Chunk<T> v = load_chunk(xn + (int64_t)r * C + c0);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float u = to_f32<T>(v.v[e]) + d[e];
+                s[e] += u;
+                ss[e] = fmaf(u, u, ss[e]);
+            }
+        }
+        lds_put8(&red[0][th.ry * C + c0], s);
+        lds_put8(&red[1][th.ry * C + c0], ss);
+    }
+    __syncthreads();
+    for (int g = threadIdx.x; g < G; g += kNhwcThreads) {
+        float s = 0.f, ss = 0.f;
+        for (int c = g * cpg; c < (g + 1) * cpg; ++c)
+            for (int r = 0; r < th.RP; ++r) {
+                s += red[0][r * C + c];
+                ss += red[1][r * C + c];
+            }
+        float* o = gpart + (((int64_t)n * G + g) * S + blockIdx.x) * 2;
+        o[0] = s;
+        o[1] = ss;
+    }
+}
+
+template <typename T, bool SILU>
+__global__ __launch_bounds__(kNhwcThreads) void nhwc_apply_fwd_kernel(const T* x, const T* a, const T* gamma, const T* beta, T* y,
+                                                                      float* mean_out, float* rstd_out, const float* gpart, int C,
+                                                                      int HW, int G, int S, int rpb, float eps) {
+    __shared__ float st[2][kMaxGroups];
+    const NhwcThread th(C);
+    const int n = blockIdx.y, cpg = C / G, c0 = th.cx * 8;
+    const T* xn = x + (int64_t)n * HW * C;
+    const T* an = a ? a + (int64_t)n * C : nullptr;
+    for (int g = threadIdx.x; g < G; g += kNhwcThreads) {
+        const float* p = gpart + ((int64_t)n * G + g) * S * 2;
+        float s = 0.f, ss = 0.f;
+        for (int i = 0; i < S; ++i) {
+            s += p[2 * i];
+            ss += p[2 * i + 1];
+        }
+        const float inv = 1.f / ((float)cpg * (float)HW), m = s * inv;
+        const float mean = nhwc_shift(xn, an, g * cpg) + m, rstd = rsqrtf(fmaxf(fmaf(-m, m, ss * inv), 0.f) + eps);
+        st[0][g] = mean;
+        st[1][g] = rstd;
+        if (blockIdx.x == 0) {
+            mean_out[n * G + g] = mean;
+            rstd_out[n * G + g] = rstd;
+        }
+    }
+    __syncthreads();
+    if (!th.active) return;
+    float d[8], sc[8], b[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int c = c0 + e, g = c / cpg;
+        d[e] = (an ? to_f32<T>(an[c]) : 0.f) - st[0][g];
+        sc[e] = st[1][g] * to_f32<T>(gamma[c]);
+        b[e] = to_f32<T>(beta[c]);
+    }
+    T* yn = y + (int64_t)n * HW * C;
+    const int r1 = min(HW, (int)(blockIdx.x + 1) * rpb);
+#pragma unroll 4
+    for (int r = blockIdx.x * rpb + th.ry; r < r1; r += th.RP) {
+        const Chunk<T> v = load_chunk(xn + (int64_t)r * C + c0);
+        Chunk<T> o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o.v[e] = from_f32<T>(act_f<SILU>(fmaf(to_f32<T>(v.v[e]) + d[e], sc[e], b[e])));
+        *reinterpret_cast<Chunk<T>*>(yn + (int64_t)r * C + c0) = o;
+    }
+}
+
+// gpart[((n·G + g)·S + s)·2 + {0,1}] = Σ γ·dz·x̂, Σ γ·dz over the row block and the group's channels;
+// with DA also cpart[((n·S + s)·3 + {0,1,2})·C + c] = Σ dz, Σ dz·x̂, Σ x̂ over the row block per channel
+template <typename T, bool SILU, bool DA>
+__global__ __launch_bounds__(kNhwcThreads) void nhwc_stats_bwd_kernel(const T* dy, const T* x, const T* a, const T* gamma,
+                                                                      const T* beta, const float* mean, const float* rstd,
+                                                                      float* gpart, float* cpart, int C, int HW, int G, int rpb) {
+    __shared__ float red[DA ? 3 : 2][kNhwcLds];
+    const NhwcThread th(C);
+    const int n = blockIdx.y, S = gridDim.x, cpg = C / G, c0 = th.cx * 8;
+    const T* xn = x + (int64_t)n * HW * C;
+    const T* dn = dy + (int64_t)n * HW * C;
+    if (th.active) {
+        float d[8], rs[8], gm[8], b[8], p[8], q[8], sx[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int c = c0 + e, ng = n * G + c / cpg;
+            d[e] = (a ? to_f32<T>(a[(int64_t)n * C + c]) : 0.f) - mean[ng];
+            rs[e] = rstd[ng];
+            gm[e] = to_f32<T>(gamma[c]);
+            b[e] = to_f32<T>(beta[c]);
+            p[e] = q[e] = sx[e] = 0.f;
+        }
+        const int r1 = min(HW, (int)(blockIdx.x + 1) * rpb);
+#pragma unroll 2
+        for (int r = blockIdx.x * rpb + th.ry; r < r1; r += th.RP) {
+            const Chunk<T> v = load_chunk(xn + (int64_t)r * C + c0), w = load_chunk(dn + (int64_t)r * C + c0);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float xh = (to_f32<T>(v.v[e]) + d[e]) * rs[e];
+                const float dz = to_f32<T>(w.v[e]) * act_grad_f<SILU>(fmaf(xh, gm[e], b[e]));
+                p[e] += dz;
+                q[e] = fmaf(dz, xh, q[e]);
+                if (DA) sx[e] += xh;
+            }
+        }
+        lds_put8(&red[0][th.ry * C + c0], p);
+        lds_put8(&red[1][th.ry * C + c0], q);
+        if (DA) lds_put8(&red[2][th.ry * C + c0], sx);
+    }
+    __syncthreads();
+    for (int g = threadIdx.x; g < G; g += kNhwcThreads) {
+        float c1 = 0.f, c2 = 0.f;
+        for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
+            float pc = 0.f, qc = 0.f;
+            for (int r = 0; r < th.RP; ++r) {
+                pc += red[0][r * C + c];
+                qc += red[1][r * C + c];
+            }
+            const float gmc = to_f32<T>(gamma[c]);
+            c2 = fmaf(gmc, pc, c2);
+            c1 = fmaf(gmc, qc, c1);
+        }
+        float* o = gpart + (((int64_t)n * G + g) * S + blockIdx.x) * 2;
+        o[0] = c1;
+        o[1] = c2;
+    }
+    if (DA) {
+        for (int c = threadIdx.x; c < C; c += kNhwcThreads) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                float v = 0.f;
+                for (int r = 0; r < th.RP; ++r) v += red[j][r * C + c];
+                cpart[(((int64_t)n * S + blockIdx.x) * 3 + j) * C + c] = v;
+            }
+        }
+    }
+}
+
+template <typename T, bool SILU>
+__global__ __launch_bounds__(kNhwcThreads) void nhwc_apply_bwd_kernel(const T* dy, const T* x, const T* a, const T* gamma,
+                                                                      const T* beta, const float* mean, const float* rstd, T* dx,
+                                                                      T* da, const float* gpart, const float* cpart, int C, int HW,
+                                                                      int G, int S, int rpb) {
+    __shared__ float st[2][kMaxGroups];
+    const NhwcThread th(C);
+    const int n = blockIdx.y, cpg = C / G, c0 = th.cx * 8;
+    for (int g = threadIdx.x; g < G; g += kNhwcThreads) {
+        const float* p = gpart + ((int64_t)n * G + g) * S * 2;
+        float c1 = 0.f, c2 = 0.f;
+        for (int i = 0; i < S; ++i) {
+            c1 += p[2 * i];
+            c2 += p[2 * i + 1];
+        }
+        const float inv = 1.f / ((float)cpg * (float)HW);
+        st[0][g] = c1 * inv;
+        st[1][g] = c2 * inv;
+    }
+    __syncthreads();
+    if (da && blockIdx.x == 0) {  // Σ_hw dx of each channel from the per-channel partials, fixed order over the row blocks
+        for (int c = threadIdx.x; c < C; c += kNhwcThreads) {
+            float pc = 0.f, sxc = 0.f;
+            for (int i = 0; i < S; ++i) {
+                pc += cpart[(((int64_t)n * S + i) * 3 + 0) * C + c];
+                sxc += cpart[(((int64_t)n * S + i) * 3 + 2) * C + c];
+            }
+            const int g = c / cpg;
+            da[(int64_t)n * C + c] =
+                from_f32<T>(rstd[n * G + g] * (to_f32<T>(gamma[c]) * pc - (float)HW * st[1][g] - st[0][g] * sxc));
+        }
+    }
+    if (!th.active) return;
+    float d[8], rs[8], gm[8], b[8], k1[8], k2[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int c = c0 + e, g = c / cpg;
+        d[e] = (a ? to_f32<T>(a[(int64_t)n * C + c]) : 0.f) - mean[n * G + g];
+        rs[e] = rstd[n * G + g];
+        gm[e] = to_f32<T>(gamma[c]);
+        b[e] = to_f32<T>(beta[c]);
+        k1[e] = st[0][g];
+        k2[e] = st[1][g];
+    }
+    const T* xn = x + (int64_t)n * HW * C;
+    const T* dn = dy + (int64_t)n * HW * C;
+    T* on = dx + (int64_t)n * HW * C;
+    const int r1 = min(HW, (int)(blockIdx.x + 1) * rpb);
+#pragma unroll 2
+    for (int r = blockIdx.x * rpb + th.ry; r < r1; r += th.RP) {
+        const Chunk<T> v = load_chunk(xn + (int64_t)r * C + c0), w = load_chunk(dn + (int64_t)r * C + c0);
+        Chunk<T> o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float xh = (to_f32<T>(v.v[e]) + d[e]) * rs[e];
+            const float dz = to_f32<T>(w.v[e]) * act_grad_f<SILU>(fmaf(xh, gm[e], b[e]));
+            o.v[e] = from_f32<T>(rs[e] * (fmaf(dz, gm[e], -k2[e]) - xh * k1[e]));
+        }
+        *reinterpret_cast<Chunk<T>*>(on + (int64_t)r * C + c0) = o;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- host side
+struct NhwcPlan {
+    int S, rpb_stats;   // statistics: S row blocks of rpb_stats rows per sample
+    int SA, rpb_apply;  // apply: SA row blocks of rpb_apply rows per sample
+};
+
+// About 256 statistics workgroups (one per CU; each also costs every apply workgroup a partial to fold) and about 1024 apply
+// workgroups over the N samples, and at least 4 (2) rows per thread where the tensor is small.
+NhwcPlan nhwc_plan(int N, int C, int HW) {
+    const int RP = kNhwcThreads / (C / 8);
+    auto split = [&](int want, int min_rows, int cap) {
+        int s = (want + N - 1) / N;
+        const int most = (HW + RP * min_rows - 1) / (RP * min_rows);
+        if (s > most) s = most;
+        if (s > cap) s = cap;
+        if (s < 1) s = 1;
+        return (HW + s - 1) / s;  // rows per block
+    };
+    NhwcPlan p;
+    p.rpb_stats = split(256, 4, kMaxSplit);
+    p.S = (HW + p.rpb_stats - 1) / p.rpb_stats;
+    p.rpb_apply = split(1024, 2, 65535);
+    p.SA = (HW + p.rpb_apply - 1) / p.rpb_apply;
+    return p;
+}
+
+int nchw_slices(int N, int G, int chunks_per_slab) {  // apply workgroups per (n,group) slab: about 2048 in all, ≥ 512 chunks each
+    int s = (2048 + N * G - 1) / (N * G);
+    const int most = (chunks_per_slab + 511) / 512;
+    if (s > most) s = most;
+    return s < 1 ? 1 : s;
+}
+
+int64_t align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
+
+int check_shape(int N, int C, int HW, int G, int channels_last) {
+    if (N < 1 || C < 1 || HW < 1 || G < 1 || C % G) return LORA_E_BADARG;
+    if (G > kMaxGroups) return LORA_E_UNSUPPORTED;
+    if (channels_last ? (C % 8 != 0 || C / 8 > kNhwcThreads) : (HW % 8 != 0)) return LORA_E_UNSUPPORTED;
+    if ((int64_t)N * G > 65535 || N > 65535) return LORA_E_UNSUPPORTED;
+    return LORA_OK;
+}
+
+template <typename T, bool SILU>
+int run_fwd(const void* x_, const void* a_, const void* gamma_, const void* beta_, void* y_, float* mean, float* rstd, void* ws,
+            int N, int C, int HW, int G, float eps, int channels_last, hipStream_t s) {
+    const T *x = static_cast<const T*>(x_), *a = static_cast<const T*>(a_), *gamma = static_cast<const T*>(gamma_),
+            *beta = static_cast<const T*>(beta_);
+    T* y = static_cast<T*>(y_);
+    float* part = static_cast<float*>(ws);
+    if (channels_last) {
+        const NhwcPlan p = nhwc_plan(N, C, HW);
+        hipLaunchKernelGGL(nhwc_stats_fwd_kernel<T>, dim3(p.S, N), dim3(kNhwcThreads), 0, s, x, a, part, C, HW, G, p.rpb_stats);
+        hipLaunchKernelGGL((nhwc_apply_fwd_kernel<T, SILU>), dim3(p.SA, N), dim3(kNhwcThreads), 0, s, x, a, gamma, beta, y, mean,
+                           rstd, part, C, HW, G, p.S, p.rpb_apply, eps);
+    } else {
+        const int rows = N * C;
+        hipLaunchKernelGGL(nchw_stats_fwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, s, x, a, part, rows, HW);
+        hipLaunchKernelGGL((nchw_apply_fwd_kernel<T, SILU>), dim3(nchw_slices(N, G, C / G * (HW / 8)), N * G), dim3(256), 0, s, x,
+                           a, gamma, beta, y, mean, rstd, part, C, HW, G, eps);
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+template <typename T, bool SILU>
+int run_bwd(const void* dy_, const void* x_, const void* a_, const void* gamma_, const void* beta_, const float* mean,
+            const float* rstd, void* dx_, void* da_, void* ws, int N, int C, int HW, int G, int channels_last, hipStream_t s) {
+    const T *dy = static_cast<const T*>(dy_), *x = static_cast<const T*>(x_), *a = static_cast<const T*>(a_),
+            *gamma = static_cast<const T*>(gamma_), *beta = static_cast<const T*>(beta_);
+    T *dx = static_cast<T*>(dx_), *da = static_cast<T*>(da_);
+    float* part = static_cast<float*>(ws);
+    if (channels_last) {
+        const NhwcPlan p = nhwc_plan(N, C, HW);
+        float* cpart = part + align16((int64_t)N * G * p.S * 2 * 4) / 4;
+        if (da)
+            hipLaunchKernelGGL((nhwc_stats_bwd_kernel<T, SILU, true>), dim3(p.S, N), dim3(kNhwcThreads), 0, s, dy, x, a, gamma, beta,
+                               mean, rstd, part, cpart, C, HW, G, p.rpb_stats);
+        else
+            hipLaunchKernelGGL((nhwc_stats_bwd_kernel<T, SILU, false>), dim3(p.S, N), dim3(kNhwcThreads), 0, s, dy, x, a, gamma, beta,
+                               mean, rstd, part, cpart, C, HW, G, p.rpb_stats);
+        hipLaunchKernelGGL((nhwc_apply_bwd_kernel<T, SILU>), dim3(p.SA, N), dim3(kNhwcThreads), 0, s, dy, x, a, gamma, beta, mean,
+                           rstd, dx, da, part, cpart, C, HW, G, p.S, p.rpb_apply);
+    } else {
+        const int rows = N * C;
+        hipLaunchKernelGGL((nchw_stats_bwd_kernel<T, SILU>), dim3((rows + 3) / 4), dim3(256), 0, s, dy, x, a, gamma, beta, mean,
+                           rstd, part, rows, C, HW, G);
+        hipLaunchKernelGGL((nchw_apply_bwd_kernel<T, SILU>), dim3(nchw_slices(N, G, C / G * (HW / 8)), N * G), dim3(256), 0, s, dy,
+                           x, a, gamma, beta, mean, rstd, dx, da, part, C, HW, G);
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t group_norm_act_workspace_bytes(int N, int C, int HW, int groups, int channels_last, int want_da) {
+    if (check_shape(N, C, HW, groups, channels_last) != LORA_OK) return 0;
+    if (!channels_last) return align16((int64_t)N * C * 3 * 4);
+    const NhwcPlan p = nhwc_plan(N, C, HW);
+    return align16((int64_t)N * groups * p.S * 2 * 4) + (want_da ? align16((int64_t)N * p.S * 3 * C * 4) : 0);
+}
+
+extern "C" int group_norm_act_fwd(const void* x, const void* addend, const void* gamma, const void* beta, void* y, float* mean,
+                                  float* rstd, void* workspace, int N, int C, int HW, int groups, float eps, int act,
+                                  int channels_last, int dtype, void* stream) {
+    if (!x || !gamma || !beta || !y || !mean || !rstd || !workspace || (act != 0 && act != 1)) return LORA_E_BADARG;
+    if (const int st = check_shape(N, C, HW, groups, channels_last)) return st;
+    if (!aligned16(x) || !aligned16(y) || !aligned16(workspace)) return LORA_E_ALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case LORA_F16:
+            return act ? run_fwd<half_t, true>(x, addend, gamma, beta, y, mean, rstd, workspace, N, C, HW, groups, eps, channels_last, s)
+                       : run_fwd<half_t, false>(x, addend, gamma, beta, y, mean, rstd, workspace, N, C, HW, groups, eps, channels_last, s);
+        case LORA_BF16:
+            return act ? run_fwd<bf16_t, true>(x, addend, gamma, beta, y, mean, rstd, workspace, N, C, HW, groups, eps, channels_last, s)
+                       : run_fwd<bf16_t, false>(x, addend, gamma, beta, y, mean, rstd, workspace, N, C, HW, groups, eps, channels_last, s);
+        case LORA_F32: return LORA_E_UNSUPPORTED;
+        default: return LORA_E_BADARG;
+    }
+}
+
+extern "C" int group_norm_act_bwd(const void* dy, const void* x, const void* addend, const void* gamma, const void* beta,
+                                  const float* mean, const float* rstd, void* dx, void* da, void* workspace, int N, int C, int HW,
+                                  int groups, int act, int channels_last, int dtype, void* stream) {
+    if (!dy || !x || !gamma || !beta || !mean || !rstd || !dx || !workspace || (act != 0 && act != 1)) return LORA_E_BADARG;
+    if (da && !addend) return LORA_E_BADARG;
+    if (const int st = check_shape(N, C, HW, groups, channels_last)) return st;
+    if (!aligned16(dy) || !aligned16(x) || !aligned16(dx) || !aligned16(workspace)) return LORA_E_ALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case LORA_F16:
+            return act ? run_bwd<half_t, true>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s)
+                       : run_bwd<half_t, false>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s);
+        case LORA_BF16:
+            return act ? run_bwd<bf16_t, true>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s)
+                       : run_bwd<bf16_t, false>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s);
+        case LORA_F32: return LORA_E_UNSUPPORTED;
+        default: return LORA_E_BADARG;
+    }
+}

@@ -7,7 +7,8 @@ exactly like diffusers' `UNet2DConditionModel` does for the reference:
     to_q, to_k, to_v, to_out.0;
   * top-level registration order down_blocks, up_blocks, mid_block (pinned by the 144-entry index table of
     example_loras/lora_disney.safetensors; tests/test_finder_order.py checks it).
-Everything that is NOT the hot path (convolutions, GroupNorm, softmax(QKᵀ)V) is stock PyTorch-ROCm.
+Everything that is NOT the hot path (convolutions, softmax(QKᵀ)V) is stock PyTorch-ROCm; on the GPU in f16 / bf16 the
+GroupNorms run through the fused norm + addend + SiLU passes of diffusion_finetuning_amd.norm (`_norm_act` below).
 Weights are random-init: there are no SD checkpoints offline.
 """
 import math
@@ -79,6 +80,20 @@ class TimestepEmbedding(nn.Module):
         return self.linear_2(self.act(self.linear_1(x)))
 
 
+def _fused_norms(x):
+    """True where the GroupNorms go through `group_norm_act`: 16-bit tensors on the GPU.  fp32 and the CPU keep the stock
+    modules (the CPU oracle runs through them); an fp32 module under autocast gets the stock composite inside
+    `group_norm_act` (γ/β are not of the activation's type)."""
+    return x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)
+
+
+def _norm_act(norm: nn.GroupNorm, x, act: bool, addend=None):
+    """act(norm(x + addend[:, :, None, None])) in one statistics and one apply pass each way (csrc/norm.hip)."""
+    from diffusion_finetuning_amd.norm import group_norm_act
+
+    return group_norm_act(x, norm.num_groups, norm.weight, norm.bias, norm.eps, act, addend)
+
+
 class ResnetBlock2D(nn.Module):
     def __init__(self, cin, cout, temb, groups):
         super().__init__()
@@ -90,6 +105,12 @@ class ResnetBlock2D(nn.Module):
         self.conv_shortcut = nn.Conv2d(cin, cout, 1) if cin != cout else None
 
     def forward(self, x, temb):
+        if _fused_norms(x) and type(self.conv1) is nn.Conv2d:
+            # conv1's bias and the time embedding are per-(n,c) constants over the image: both ride into norm2 as its addend
+            # instead of one bias pass and one broadcast-add pass over the activation
+            h = F.conv2d(_norm_act(self.norm1, x, True), self.conv1.weight, None, padding=1)
+            h = self.conv2(_norm_act(self.norm2, h, True, self.time_emb_proj(F.silu(temb)) + self.conv1.bias))
+            return (x if self.conv_shortcut is None else self.conv_shortcut(x)) + h
         h = self.conv1(F.silu(self.norm1(x)))
         h = h + self.time_emb_proj(F.silu(temb))[:, :, None, None]
         h = self.conv2(F.silu(self.norm2(h)))
@@ -195,7 +216,7 @@ class Transformer2DModel(nn.Module):
     def forward(self, x, context):
         b, c, h, w = x.shape
         res = x
-        x = self.norm(x)
+        x = _norm_act(self.norm, x, False) if _fused_norms(x) else self.norm(x)
         if x.is_cuda and not self.linear_projection:
             # A 1×1 convolution IS a linear layer over the channels.  On the GPU run it on the token layout the
             # transformer blocks need anyway (one NCHW→NHWC copy in, one back): the convolution library would
@@ -348,5 +369,6 @@ class UNet2DConditionModel(nn.Module):
         x = self.mid_block(x, temb, ctx)
         for blk in self.up_blocks:
             x = blk(x, skips, temb, ctx)
-        x = self.conv_out(F.silu(self.conv_norm_out(x)))
+        x = _norm_act(self.conv_norm_out, x, True) if _fused_norms(x) else F.silu(self.conv_norm_out(x))
+        x = self.conv_out(x)
         return UNetOutput(sample=x)

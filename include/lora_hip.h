@@ -384,6 +384,28 @@ int attn_merge_heads_strided(const void* src, void* dst, int B, int N, int H, in
                              int64_t sN, int dtype, void* stream);
 
 /*
+ * GroupNorm of the UNet's convolution trunk with its neighbours folded in (csrc/norm.hip):
+ *     y = act(GroupNorm(x + a)),   x [N,C,H,W] with HW = H·W,  a [N,C] an optional per-(n,c) addend (nullable),
+ *     gamma / beta [C] (same dtype as x),  act = 1: SiLU, 0: identity.
+ * channels_last = 0: x, y, dy, dx are NCHW-contiguous (needs HW % 8 == 0); 1: NHWC-contiguous, torch's channels_last
+ * (needs C % 8 == 0, C <= 4096).  The group width C/groups may be anything.  groups <= 256.  dtype f16 / bf16 only
+ * (LORA_E_UNSUPPORTED for f32 and for the shapes above: the caller keeps the stock composite).
+ * Statistics, the normalised value and the activation are fp32 up to the one rounding of y / dx / da.  Two launches each way
+ * (statistics, apply), partial sums folded in a fixed order, no atomics: results are bit-reproducible.
+ *   group_norm_act_fwd : writes y and the per-(n,group) mean / rstd [N,groups] fp32 of x + a that the backward takes.
+ *   group_norm_act_bwd : recomputes the normalised value and act' from x; writes dx and, when da is not null, da [N,C] (the
+ *                        gradient of the addend, a by-product of the per-channel sums).  No gamma / beta gradients.
+ * workspace: group_norm_act_workspace_bytes(...) bytes (0: unsupported shape), 16-byte aligned, caller-owned, per call.
+ */
+int64_t group_norm_act_workspace_bytes(int N, int C, int HW, int groups, int channels_last, int want_da);
+int group_norm_act_fwd(const void* x, const void* addend /* nullable */, const void* gamma, const void* beta, void* y,
+                       float* mean, float* rstd, void* workspace, int N, int C, int HW, int groups, float eps, int act,
+                       int channels_last, int dtype, void* stream);
+int group_norm_act_bwd(const void* dy, const void* x, const void* addend /* nullable */, const void* gamma, const void* beta,
+                       const float* mean, const float* rstd, void* dx, void* da /* nullable */, void* workspace, int N, int C,
+                       int HW, int groups, int act, int channels_last, int dtype, void* stream);
+
+/*
  * Token-embedding rows for a text encoder whose INPUT EMBEDDINGS train next to the UNet's LoRA factors: the tuning phase of
  * lora_diffusion/cli_lora_pti.py with continue_inversion (default, :528) puts `text_encoder.get_input_embeddings().parameters()`
  * in the optimizer (:706-722) and runs `text_encoder(batch["input_ids"])[0]` inside loss_step (:199-206) — BASELINE config 5,
