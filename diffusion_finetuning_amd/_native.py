@@ -789,8 +789,11 @@ def group_norm_act_layout(x):
 
 
 def group_norm_act_supported(x, groups: int, layout) -> bool:
+    """Whether the kernels take x: a dense layout, a shape they cover, and storage that starts on a 16-byte boundary (a dense
+    view at an odd offset into its buffer does not; the entry points answer LORA_E_ALIGN to it)."""
     N, C, H, W = x.shape
-    return layout is not None and C % groups == 0 and lib().group_norm_act_workspace_bytes(N, C, H * W, groups, layout, 0) > 0
+    return (layout is not None and C % groups == 0 and x.data_ptr() % 16 == 0 and
+            lib().group_norm_act_workspace_bytes(N, C, H * W, groups, layout, 0) > 0)
 
 
 def _norm_workspace(x, groups: int, layout: int, want_da: bool):

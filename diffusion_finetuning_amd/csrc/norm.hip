@@ -11,8 +11,20 @@
 //     a multiple of 8) over a block of rows; a workgroup reduces its rows × all channels through LDS to one partial per group,
 //     S partials per (n,group) in all, and the apply kernels fold them.
 // Every fold runs in a fixed order and there are no float atomics: two runs are bit-identical.  Statistics, the normalised
-// value and the activation are fp32 up to the single rounding of the output.  Sums of squares are taken about a shift (an
-// element of the group / channel), so a mean that is large against the deviation costs no digits.
+// value and the activation are fp32 up to the single rounding of the output.
+//
+// Statistics are sums of d and d² about a shift, merged in centred form, so a mean that is large against the deviation costs
+// no digits:
+//   * NCHW: the shift of a row is its first element and the row leaves (mean, M2 = Σd² − (Σd)²/HW); the group's cpg rows are
+//     merged about the group mean.  An element far from the rest of its row costs up to about H·W·2⁻²⁴ of the group's
+//     variance when it is the row's first one (2.4e-5 of rstd measured at H·W = 4096).
+//   * NHWC: a thread's shift per channel is its OWN first row, over the n_t rows it reads of one row block (4 … 32 for the
+//     planner's splits unless H·W exceeds 64·RP·32), and it leaves (n_t, mean_t, M2_t).  The workgroup's fold through LDS and
+//     the fold of the S row blocks merge such triples in two passes: the weighted mean μ of the means, then
+//     S1 = Σ n(mean_t − μ) and S2 = Σ M2_t + n(mean_t − μ)², giving (μ + S1/n, S2 − S1²/n) with S1 ≈ 0.  An element far from
+//     the rest of its group, wherever it sits, costs at most about n_t·2⁻²³ of the variance.  (One shift per group, the
+//     group's first element, lost up to 9.5e-2 of rstd at 262 144 elements: tests/test_gpu_norm_edges.py.)
+// The mean is within a few fp32 roundings of the exact one at its own magnitude.
 #include "common.h"
 
 namespace {
@@ -174,10 +186,13 @@ __global__ __launch_bounds__(256) void nchw_apply_bwd_kernel(const T* dy, const 
     }
     __syncthreads();
     const float k1 = st[0], k2 = st[1], mean = mean_in[ng], rs = rstd_in[ng];
-    if (da && blockIdx.x == 0 && (int)threadIdx.x < cpg) {  // Σ_hw dx of each channel, from the same channel sums
+    // Σ_hw dx of each channel, from the same channel sums.  dx sums to zero over a group, so a group of one channel has
+    // da = 0 exactly: written as such, not as what the three terms leave of each other in fp32
+    if (da && blockIdx.x == 0 && (int)threadIdx.x < cpg) {
         for (int c = threadIdx.x; c < cpg; c += 256) {
             const float* pc = part + (row0 + c) * 3;
-            da[row0 + c] = from_f32<T>(rs * (to_f32<T>(gamma[g * cpg + c]) * pc[0] - (float)HW * k2 - k1 * pc[2]));
+            const float v = rs * (to_f32<T>(gamma[g * cpg + c]) * pc[0] - (float)HW * k2 - k1 * pc[2]);
+            da[row0 + c] = from_f32<T>(cpg == 1 ? 0.f : v);
         }
     }
     const int cpr = HW / VEC, total = cpg * cpr;
@@ -220,12 +235,11 @@ __device__ __forceinline__ void lds_put8(float* dst, const float* v) {
     *reinterpret_cast<f32x4*>(dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
 }
 
-// the shift of group g of sample n: its first element of row 0 (plus the addend), the same in every workgroup
-template <typename T> __device__ __forceinline__ float nhwc_shift(const T* xn, const T* an, int c_first) {
-    return to_f32<T>(xn[c_first]) + (an ? to_f32<T>(an[c_first]) : 0.f);
-}
+// rows of row block s (rpb rows each, the last one short) and how many of them the thread row ry of RP reads
+__device__ __forceinline__ int nhwc_block_rows(int s, int rpb, int HW) { return min(HW, (s + 1) * rpb) - s * rpb; }
+__device__ __forceinline__ int nhwc_thread_rows(int rows, int ry, int RP) { return rows / RP + (ry < rows % RP); }
 
-// gpart[((n·G + g)·S + s)·2 + {0,1}] = Σ v, Σ v² over the row block, v = x + a − shift(n,g)
+// gpart[((n·G + g)·S + s)·2 + {0,1}] = mean and centred sum of squares of x + a over the row block and the group's channels
 template <typename T>
 __global__ __launch_bounds__(kNhwcThreads) void nhwc_stats_fwd_kernel(const T* x, const T* a, float* gpart, int C, int HW, int G,
                                                                       int rpb) {
@@ -234,60 +248,84 @@ __global__ __launch_bounds__(kNhwcThreads) void nhwc_stats_fwd_kernel(const T* x
     const int n = blockIdx.y, S = gridDim.x, cpg = C / G, c0 = th.cx * 8;
     const T* xn = x + (int64_t)n * HW * C;
     const T* an = a ? a + (int64_t)n * C : nullptr;
+    const int rb = blockIdx.x * rpb, rows = nhwc_block_rows(blockIdx.x, rpb, HW), r1 = rb + rows;
     if (th.active) {
-        float d[8], s[8], ss[8];
+        // per channel the thread's (cnt, mean, M2) about its own first row (a thread without rows: cnt = 0, any row's value)
+        const int cnt = nhwc_thread_rows(rows, th.ry, th.RP);
+        const Chunk<T> f = load_chunk(xn + (int64_t)min(rb + th.ry, r1 - 1) * C + c0);
+        float sh[8], s[8], ss[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const int c = c0 + e;
-            d[e] = (an ? to_f32<T>(an[c]) : 0.f) - nhwc_shift(xn, an, (c / cpg) * cpg);
+            sh[e] = to_f32<T>(f.v[e]);
             s[e] = ss[e] = 0.f;
         }
-        const int r1 = min(HW, (int)(blockIdx.x + 1) * rpb);
 #pragma unroll 4
-        for (int r = blockIdx.x * rpb + th.ry; r < r1; r += th.RP) {
+        for (int r = rb + th.ry; r < r1; r += th.RP) {
             const Chunk<T> v = load_chunk(xn + (int64_t)r * C + c0);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float u = to_f32<T>(v.v[e]) + d[e];
+                const float u = to_f32<T>(v.v[e]) - sh[e];
                 s[e] += u;
                 ss[e] = fmaf(u, u, ss[e]);
             }
+        }
+        const float inv = cnt ? 1.f / (float)cnt : 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float q = s[e] * inv;
+            ss[e] = fmaxf(ss[e] - s[e] * q, 0.f);
+            s[e] = cnt ? sh[e] + q + (an ? to_f32<T>(an[c0 + e]) : 0.f) : 0.f;
         }
         lds_put8(&red[0][th.ry * C + c0], s);
         lds_put8(&red[1][th.ry * C + c0], ss);
     }
     __syncthreads();
-    for (int g = threadIdx.x; g < G; g += kNhwcThreads) {
-        float s = 0.f, ss = 0.f;
-        for (int c = g * cpg; c < (g + 1) * cpg; ++c)
-            for (int r = 0; r < th.RP; ++r) {
-                s += red[0][r * C + c];
-                ss += red[1][r * C + c];
+    for (int g = threadIdx.x; g < G; g += kNhwcThreads) {  // merge the RP × cpg triples of group g, fixed order
+        const int ca = g * cpg, cb = ca + cpg, full = rows / th.RP, rem = rows - full * th.RP;
+        float sm = 0.f;
+        for (int r = 0; r < th.RP; ++r) {
+            const float w = (float)(full + (r < rem));
+            for (int c = ca; c < cb; ++c) sm = fmaf(w, red[0][r * C + c], sm);
+        }
+        const float tot = (float)cpg * (float)rows, mu = sm / tot;
+        float s1 = 0.f, s2 = 0.f;
+        for (int r = 0; r < th.RP; ++r) {
+            const float w = (float)(full + (r < rem));
+            for (int c = ca; c < cb; ++c) {
+                const float d = red[0][r * C + c] - mu, wd = w * d;
+                s1 += wd;
+                s2 += fmaf(wd, d, red[1][r * C + c]);
             }
+        }
+        const float cm = s1 / tot;
         float* o = gpart + (((int64_t)n * G + g) * S + blockIdx.x) * 2;
-        o[0] = s;
-        o[1] = ss;
+        o[0] = mu + cm;
+        o[1] = fmaxf(s2 - s1 * cm, 0.f);
     }
 }
 
 template <typename T, bool SILU>
 __global__ __launch_bounds__(kNhwcThreads) void nhwc_apply_fwd_kernel(const T* x, const T* a, const T* gamma, const T* beta, T* y,
                                                                       float* mean_out, float* rstd_out, const float* gpart, int C,
-                                                                      int HW, int G, int S, int rpb, float eps) {
+                                                                      int HW, int G, int S, int rpb_stats, int rpb, float eps) {
     __shared__ float st[2][kMaxGroups];
     const NhwcThread th(C);
     const int n = blockIdx.y, cpg = C / G, c0 = th.cx * 8;
     const T* xn = x + (int64_t)n * HW * C;
     const T* an = a ? a + (int64_t)n * C : nullptr;
-    for (int g = threadIdx.x; g < G; g += kNhwcThreads) {
+    for (int g = threadIdx.x; g < G; g += kNhwcThreads) {  // merge the S row blocks' (rows·cpg, mean, M2), fixed order
         const float* p = gpart + ((int64_t)n * G + g) * S * 2;
-        float s = 0.f, ss = 0.f;
+        float sm = 0.f;
+        for (int i = 0; i < S; ++i) sm = fmaf((float)nhwc_block_rows(i, rpb_stats, HW), p[2 * i], sm);
+        const float mu = sm / (float)HW;
+        float s1 = 0.f, s2 = 0.f;
         for (int i = 0; i < S; ++i) {
-            s += p[2 * i];
-            ss += p[2 * i + 1];
+            const float d = p[2 * i] - mu, wd = (float)(nhwc_block_rows(i, rpb_stats, HW) * cpg) * d;
+            s1 += wd;
+            s2 += fmaf(wd, d, p[2 * i + 1]);
         }
-        const float inv = 1.f / ((float)cpg * (float)HW), m = s * inv;
-        const float mean = nhwc_shift(xn, an, g * cpg) + m, rstd = rsqrtf(fmaxf(fmaf(-m, m, ss * inv), 0.f) + eps);
+        const float tot = (float)cpg * (float)HW, cm = s1 / tot;
+        const float mean = mu + cm, rstd = rsqrtf(fmaxf(s2 - s1 * cm, 0.f) / tot + eps);
         st[0][g] = mean;
         st[1][g] = rstd;
         if (blockIdx.x == 0) {
@@ -413,8 +451,8 @@ __global__ __launch_bounds__(kNhwcThreads) void nhwc_apply_bwd_kernel(const T* d
                 sxc += cpart[(((int64_t)n * S + i) * 3 + 2) * C + c];
             }
             const int g = c / cpg;
-            da[(int64_t)n * C + c] =
-                from_f32<T>(rstd[n * G + g] * (to_f32<T>(gamma[c]) * pc - (float)HW * st[1][g] - st[0][g] * sxc));
+            const float v = rstd[n * G + g] * (to_f32<T>(gamma[c]) * pc - (float)HW * st[1][g] - st[0][g] * sxc);
+            da[(int64_t)n * C + c] = from_f32<T>(cpg == 1 ? 0.f : v);  // one channel per group: Σ_hw dx = 0 exactly
         }
     }
     if (!th.active) return;
@@ -501,7 +539,7 @@ int run_fwd(const void* x_, const void* a_, const void* gamma_, const void* beta
         const NhwcPlan p = nhwc_plan(N, C, HW);
         hipLaunchKernelGGL(nhwc_stats_fwd_kernel<T>, dim3(p.S, N), dim3(kNhwcThreads), 0, s, x, a, part, C, HW, G, p.rpb_stats);
         hipLaunchKernelGGL((nhwc_apply_fwd_kernel<T, SILU>), dim3(p.SA, N), dim3(kNhwcThreads), 0, s, x, a, gamma, beta, y, mean,
-                           rstd, part, C, HW, G, p.S, p.rpb_apply, eps);
+                           rstd, part, C, HW, G, p.S, p.rpb_stats, p.rpb_apply, eps);
     } else {
         const int rows = N * C;
         hipLaunchKernelGGL(nchw_stats_fwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, s, x, a, part, rows, HW);

@@ -1,8 +1,10 @@
 """Autograd front of the fused GroupNorm (+ per-(n,c) addend, + SiLU) of the UNet's convolution trunk (csrc/norm.hip).
 
-The HIP path takes f16 / bf16 tensors on the HIP device that are NCHW-contiguous or channels-last and whose γ/β are frozen;
-everything else (CPU, fp32, other strides, trainable γ/β, shapes the kernels do not cover) gets the stock composite
-`F.silu(F.group_norm(x + addend[:, :, None, None]))`, which is what the caller would have written."""
+The HIP path takes f16 / bf16 tensors on the HIP device that are NCHW-contiguous or channels-last, start on a 16-byte boundary
+and whose γ/β are frozen; everything else (CPU, fp32, other strides, an x at an odd offset into its storage, trainable γ/β,
+shapes the kernels do not cover) gets the stock composite `F.silu(F.group_norm(x + addend[:, :, None, None]))`, which is what
+the caller would have written.  In the backward the forward's choice is already made: a `dy` in the other memory format, or
+one that does not start on a 16-byte boundary, is copied once into x's layout and the kernels run on the copy."""
 import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
@@ -23,7 +25,10 @@ class _GroupNormActFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dy):
         x, addend, weight, bias, mean, rstd = ctx.saved_tensors
-        dy = dy.contiguous(memory_format=torch.channels_last if ctx.layout else torch.contiguous_format)
+        fmt = torch.channels_last if ctx.layout else torch.contiguous_format
+        dy = dy.contiguous(memory_format=fmt)
+        if dy.data_ptr() % 16:  # dense but at an odd offset into its storage: the kernels read 16-byte chunks
+            dy = dy.clone(memory_format=fmt)
         want_da = addend is not None and ctx.needs_input_grad[1]
         dx, da = nat.group_norm_act_bwd(dy, x, addend, weight, bias, mean, rstd, ctx.groups, ctx.act, ctx.layout, want_da)
         return (dx if ctx.needs_input_grad[0] else None), da, None, None, None, None, None, None

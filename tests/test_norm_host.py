@@ -4,8 +4,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from diffusion_finetuning_amd import _native as nat
 from diffusion_finetuning_amd import norm as dnorm
 from tests.conftest import build_tiny_unet
+from tests.norm_cases import BIG_GROUP, NCHW_GEOMETRY, NHWC_GEOMETRY, SMALL_GROUPS
 
 
 @pytest.mark.parametrize("act", [True, False])
@@ -59,3 +61,53 @@ def test_unsupported_operands_are_told_apart_without_a_device():
     w = torch.ones(16)
     assert dnorm._hip_layout(x, 4, w, w, None) is None  # CPU
     assert dnorm._hip_layout(x.half(), 4, w.half(), w.half(), None) is None  # still CPU
+
+
+# ------------------------------------------------------------------------------------------------ C ABI, without a device
+BADARG, ALIGN, UNSUPPORTED = -1, -3, -5
+P = 1 << 20  # a 16-byte-aligned stand-in for a device pointer: every call below is refused before anything reads it
+
+
+def _fwd(x=P, addend=P, y=P, ws=P, N=2, C=16, HW=8, G=4, act=1, cl=0, dtype=1):
+    return nat.lib().group_norm_act_fwd(x, addend, P, P, y, P, P, ws, N, C, HW, G, 1e-5, act, cl, dtype, None)
+
+
+def _bwd(dy=P, x=P, addend=P, dx=P, da=P, ws=P, N=2, C=16, HW=8, G=4, act=1, cl=0, dtype=1):
+    return nat.lib().group_norm_act_bwd(dy, x, addend, P, P, P, P, dx, da, ws, N, C, HW, G, act, cl, dtype, None)
+
+
+def test_entry_points_tell_bad_arguments_from_unsupported_ones_before_any_launch():
+    for call in (_fwd, _bwd):
+        assert call(C=18, G=4) == BADARG  # C % G ≠ 0
+        assert call(act=2) == BADARG
+        assert call(dtype=7) == BADARG
+        assert call(x=None) == BADARG
+        assert call(dtype=0) == UNSUPPORTED  # f32
+        assert call(C=257 * 8, G=257, cl=0) == call(C=257 * 8, G=257, cl=1) == UNSUPPORTED  # kMaxGroups = 256
+        assert call(HW=9) == UNSUPPORTED  # NCHW rows of 16-byte chunks
+        assert call(C=12, cl=1) == UNSUPPORTED  # NHWC threads of 8 channels
+        assert call(x=P + 2) == call(ws=P + 2) == call(x=P + 8) == ALIGN
+    assert _fwd(y=P + 2) == _bwd(dy=P + 2) == _bwd(dx=P + 2) == ALIGN
+    assert _bwd(addend=None, da=P) == BADARG  # an addend gradient without an addend
+    assert _fwd(C=18, G=4, x=P + 2) == BADARG and _fwd(HW=9, x=P + 2) == UNSUPPORTED  # the shape is judged before the pointers
+
+
+def test_workspace_bytes_is_zero_for_what_the_kernels_do_not_cover_and_grows_with_da():
+    ws = nat.lib().group_norm_act_workspace_bytes
+    for want_da in (0, 1):
+        assert ws(2, 16, 9, 4, 0, want_da) == 0  # NCHW, H·W % 8 ≠ 0
+        assert ws(2, 16, 1, 4, 0, want_da) == 0  # H·W = 1
+        assert ws(2, 12, 16, 4, 1, want_da) == 0  # NHWC, C % 8 ≠ 0
+        assert ws(1, 512, 8, 512, 0, want_da) == ws(1, 512, 8, 512, 1, want_da) == 0  # G = 512
+        assert ws(1, 257 * 8, 8, 257, 1, want_da) == 0 and ws(1, 256 * 8, 8, 256, 1, want_da) > 0  # G = 257 / kMaxGroups
+        assert ws(2, 18, 8, 4, 0, want_da) == 0  # C % G ≠ 0
+        assert ws(65536, 8, 8, 1, 0, want_da) == 0  # more (n, group) slabs than a grid dimension holds
+    for cl, shapes in ((0, NCHW_GEOMETRY + [BIG_GROUP, SMALL_GROUPS]), (1, NHWC_GEOMETRY + [BIG_GROUP, SMALL_GROUPS])):
+        for N, C, G, H, W in shapes:
+            no_da, with_da = ws(N, C, H * W, G, cl, 0), ws(N, C, H * W, G, cl, 1)
+            assert 0 < no_da <= with_da and no_da % 16 == 0 and with_da % 16 == 0, (cl, N, C, G, H, W)
+            # the forward's partials: one (mean, M2) pair per row in NCHW (3 floats a row are kept for the backward's sums),
+            # at least one pair per (n, group) in NHWC
+            assert no_da >= (N * C * 3 * 4 if not cl else N * G * 2 * 4)
+            if cl:  # the per-channel partials of the addend gradient: three sums per channel and row block, at least one block
+                assert with_da - no_da >= N * 3 * C * 4
