@@ -97,6 +97,9 @@ SIGNATURES = {
     "group_norm_act_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "group_norm_act_fwd": (_i32, [_vp] * 8 + [_i32, _i32, _i32, _i32, _f32, _i32, _i32, _i32, _vp]),
     "group_norm_act_bwd": (_i32, [_vp] * 10 + [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "add_layer_norm_max_channels": (_i32, []),
+    "add_layer_norm_fwd": (_i32, [_vp] * 8 + [_i64, _i32, _f32, _i32, _vp]),
+    "add_layer_norm_bwd": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _vp]),
     "attn_ctx_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "attn_ctx_fwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "attn_ctx_bwd_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
@@ -826,6 +829,37 @@ def group_norm_act_bwd(dy, x, addend, gamma, beta, mean, rstd, groups: int, act:
                                     _ptr(da), _ptr(ws), N, C, H * W, groups, int(act), layout, dtype_code(x.dtype), _stream(x)),
            "group_norm_act_bwd")
     return dx, da
+
+
+def add_layer_norm_supported(x) -> bool:
+    """Whether the kernels of csrc/layer_norm.hip take x as rows [M, C]: dense, a width they cover, a 16-byte-aligned start."""
+    C = x.shape[-1] if x.dim() else 0
+    return (x.numel() > 0 and x.is_contiguous() and C % 8 == 0 and C <= lib().add_layer_norm_max_channels() and
+            x.data_ptr() % 16 == 0)
+
+
+def add_layer_norm_fwd(x, delta, gamma, beta, eps: float):
+    """(h, y, mean, rstd): h = x + delta (None when delta is None), y = LayerNorm(h)·gamma + beta over the last dimension,
+    mean / rstd [M] fp32 of the rounded h."""
+    _require_device(x, delta, gamma, beta)
+    C = x.shape[-1]
+    M = x.numel() // C
+    h = None if delta is None else torch.empty_like(x)
+    y = torch.empty_like(x)
+    mean = torch.empty(M, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    _check(lib().add_layer_norm_fwd(_ptr(x), _ptr(delta), _ptr(gamma), _ptr(beta), _ptr(h), _ptr(y), _ptr(mean), _ptr(rstd), M, C,
+                                    float(eps), dtype_code(x.dtype), _stream(x)), "add_layer_norm_fwd")
+    return h, y, mean, rstd
+
+
+def add_layer_norm_bwd(dy, dh, h, gamma, mean, rstd):
+    """dx = LayerNorm's input gradient + dh (dh None: without it); dy / dh dense like h and 16-byte aligned."""
+    C = h.shape[-1]
+    dx = torch.empty_like(h)
+    _check(lib().add_layer_norm_bwd(_ptr(dy), _ptr(dh), _ptr(h), _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx), h.numel() // C, C,
+                                    dtype_code(h.dtype), _stream(h)), "add_layer_norm_bwd")
+    return dx
 
 
 def attn_ctx_supported(B: int, Tq: int, Tk: int, H: int, d: int, dtype) -> bool:

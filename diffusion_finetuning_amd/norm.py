@@ -1,4 +1,5 @@
-"""Autograd front of the fused GroupNorm (+ per-(n,c) addend, + SiLU) of the UNet's convolution trunk (csrc/norm.hip).
+"""Autograd fronts of the fused norms: GroupNorm (+ per-(n,c) addend, + SiLU) of the UNet's convolution trunk (csrc/norm.hip)
+and residual add + LayerNorm of its transformer blocks (csrc/layer_norm.hip, second half of this file).
 
 The HIP path takes f16 / bf16 tensors on the HIP device that are NCHW-contiguous or channels-last, start on a 16-byte boundary
 and whose γ/β are frozen; everything else (CPU, fp32, other strides, an x at an odd offset into its storage, trainable γ/β,
@@ -60,3 +61,67 @@ def group_norm_act(x: torch.Tensor, groups: int, weight, bias, eps: float, act: 
     if addend is not None and not addend.is_contiguous():
         addend = addend.contiguous()
     return _GroupNormActFn.apply(x, addend, weight, bias, int(groups), float(eps), bool(act), layout)
+
+
+# ------------------------------------------------------------------------------------ residual add + LayerNorm (layer_norm.hip)
+class _AddLayerNormFn(torch.autograd.Function):
+    """(h, y) = (x + delta, LayerNorm(h)) with delta, or y = LayerNorm(x) without: one launch each way."""
+
+    @staticmethod
+    def forward(ctx, x, delta, weight, bias, eps):
+        # a missing dh or dy arrives as None, never as a tensor of zeros that a kernel would have to read
+        ctx.set_materialize_grads(False)
+        h, y, mean, rstd = nat.add_layer_norm_fwd(x, delta, weight, bias, eps)
+        # h (x where there is no delta) is saved, not the normalised tensor: the backward recomputes it from h, mean and rstd
+        ctx.save_for_backward(x if delta is None else h, weight, mean, rstd)
+        return y if delta is None else (h, y)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        dh, dy = grads if len(grads) == 2 else (None, grads[0])
+        if dy is None:  # only the residual path carries a gradient: it passes through, no launch
+            dx = dh
+        else:
+            h, weight, mean, rstd = ctx.saved_tensors
+            dy, dh = _dense16(dy), _dense16(dh)
+            dx = nat.add_layer_norm_bwd(dy, dh, h, weight, mean, rstd)
+        return (dx if ctx.needs_input_grad[0] else None), (dx if ctx.needs_input_grad[1] else None), None, None, None
+
+
+def _dense16(g):
+    """An upstream gradient as the kernels read it: dense rows from a 16-byte boundary, copied once when it is not."""
+    if g is None:
+        return None
+    g = g.contiguous()
+    return g.clone() if g.data_ptr() % 16 else g
+
+
+def _hip_layer_norm(x, delta, weight, bias):
+    """Whether these operands take the HIP path; everything else gets the stock composite."""
+    if not x.is_cuda or x.dtype not in (torch.float16, torch.bfloat16) or weight is None or bias is None:
+        return False
+    if torch.is_grad_enabled() and (weight.requires_grad or bias.requires_grad):
+        return False  # the kernels produce no γ/β gradients
+    for p in (weight, bias):
+        if p.dtype != x.dtype or p.shape != x.shape[-1:] or not p.is_contiguous() or p.data_ptr() % 16:
+            return False
+    if delta is not None and (delta.dtype != x.dtype or delta.shape != x.shape or not nat.add_layer_norm_supported(delta)):
+        return False
+    return nat.add_layer_norm_supported(x)
+
+
+def add_layer_norm(x: torch.Tensor, delta: torch.Tensor, weight, bias, eps: float):
+    """(h, y) with h = x + delta and y = LayerNorm(h) over the last dimension: the residual sum and the normalised tensor the
+    next sublayer reads, in one pass each way on the HIP path (the backward joins the gradient of h into dx)."""
+    if not _hip_layer_norm(x, delta, weight, bias):
+        h = x + delta
+        return h, F.layer_norm(h, (h.shape[-1],), weight, bias, eps)
+    return _AddLayerNormFn.apply(x, delta, weight, bias, float(eps))
+
+
+def layer_norm(x: torch.Tensor, weight, bias, eps: float) -> torch.Tensor:
+    """LayerNorm(x) over the last dimension; the same kernels without the add."""
+    if not _hip_layer_norm(x, None, weight, bias):
+        return F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
+    return _AddLayerNormFn.apply(x, None, weight, bias, float(eps))

@@ -81,7 +81,8 @@ class TimestepEmbedding(nn.Module):
 
 
 def _fused_norms(x):
-    """True where the GroupNorms go through `group_norm_act`: 16-bit tensors on the GPU.  fp32 and the CPU keep the stock
+    """True where the GroupNorms go through `group_norm_act` and the transformer blocks' LayerNorms through `layer_norm` /
+    `add_layer_norm`: 16-bit tensors on the GPU.  fp32 and the CPU keep the stock
     modules (the CPU oracle runs through them); an fp32 module under autocast gets the stock composite inside
     `group_norm_act` (γ/β are not of the activation's type)."""
     return x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)
@@ -92,6 +93,19 @@ def _norm_act(norm: nn.GroupNorm, x, act: bool, addend=None):
     from diffusion_finetuning_amd.norm import group_norm_act
 
     return group_norm_act(x, norm.num_groups, norm.weight, norm.bias, norm.eps, act, addend)
+
+
+def _layer_norm(norm: nn.LayerNorm, x):
+    from diffusion_finetuning_amd import norm as dnorm
+
+    return dnorm.layer_norm(x, norm.weight, norm.bias, norm.eps)
+
+
+def _add_layer_norm(norm: nn.LayerNorm, x, delta):
+    """(x + delta, norm(x + delta)) in one pass each way."""
+    from diffusion_finetuning_amd import norm as dnorm
+
+    return dnorm.add_layer_norm(x, delta, norm.weight, norm.bias, norm.eps)
 
 
 class ResnetBlock2D(nn.Module):
@@ -197,6 +211,13 @@ class BasicTransformerBlock(nn.Module):
         self.norm3 = nn.LayerNorm(dim)
 
     def forward(self, x, context):
+        if _fused_norms(x):
+            # each residual sum is written together with the LayerNorm that reads it, and in the backward each LayerNorm's
+            # input gradient leaves with the residual gradient already added (csrc/layer_norm.hip)
+            n = _layer_norm(self.norm1, x)
+            x, n = _add_layer_norm(self.norm2, self.attn1(n), x)
+            x, n = _add_layer_norm(self.norm3, self.attn2(n, context), x)
+            return self.ff(n) + x
         x = self.attn1(self.norm1(x)) + x
         x = self.attn2(self.norm2(x), context) + x
         return self.ff(self.norm3(x)) + x

@@ -406,6 +406,27 @@ int group_norm_act_bwd(const void* dy, const void* x, const void* addend /* null
                        int HW, int groups, int act, int channels_last, int dtype, void* stream);
 
 /*
+ * LayerNorm of the transformer blocks with the residual add in front of it folded in (csrc/layer_norm.hip), over rows [M, C]
+ * with the last dimension contiguous; the caller's `attn(norm(x)) + x` chain, one launch each way:
+ *     forward : h = x + delta, rounded to the storage type (bit-equal to the stock sum);  y = (h − mean)·rstd·gamma + beta,
+ *               mean and the biased, centred variance of the ROUNDED h in fp32, rstd = rsqrt(var + eps).  Writes h, y and
+ *               mean / rstd [M] fp32.  delta and h are null TOGETHER: then it is a plain LayerNorm of x and no h is written.
+ *     backward: x̂ = (h − mean)·rstd, g = dy·gamma;  dx = rstd·(g − mean_c(g) − x̂·mean_c(g·x̂)) + dh, fp32 up to the one
+ *               rounding of dx.  `h` is the forward's h (x itself where there was no delta); dh, the gradient that reaches h
+ *               along the residual path, is nullable.  dx is the gradient of x and of delta alike.  No gamma / beta gradients.
+ * Any M >= 1; C % 8 == 0, 8 <= C <= add_layer_norm_max_channels() (2048); dtype f16 / bf16 only (LORA_E_UNSUPPORTED for f32
+ * and for other C: the caller keeps the stock composite).  Every tensor pointer 16-byte aligned, gamma / beta [C] of the same
+ * dtype included.  One wave per row, reductions inside the wave in a fixed order, no atomics, no workspace: results are
+ * bit-reproducible.  The shape is judged before the pointers' alignment, and everything is refused before any launch.
+ */
+int add_layer_norm_max_channels(void);
+int add_layer_norm_fwd(const void* x, const void* delta /* nullable */, const void* gamma, const void* beta,
+                       void* h /* null iff delta is null */, void* y, float* mean, float* rstd, int64_t M, int C, float eps,
+                       int dtype, void* stream);
+int add_layer_norm_bwd(const void* dy, const void* dh /* nullable */, const void* h, const void* gamma, const float* mean,
+                       const float* rstd, void* dx, int64_t M, int C, int dtype, void* stream);
+
+/*
  * Token-embedding rows for a text encoder whose INPUT EMBEDDINGS train next to the UNet's LoRA factors: the tuning phase of
  * lora_diffusion/cli_lora_pti.py with continue_inversion (default, :528) puts `text_encoder.get_input_embeddings().parameters()`
  * in the optimizer (:706-722) and runs `text_encoder(batch["input_ids"])[0]` inside loss_step (:199-206) — BASELINE config 5,

@@ -21,7 +21,7 @@ import sys
 
 
 def short(name):
-    m = re.search(r"(lora_\w+kernel|attn_\w+kernel|ddpm_mse_kernel|add_noise_kernel|noise_prologue_kernel|reduce_partials_kernel|pack_factors\w*|grad_sqnorm_kernel|adamw_kernel)", name)
+    m = re.search(r"(lora_\w+kernel|attn_\w+kernel|add_layer_norm_\w+kernel|ddpm_mse_kernel|add_noise_kernel|noise_prologue_kernel|reduce_partials_kernel|pack_factors\w*|grad_sqnorm_kernel|adamw_kernel)", name)
     if not m:
         return name[:80]
     t = re.search(r"I(DF16_|DF16b|f)(?:Li(\d+)E)?(?:Li(\d+)E)?(?:Lb(\d)E)?(?:Lb(\d)E)?", name)
