@@ -108,6 +108,10 @@ SIGNATURES = {
     "attn_flash_fwd_strided": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "attn_flash_bwd_strided": (_i32, [_vp] * 10 + [_i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "attn_ctx_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "attn_causal_supported": (_i32, [_i32, _i32, _i32, _i32, _i32]),
+    "attn_causal_fwd_strided": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "attn_causal_bwd_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "attn_causal_bwd_strided": (_i32, [_vp] * 8 + [_i64, _i64, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "attn_flash_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "attn_flash_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "attn_flash_bwd_workspace_bytes": (_i64, [_i32, _i32, _i32]),
@@ -931,6 +935,78 @@ def attn_ctx_bwd_kv(q, kv, dkv, off_k: int, off_v: int, dout, heads: int, scale:
                                       dkv.shape[-1], B, Tq, Tk, heads, d, float(scale), dtype_code(q.dtype), _stream(q)),
            "attn_ctx_bwd_strided")
     return dq
+
+
+def attn_causal_supported(B: int, T: int, H: int, d: int, dtype) -> bool:
+    key = (2, B, T, H, d, dtype)
+    ok = _attn_supported.get(key)
+    if ok is None:
+        ok = _attn_supported[key] = (dtype in (torch.float16, torch.bfloat16) and
+                                     bool(lib().attn_causal_supported(B, T, H, d, dtype_code(dtype))))
+    return ok
+
+
+def shared_row_stride(*tensors):
+    """The one row stride (elements) of [B, T, W] tensors that are dense or column slices of row-major [B·T, ld] buffers —
+    unit stride along W, batches T rows apart — or None when they have no such common stride.  The strides of size-1
+    dimensions say nothing (PyTorch leaves them arbitrary): with T == 1 the batch stride is the row stride, with B == 1 and
+    T == 1 any stride ≥ W serves."""
+    ld = None
+    for t in tensors:
+        if t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1):
+            return None
+        B, T, W = t.shape
+        if T > 1:
+            mine = t.stride(1)
+            if B > 1 and t.stride(0) != T * mine:
+                return None
+        elif B > 1:
+            mine = t.stride(0)
+        else:
+            continue
+        if mine < W or (ld is not None and mine != ld):
+            return None
+        ld = mine
+    return tensors[0].shape[2] if ld is None else ld
+
+
+def attn_causal_fwd(q, k, v, heads: int, scale: float):
+    """Causal self-attention: q, k, v [B,T,H·d] with one row stride (dense, or the column slices of one [B·T, 3·H·d]
+    buffer) → softmax(mask(q·kᵀ·scale))·v per head, [B,T,H·d] dense."""
+    _require_device(q, k, v)
+    B, T, HD = q.shape
+    ld = shared_row_stride(q, k, v)
+    if ld is None:
+        raise RuntimeError("attn_causal_fwd: q, k, v must share one row stride")
+    out = torch.empty((B, T, HD), dtype=q.dtype, device=q.device)
+    _check(lib().attn_causal_fwd_strided(_ptr(q), _ptr(k), _ptr(v), _ptr(out), ld, B, T, heads, HD // heads, float(scale),
+                                         dtype_code(q.dtype), _stream(q)), "attn_causal_fwd_strided")
+    return out
+
+
+def attn_causal_bwd(q, k, v, dout, heads: int, scale: float, out=None):
+    """→ (dq, dk, dv) [B,T,H·d]: new dense tensors, or `out` — three tensors with one row stride of their own (the column
+    slices of one gradient buffer), written in place.  dout dense."""
+    _require_device(q, k, v, dout)
+    B, T, HD = q.shape
+    d = HD // heads
+    ld = shared_row_stride(q, k, v)
+    if ld is None:
+        raise RuntimeError("attn_causal_bwd: q, k, v must share one row stride")
+    nbytes = lib().attn_causal_bwd_workspace_bytes(B, T, heads, d)
+    if nbytes < 0:
+        raise RuntimeError("attn_causal_bwd: unsupported shape")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
+    if out is None:
+        out = tuple(torch.empty((B, T, HD), dtype=q.dtype, device=q.device) for _ in range(3))
+    dq, dk, dv = out
+    ld_dq = shared_row_stride(dq, dk, dv)
+    if ld_dq is None or any(t.shape != q.shape or t.dtype != q.dtype for t in out):
+        raise RuntimeError("attn_causal_bwd: dq, dk, dv must be [B,T,H·d] tensors of q's dtype sharing one row stride")
+    _check(lib().attn_causal_bwd_strided(_ptr(q), _ptr(k), _ptr(v), _ptr(dout), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), ld,
+                                         ld_dq, B, T, heads, d, float(scale), dtype_code(q.dtype), _stream(q)),
+           "attn_causal_bwd_strided")
+    return dq, dk, dv
 
 
 def attn_flash_fwd_qkv(qkv, heads: int, scale: float, want_lse: bool = True):

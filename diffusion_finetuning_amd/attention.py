@@ -14,8 +14,19 @@ else.
 Attention modules are recognised structurally, like the reference recognises LoRA targets by class name
 (lora.py:78-114): class name "CrossAttention" or "Attention" with `heads`, `to_q`, `to_k`, `to_v` and a `to_out`
 sequence — the layout of diffusers' class in every version the reference supports, and of the build's harness UNet.
+
+The same switch covers the text encoder: transformers' `CLIPAttention` (the text encoder's LoRA target class, lora.py:54 —
+`q_proj`, `k_proj`, `v_proj`, `out_proj`, `num_heads`) gets a forward that runs its causal softmax core through
+csrc/attn_causal.hip on the [B, T, H·d] tensors the three projections produce (`sandwich.causal_attention`), in place of
+three view/transpose re-layouts, an SDPA call and a `reshape().contiguous()` per layer and direction.  It takes the HIP
+path for exactly the call the text tower makes — `is_causal=True`, no mask tensor, f16/bf16 on the device, no active
+attention dropout, at most 128 tokens, heads of at most 96 — and hands every other call (a padding mask, the `eager`
+implementation's 4-D mask, the vision tower's `is_causal=False`, fp32, CPU, the older `causal_attention_mask=` signature)
+back to the module's own forward.  Opt-in like the UNet's: flip it on the text encoder before building a LoraTrainer.
 """
 import functools
+import logging
+
 import torch
 from torch import nn
 
@@ -23,7 +34,7 @@ from . import _native as nat
 from ._fastattr import factor_weights, linear_params
 from .groups import ctx_cross_attention, qkv_self_attention
 from .ops import feed_forward_geglu, lora_tail
-from .sandwich import ctx_attention, flash_attention
+from .sandwich import causal_attention, ctx_attention, flash_attention
 
 ATTENTION_CLASS_NAMES = {"CrossAttention", "Attention"}
 _ORIG = "_dfa_original_forward"
@@ -107,6 +118,61 @@ def _hip_forward(self, hidden_states, *args, **kwargs):
     return out
 
 
+def _is_clip_attention_module(m: nn.Module) -> bool:
+    return (m.__class__.__name__ == "CLIPAttention"
+            and all(hasattr(m, a) for a in ("q_proj", "k_proj", "v_proj", "out_proj", "num_heads")))
+
+
+_CLIP_KWARGS = ("hidden_states", "attention_mask", "is_causal", "output_attentions")
+_CLIP_LOGGED = set()  # hand-back reasons already logged
+_LOG = logging.getLogger(__name__)
+
+
+def _clip_hand_back_reason(self, args, kwargs, h):
+    """None when the call is the one the causal core covers, else why it goes back to the module's own forward."""
+    if len(args) + ("hidden_states" in kwargs) != 1 or not torch.is_tensor(h):
+        return "positional arguments beyond hidden_states"
+    unknown = [k for k in kwargs if k not in _CLIP_KWARGS]
+    if unknown:
+        return f"keyword arguments {unknown}"
+    if kwargs.get("is_causal") is not True:
+        return "is_causal is not True"
+    if kwargs.get("attention_mask") is not None:
+        return "an attention_mask tensor"
+    if kwargs.get("output_attentions"):
+        return "output_attentions"
+    if not h.is_cuda or h.dim() != 3:
+        return "not a 3-D tensor on the HIP device"
+    if self.training and self.dropout:
+        return "active attention dropout"
+    heads = int(self.num_heads)
+    width = _out_features(self.q_proj)
+    cdtype = _compute_dtype(h)
+    if width % heads or not nat.attn_causal_supported(h.shape[0], h.shape[1], heads, width // heads, cdtype):
+        return f"shape {tuple(h.shape)}, {heads} heads, {cdtype} outside the causal core's envelope"
+    return None
+
+
+def _hip_clip_forward(self, *args, **kwargs):
+    """Replacement forward of transformers' CLIPAttention, for the calling convention of its encoder layer — all keywords:
+    `hidden_states=…, attention_mask=None, is_causal=True` — returning `(attn_output, None)`.  The q/k/v projections are
+    called as modules on the same tensor, so under a trainer with groups they stay ONE grouped launch
+    (groups.shared_projection) and the core works on the three column slices of its output.  A call outside the envelope
+    goes to the module's own forward; the first reason of each kind is logged at DEBUG level, so a fall-back nobody asked
+    for (a transformers version that passes a new keyword, say) can be found."""
+    h = args[0] if args else kwargs.get("hidden_states")
+    why = _clip_hand_back_reason(self, args, kwargs, h)
+    if why is not None:
+        if why not in _CLIP_LOGGED:
+            _CLIP_LOGGED.add(why)
+            _LOG.debug("CLIPAttention: handed back to the module's own forward (%s)", why)
+        return self.__dict__[_ORIG](*args, **kwargs)
+    q, k, v = self.q_proj(h), self.k_proj(h), self.v_proj(h)
+    if q.dtype != k.dtype or q.dtype != v.dtype:  # mixed module dtypes outside autocast: compute in the query's dtype
+        k, v = k.to(q.dtype), v.to(q.dtype)
+    return self.out_proj(causal_attention(q, k, v, int(self.num_heads), float(self.scale))), None
+
+
 def _attach_dropin_groups(module: nn.Module, valid: bool) -> None:
     """Grouped LoRA projections for a model that is NOT under a trainer.LoraSlab — what an unchanged reference trainer gets
     from flipping its one switch (train_lora_dreambooth.py:623-625): to_q/to_k/to_v of every self-attention as one launch each
@@ -166,20 +232,22 @@ def _attach_dropin_groups(module: nn.Module, valid: bool) -> None:
 
 
 def set_use_hip_attention(module: nn.Module, valid: bool = True) -> int:
-    """Install (valid=True) or remove (valid=False) the HIP short-context attention forward on every attention module
-    under `module`.  Returns the number of modules touched.  Idempotent."""
+    """Install (valid=True) or remove (valid=False) the HIP attention forward on every attention module under `module` — the
+    UNet's CrossAttention / Attention and the text encoder's CLIPAttention.  Returns the number of modules touched.
+    Idempotent."""
     import os
 
     if os.environ.get("DFA_DROPIN_GROUPS", "1") != "0":
         _attach_dropin_groups(module, bool(valid))
     touched = 0
     for m in module.modules():
-        if not _is_attention_module(m):
+        clip = _is_clip_attention_module(m)
+        if not clip and not _is_attention_module(m):
             continue
         has = _ORIG in m.__dict__
         if valid and not has:
             m.__dict__[_ORIG] = m.forward  # the bound method (class forward, or whatever was installed before)
-            m.forward = functools.partial(_hip_forward, m)
+            m.forward = functools.partial(_hip_clip_forward if clip else _hip_forward, m)
             touched += 1
         elif not valid and has:
             orig = m.__dict__.pop(_ORIG)

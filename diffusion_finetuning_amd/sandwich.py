@@ -1,5 +1,5 @@
 """Autograd fronts of the ops sandwiched by the hot path in a transformer block: the GEGLU gate, the
-short-context (cross-) and long-context (self-) attention cores, and the head split/merge for callers that keep their
+short-context (cross-), causal short-context (text encoder) and long-context (self-) attention cores, and the head split/merge for callers that keep their
 own attention kernel.
 HIP device only, like the rest of the path."""
 import torch
@@ -101,6 +101,48 @@ def ctx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
     if scale is None:
         scale = (q.shape[-1] // heads) ** -0.5
     return _CtxAttentionFn.apply(q, k, v, heads, float(scale))
+
+
+class _CausalAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, heads, scale):
+        # column slices of ONE row-major buffer (groups.shared_projection / _SplitQKVFn hand those out) go in as they are
+        if nat.shared_row_stride(q, k, v) is None:
+            q, k, v = (t if t.is_contiguous() else t.contiguous() for t in (q, k, v))
+        ctx.save_for_backward(q, k, v)
+        ctx.heads, ctx.scale = heads, scale
+        return nat.attn_causal_fwd(q, k, v, heads, scale)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        q, k, v = ctx.saved_tensors
+        dq, dk, dv = nat.attn_causal_bwd(q, k, v, dout if dout.is_contiguous() else dout.contiguous(), ctx.heads,
+                                         ctx.scale)
+        return dq, dk, dv, None, None
+
+
+def causal_attention_supported(q: torch.Tensor, heads: int) -> bool:
+    """True when `causal_attention` handles this tensor (f16/bf16 on the HIP device, ≤ 128 tokens, head dim ≤ 96)."""
+    if not q.is_cuda or q.dim() != 3 or q.shape[-1] % heads:
+        return False
+    return nat.attn_causal_supported(q.shape[0], q.shape[1], heads, q.shape[-1] // heads, q.dtype)
+
+
+def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float = None) -> torch.Tensor:
+    """Causal self-attention softmax(mask(q·kᵀ·scale))·v per head, mask = −inf for key j > query i, over at most 128
+    tokens.  q, k, v [B,T,H·d] → [B,T,H·d]: the layouts transformers' CLIPAttention q_proj/k_proj/v_proj produce and
+    out_proj consumes, no head split/merge and no [T,T] matrix."""
+    if not q.is_cuda:
+        raise RuntimeError("causal_attention runs only on a HIP device; there is no CPU fallback")
+    if q.shape != k.shape or q.shape != v.shape or q.dtype != k.dtype or q.dtype != v.dtype:
+        raise RuntimeError("causal_attention: q, k, v must have one shape and dtype (self-attention)")
+    if not causal_attention_supported(q, heads):
+        raise RuntimeError(f"causal_attention: unsupported shape or dtype {tuple(q.shape)}, {heads} heads, {q.dtype} "
+                           "(f16/bf16, at most 128 tokens, head dim a multiple of 8 up to 96)")
+    if scale is None:
+        scale = (q.shape[-1] // heads) ** -0.5
+    return _CausalAttentionFn.apply(q, k, v, heads, float(scale))
 
 
 class _FlashAttentionFn(torch.autograd.Function):

@@ -239,8 +239,10 @@ class LoraSlab:
                     m.__dict__["_dfa_qkv"] = grp
                     self.qkv_groups.append(grp)
             # transformers' CLIPAttention (LoRA target class of the text encoder, lora.py:54): q_proj / k_proj / v_proj multiply
-            # the same hidden states and are called one after the other by a forward this package does not replace — the
-            # members share one launch through groups.shared_projection (biases ride along; 3·r ≤ 16 rank slots)
+            # the same hidden states and are called one after the other, as modules — by transformers' own forward, or by the
+            # one attention.set_use_hip_attention installs when the user flips it on the text encoder (the causal core of
+            # csrc/attn_causal.hip then reads the three column slices in place) — the members share one launch through
+            # groups.shared_projection (biases ride along; 3·r ≤ 16 rank slots)
             for name, m in model.named_modules():
                 if m.__class__.__name__ != "CLIPAttention" or not all(hasattr(m, a) for a in ("q_proj", "k_proj", "v_proj")):
                     continue

@@ -496,6 +496,28 @@ int attn_ctx_bwd(const void* Q, const void* K, const void* V, const void* dO, vo
                  void* workspace, int B, int Tq, int Tk, int H, int d, float scale, int dtype, void* stream);
 
 /*
+ * Causal short-context attention core  O = softmax(mask(Q·Kᵀ·scale))·V  per head, mask(i, j) = −inf for j > i, self-attention
+ * over T <= 128 tokens: the text encoder's attention between the q_proj/k_proj/v_proj and out_proj LoRA linears (transformers
+ * CLIPAttention.forward, the caller of the layers wrapped per lora_diffusion/lora.py:54; 77 tokens, heads of 64).  The
+ * structure of attn_ctx_* with the triangle used: key fragments above a query block's diagonal are skipped, the diagonal
+ * fragment's mask is the initial accumulator of its scores; masked probabilities are exact zeros.  Tensors are [B, T, H·d]:
+ * Q, K, V with one row stride ldq (elements; H·d when dense, 3·H·d for the column slices of a grouped q/k/v projection's
+ * output), dQ, dK, dV with one row stride ld_dq, O and dO dense.  No head split/merge copies, no [T, T] matrix in memory.
+ *   attn_causal_supported          : 1 when (shape, dtype) runs here: f16/bf16, d % 8 == 0, d <= 96, 1 <= T <= 128.
+ *   attn_causal_fwd_strided        : O.  Nothing else is saved: backward recomputes the single key tile.
+ *   attn_causal_bwd_workspace_bytes: size of the fp32 partial-sum workspace for dK/dV (-1 when unsupported).
+ *   attn_causal_bwd_strided        : dQ, dK, dV from Q, K, V, dO.  Deterministic (ordered partial sums, no atomics).
+ * Unsupported shapes return LORA_E_BADARG.  Nothing is allocated or retained; all work goes on `stream` (capturable).
+ */
+int attn_causal_supported(int B, int T, int H, int d, int dtype);
+int attn_causal_fwd_strided(const void* Q, const void* K, const void* V, void* O, int64_t ldq, int B, int T, int H, int d,
+                            float scale, int dtype, void* stream);
+int64_t attn_causal_bwd_workspace_bytes(int B, int T, int H, int d);
+int attn_causal_bwd_strided(const void* Q, const void* K, const void* V, const void* dO, void* dQ, void* dK, void* dV,
+                            void* workspace, int64_t ldq, int64_t ld_dq, int B, int T, int H, int d, float scale,
+                            int dtype, void* stream);
+
+/*
  * Long-context attention core (self-attention: thousands of keys), same tensor layouts as attn_ctx_*: flash-style
  * online softmax over 64-key tiles, no [Tq, Tk] matrix in memory.
  *   attn_flash_supported          : 1 for f16/bf16, d % 8 == 0, d <= 160.
