@@ -116,6 +116,10 @@ SIGNATURES = {
     "attn_flash_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "attn_flash_bwd_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "attn_flash_bwd": (_i32, [_vp] * 10 + [_i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "attn_f32_supported": (_i32, [_i32, _i32, _i32, _i32, _i32]),
+    "attn_f32_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "attn_f32_bwd_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "attn_f32_bwd": (_i32, [_vp] * 10 + [_i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "lora_distill_workspace_bytes": (_i64, [_i64, _i64]),
     "lora_distill_start": (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _vp]),
     "lora_distill_diff": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp]),
@@ -1070,6 +1074,48 @@ def attn_flash_bwd(q, k, v, out, dout, lse, heads: int, scale: float):
     _check(lib().attn_flash_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dq), _ptr(dk),
                                 _ptr(dv), _ptr(ws), B, Tq, Tk, heads, HD // heads, float(scale), dtype_code(q.dtype),
                                 _stream(q)), "attn_flash_bwd")
+    return dq, dk, dv
+
+
+def attn_f32_supported(B: int, Tq: int, Tk: int, H: int, d: int) -> bool:
+    key = (3, B, Tq, Tk, H, d)
+    ok = _attn_supported.get(key)
+    if ok is None:
+        ok = _attn_supported[key] = bool(lib().attn_f32_supported(B, Tq, Tk, H, d))
+    return ok
+
+
+def _require_f32_dense(name: str, *tensors) -> None:
+    for t in tensors:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"{name}: operands must be contiguous float32 tensors (got {t.dtype}, strides {t.stride()})")
+
+
+def attn_f32_fwd(q, k, v, heads: int, scale: float, want_lse: bool = True):
+    """fp32 q [B,Tq,H·d], k/v [B,Tk,H·d] contiguous → (o [B,Tq,H·d], lse [B,H,Tq] | None)  (csrc/attn_f32.hip)."""
+    _require_device(q, k, v)
+    _require_f32_dense("attn_f32_fwd", q, k, v)
+    B, Tq, HD = q.shape
+    Tk = k.shape[1]
+    if HD % heads or k.shape != (B, Tk, HD) or v.shape != k.shape:
+        raise RuntimeError(f"attn_f32_fwd: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)} with {heads} heads")
+    out = torch.empty_like(q)
+    lse = torch.empty((B, heads, Tq), dtype=torch.float32, device=q.device) if want_lse else None
+    _check(lib().attn_f32_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, Tq, Tk, heads, HD // heads, float(scale),
+                              _stream(q)), "attn_f32_fwd")
+    return out, lse
+
+
+def attn_f32_bwd(q, k, v, out, dout, lse, heads: int, scale: float):
+    """→ (dq, dk, dv), same layouts as the inputs."""
+    _require_device(q, k, v, out, dout, lse)
+    _require_f32_dense("attn_f32_bwd", q, k, v, out, dout, lse)
+    B, Tq, HD = q.shape
+    Tk = k.shape[1]
+    ws = torch.empty(lib().attn_f32_bwd_workspace_bytes(B, Tq, heads) // 4, dtype=torch.float32, device=q.device)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    _check(lib().attn_f32_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dq), _ptr(dk), _ptr(dv),
+                              _ptr(ws), B, Tq, Tk, heads, HD // heads, float(scale), _stream(q)), "attn_f32_bwd")
     return dq, dk, dv
 
 

@@ -7,9 +7,11 @@ with the same signature.  Instead of xformers it installs, on every attention mo
 runs `softmax(QKᵀ·scale)V` through the HIP attention cores — csrc/attn_ctx.hip for a short key/value sequence (the
 cross-attention over the text tokens), csrc/attn_flash.hip for a long one (self-attention over thousands of tokens) —
 directly on the [B, T, H·d] tensors its `to_q/to_k/to_v` linears (the LoRA targets, lora_diffusion/lora.py:53)
-produce.  Everything the kernels do not cover (fp32 tensors, head dims above 160, masks, CPU tensors, exotic module
-options) is handed back, untouched, to the module's own forward: the product implements what it accelerates and nothing
-else.
+produce.  Everything the kernels do not cover (fp32 tensors unless the fp32 core is switched on, head dims above 160,
+masks, CPU tensors, exotic module options) is handed back, untouched, to the module's own forward: the product implements
+what it accelerates and nothing else.  `set_use_hip_attention(module, True, fp32=True)` adds the fp32 core
+(csrc/attn_f32.hip, `sandwich.f32_attention`) for the routes the reference runs in fp32 — PTI's textual-inversion phase
+(cli_lora_pti.py:685, mixed_precision=False) — on the plain to_q/to_k/to_v path.
 
 Attention modules are recognised structurally, like the reference recognises LoRA targets by class name
 (lora.py:78-114): class name "CrossAttention" or "Attention" with `heads`, `to_q`, `to_k`, `to_v` and a `to_out`
@@ -34,10 +36,11 @@ from . import _native as nat
 from ._fastattr import factor_weights, linear_params
 from .groups import ctx_cross_attention, qkv_self_attention
 from .ops import feed_forward_geglu, lora_tail
-from .sandwich import causal_attention, ctx_attention, flash_attention
+from .sandwich import causal_attention, ctx_attention, f32_attention, flash_attention
 
 ATTENTION_CLASS_NAMES = {"CrossAttention", "Attention"}
 _ORIG = "_dfa_original_forward"
+_FP32 = "_dfa_fp32_attention"  # set on a module by set_use_hip_attention(..., fp32=True)
 
 
 def _is_attention_module(m: nn.Module) -> bool:
@@ -85,6 +88,20 @@ def _hip_forward(self, hidden_states, *args, **kwargs):
             core = ctx_attention
         elif nat.attn_flash_supported(*shape):  # any length: online softmax over key tiles
             core = flash_attention
+        elif (cdtype == torch.float32 and self.__dict__.get(_FP32) and hidden_states.dtype == torch.float32
+              and ctx.dtype == torch.float32 and nat.attn_f32_supported(*shape[:5])):
+            # fp32 compute (PTI's inversion phase, the parity routes), opted in with fp32=True: the fp32 core on the plain
+            # to_q/to_k/to_v path — the LoRA groups are 16-bit and stay out
+            q, k, v = to_q(hidden_states), self.to_k(ctx), self.to_v(ctx)
+            if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
+                return original(hidden_states, *args, **kwargs)  # (projections that change the dtype: not this core's call)
+            scale = getattr(self, "scale", None)
+            out = f32_attention(q, k, v, heads, float(scale) if isinstance(scale, (int, float)) else None)
+            for layer in self.to_out:
+                if type(layer) is nn.Dropout and layer.p == 0.0 and not layer._forward_hooks and not layer._forward_pre_hooks:
+                    continue
+                out = layer(out)
+            return out
     if core is None:
         return original(hidden_states, *args, **kwargs)
     scale = getattr(self, "scale", None)
@@ -231,10 +248,15 @@ def _attach_dropin_groups(module: nn.Module, valid: bool) -> None:
             lambda mod, args, gs=tuple(groups): [g.new_pass() for g in gs] and None)
 
 
-def set_use_hip_attention(module: nn.Module, valid: bool = True) -> int:
+def set_use_hip_attention(module: nn.Module, valid: bool = True, fp32: bool = False) -> int:
     """Install (valid=True) or remove (valid=False) the HIP attention forward on every attention module under `module` — the
     UNet's CrossAttention / Attention and the text encoder's CLIPAttention.  Returns the number of modules touched.
-    Idempotent."""
+    Idempotent.
+
+    fp32=True also sends the UNet modules' fp32 calls (no mask, known signature, on the device, head dim a multiple of 8 up to
+    160) through the fp32 core (sandwich.f32_attention, csrc/attn_f32.hip); with the default an fp32 call is handed back to the
+    module's own forward, as every call outside the 16-bit cores' envelope is.  The flag is per module and follows the last
+    call; valid=False clears it.  The text encoder's causal core has no fp32 form."""
     import os
 
     if os.environ.get("DFA_DROPIN_GROUPS", "1") != "0":
@@ -245,6 +267,10 @@ def set_use_hip_attention(module: nn.Module, valid: bool = True) -> int:
         if not clip and not _is_attention_module(m):
             continue
         has = _ORIG in m.__dict__
+        if valid and fp32 and not clip:
+            m.__dict__[_FP32] = True
+        else:
+            m.__dict__.pop(_FP32, None)
         if valid and not has:
             m.__dict__[_ORIG] = m.forward  # the bound method (class forward, or whatever was installed before)
             m.forward = functools.partial(_hip_clip_forward if clip else _hip_forward, m)

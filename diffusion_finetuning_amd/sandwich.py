@@ -180,3 +180,47 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
     if scale is None:
         scale = (q.shape[-1] // heads) ** -0.5
     return _FlashAttentionFn.apply(q, k, v, heads, float(scale))
+
+
+class _F32AttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, heads, scale):
+        q, k, v = (t if t.is_contiguous() else t.contiguous() for t in (q, k, v))
+        need = any(ctx.needs_input_grad[:3])
+        out, lse = nat.attn_f32_fwd(q, k, v, heads, scale, want_lse=need)
+        if need:
+            ctx.save_for_backward(q, k, v, out, lse)
+        ctx.heads, ctx.scale = heads, scale
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = nat.attn_f32_bwd(q, k, v, out, dout if dout.is_contiguous() else dout.contiguous(), lse, ctx.heads,
+                                      ctx.scale)
+        return dq, dk, dv, None, None
+
+
+def f32_attention_supported(q: torch.Tensor, k: torch.Tensor, heads: int) -> bool:
+    """True when `f32_attention` handles these tensors (fp32 on the HIP device, head dim a multiple of 8 from 8 to 160, any
+    lengths)."""
+    if not q.is_cuda or q.dtype != torch.float32 or k.dtype != torch.float32 or q.dim() != 3 or k.dim() != 3:
+        return False
+    if q.shape[-1] % heads or k.shape[-1] != q.shape[-1] or k.shape[0] != q.shape[0]:
+        return False
+    return nat.attn_f32_supported(q.shape[0], q.shape[1], k.shape[1], heads, q.shape[-1] // heads)
+
+
+def f32_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float = None) -> torch.Tensor:
+    """softmax(q·kᵀ·scale)·v per head on fp32 tensors, key/value sequences of any length (csrc/attn_f32.hip: online softmax
+    over key tiles on the exact f32-input MFMA; nothing of size Tq×Tk is stored).  Same [B,T,H·d] layouts as
+    `flash_attention`; O and the row log-sum-exp are saved only when a gradient is wanted."""
+    if not q.is_cuda:
+        raise RuntimeError("f32_attention runs only on a HIP device; there is no CPU fallback")
+    if not f32_attention_supported(q, k, heads):
+        raise RuntimeError(f"f32_attention: unsupported shape or dtype {tuple(q.shape)} x {tuple(k.shape)}, {heads} heads, "
+                           f"{q.dtype} (fp32, head dim a multiple of 8 from 8 to 160)")
+    if scale is None:
+        scale = (q.shape[-1] // heads) ** -0.5
+    return _F32AttentionFn.apply(q, k, v, heads, float(scale))

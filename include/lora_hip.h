@@ -544,6 +544,29 @@ int attn_flash_bwd(const void* Q, const void* K, const void* V, const void* O, c
                    int dtype, void* stream);
 
 /*
+ * fp32 attention core  O = softmax(Q·Kᵀ·scale)·V  per head on fp32 tensors, any Tq >= 1 and Tk >= 1: the attention of the routes
+ * the reference runs in fp32 — diffusers CrossAttention.forward under cli_lora_pti.py:685 (mixed_precision=False: PTI's
+ * textual-inversion phase) and BASELINE config 1.  Same tensor layouts as attn_flash_* (dense [B, T, H·d], no head split/merge,
+ * no [Tq, Tk] matrix in memory); online softmax over 64-key tiles; every product on the exact f32-input MFMA
+ * (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain, no reduced-precision path), softmax in fp32 with exp2.
+ *   attn_f32_supported          : 1 for d % 8 == 0, 8 <= d <= 160, B, H, Tq, Tk >= 1.
+ *   attn_f32_fwd                : O and LSE [B, H, Tq] = log2-sum-exp2 of the scaled scores (saved for backward; may be NULL
+ *                                 when no backward follows).
+ *   attn_f32_bwd_workspace_bytes: B·H·Tq·4 (the softmax correction Δ = Σ dO·O per query row); -1 for non-positive sizes.
+ *   attn_f32_bwd                : dQ, dK, dV from Q, K, V, O, dO, LSE.  Two launches (query-owned dQ, which also fills the
+ *                                 workspace with Δ; key-owned dK/dV), every output element written by one wave: no atomics,
+ *                                 bit-identical from run to run.
+ * Outside the envelope the entries return LORA_E_BADARG, for an operand off a 16-byte boundary LORA_E_ALIGN.  Nothing is
+ * allocated or retained; all work goes on `stream` (capturable).
+ */
+int attn_f32_supported(int B, int Tq, int Tk, int H, int d);
+int attn_f32_fwd(const float* Q, const float* K, const float* V, float* O, float* LSE, int B, int Tq, int Tk, int H, int d,
+                 float scale, void* stream);
+int64_t attn_f32_bwd_workspace_bytes(int B, int Tq, int H);
+int attn_f32_bwd(const float* Q, const float* K, const float* V, const float* O, const float* dO, const float* LSE, float* dQ,
+                 float* dK, float* dV, float* workspace, int B, int Tq, int Tk, int H, int d, float scale, void* stream);
+
+/*
  * svd_distill — lora_diffusion/cli_svd.py:29-111: a fully fine-tuned model → rank-r LoRA factors, per target linear
  *     D = float(T(W1 − W0))  (:59-69);  U, S, Vh = svd(D);  up = U_r·diag(S_r) [N,r], down = Vh_r [r,K]  (:71-77)
  *     hi = quantile(cat(up, down), q) (linear interpolation);  up, down ← clamp(·, −hi, hi)  (:79-84)

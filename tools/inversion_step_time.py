@@ -8,7 +8,11 @@ Each run: `--warmup` micro-steps, then `--steps` timed ones (whole accumulation 
 optimizer at every 4th).  Peak = torch.cuda.max_memory_allocated() over the run minus what was allocated before it (the models).
 Prints one JSON line.
 
-    python tools/inversion_step_time.py [--steps 16] [--warmup 4]
+`--fp32-attention` flips the UNet's attention onto the fp32 HIP core (attention.set_use_hip_attention(unet, True, fp32=True),
+csrc/attn_f32.hip) before the trainers are built — all three runs then share the switched UNet; `--runs` restricts the runs
+(a kernel trace of one route: `--runs eager`).
+
+    python tools/inversion_step_time.py [--steps 16] [--warmup 4] [--fp32-attention] [--runs eager,recorded,stock]
 """
 import argparse
 import json
@@ -50,18 +54,28 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--fp32-attention", action="store_true", help="run the UNet's fp32 attention on the HIP fp32 core")
+    ap.add_argument("--runs", default="eager,recorded,stock", help="comma-separated subset of eager, recorded, stock")
     args = ap.parse_args()
+    runs = [r for r in args.runs.split(",") if r]
     dev = "cuda"
     unet, te = config5_models(dev)
+    if args.fp32_attention:
+        from diffusion_finetuning_amd.attention import set_use_hip_attention
+
+        set_use_hip_attention(unet, True, fp32=True)
     emb = te.get_input_embeddings()
     init = emb.weight.detach().clone()
     n = args.warmup + args.steps
     batches = config5_batches(n, dev, PLACEHOLDERS)
     acp, s1 = tr.ddpm_tables(device=dev)
     out = {"shape": "config 5: SD2.1-768 UNet, OpenCLIP-H encoder, 49408x1024 table, 96x96 latents, batch 1, fp32",
-           "accum_iter": 4, "warmup": args.warmup, "steps": args.steps, "table_MiB": init.numel() * 4 / 2**20}
+           "accum_iter": 4, "warmup": args.warmup, "steps": args.steps, "table_MiB": init.numel() * 4 / 2**20,
+           "fp32_attention": bool(args.fp32_attention)}
 
     for name, graph in (("eager", False), ("recorded", True)):
+        if name not in runs:
+            continue
         with torch.no_grad():
             emb.weight.copy_(init)
         trainer = InversionTrainer(unet, te, PLACEHOLDERS, capture_graph=graph)
@@ -83,8 +97,9 @@ def main():
     def run_stock(k, on_step):
         reference_inversion(unet, te, PLACEHOLDERS, batches[:k], 5e-4, 0.0, 4, lam, True, False, acp, s1, on_step=on_step)
 
-    ms, peak = timed(run_stock, args.warmup, args.steps)
-    out["stock"] = {"ms_per_micro_step": round(ms, 3), "peak_MiB": round(peak / 2**20, 1)}
+    if "stock" in runs:
+        ms, peak = timed(run_stock, args.warmup, args.steps)
+        out["stock"] = {"ms_per_micro_step": round(ms, 3), "peak_MiB": round(peak / 2**20, 1)}
     print(json.dumps(out))
 
 
