@@ -82,6 +82,9 @@ SIGNATURES = {
     "ddpm_add_noise": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp]),
     "ddpm_noise_prologue": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, ctypes.c_uint64, ctypes.c_uint64,
                                    _i32, _i32, _vp]),
+    "ddpm_posterior_prologue": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32,
+                                       ctypes.c_uint64, ctypes.c_uint64, _i32, _i32, _vp]),
+    "ddpm_posterior_sample": (_i32, [_vp, _i32, _vp, _vp, _i32, _i64, _f32, _vp]),
     "embed_rows_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "embed_rows_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp]),
     "lora_adamw_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
@@ -607,6 +610,47 @@ def ddpm_noise_prologue(x0, sqrt_acp, sqrt_1macp, out_dtype: torch.dtype, seed: 
                                      int(step) & (2**64 - 1), int(v_prediction), dtype_code(out_dtype), _stream(x0)),
            "ddpm_noise_prologue")
     return (noisy, target, t, eps) if want_draw else (noisy, target, t)
+
+
+def _moments_rows(moments):
+    """(B, per_row, latent shape) of VAE moments [B, 2C, ...]: row b = mean [per_row] | logvar [per_row]."""
+    if moments.dim() < 2 or moments.shape[1] % 2 or not moments.is_contiguous():
+        raise ValueError(f"moments must be a contiguous [B, 2C, ...] tensor (mean | logvar); got {tuple(moments.shape)}, "
+                         f"strides {moments.stride()}")
+    shape = (moments.shape[0], moments.shape[1] // 2) + tuple(moments.shape[2:])
+    return moments.shape[0], moments[0].numel() // 2, shape
+
+
+def ddpm_posterior_prologue(moments, sqrt_acp, sqrt_1macp, out_dtype: torch.dtype, seed: int, step: int, v_prediction: bool,
+                            n_timesteps: int = 1000, scale: float = 0.18215, want_draw: bool = False, want_target: bool = True):
+    """Draws the latents from the VAE moments [B, 2C, h, w] (f32 / f16 / bf16), eps and t on the device (Philox keyed by seed,
+    step) in one launch and returns (noisy, target, t[, x0, z, eps]) — include/lora_hip.h: ddpm_posterior_prologue."""
+    _require_device(moments, sqrt_acp, sqrt_1macp)
+    B, per_row, shape = _moments_rows(moments)
+    dev = moments.device
+    noisy = torch.empty(shape, dtype=out_dtype, device=dev)
+    target = torch.empty(shape, dtype=out_dtype, device=dev) if want_target else None
+    t = torch.empty(B, dtype=torch.int64, device=dev)
+    x0, z, eps = (torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3)) if want_draw else (None, None, None)
+    _check(lib().ddpm_posterior_prologue(_ptr(moments), dtype_code(moments.dtype), _ptr(sqrt_acp), _ptr(sqrt_1macp), _ptr(noisy),
+                                         _ptr(target), _ptr(x0), _ptr(z), _ptr(eps), _ptr(t), B, per_row, int(n_timesteps),
+                                         float(scale), int(seed) & (2**64 - 1), int(step) & (2**64 - 1), int(v_prediction),
+                                         dtype_code(out_dtype), _stream(moments)),
+           "ddpm_posterior_prologue")
+    return (noisy, target, t, x0, z, eps) if want_draw else (noisy, target, t)
+
+
+def ddpm_posterior_sample(moments, z, scale: float = 0.18215):
+    """x0 = (mean + exp(0.5·clamp(logvar, −30, 20))·z)·scale, fp32, from the caller's fp32 z (shaped like the latents)."""
+    _require_device(moments, z)
+    B, per_row, shape = _moments_rows(moments)
+    if z.dtype != torch.float32 or tuple(z.shape) != shape or not z.is_contiguous():
+        raise ValueError(f"the posterior noise must be a contiguous fp32 {shape} tensor; got {z.dtype} {tuple(z.shape)}")
+    x0 = torch.empty(shape, dtype=torch.float32, device=moments.device)
+    _check(lib().ddpm_posterior_sample(_ptr(moments), dtype_code(moments.dtype), _ptr(z), _ptr(x0), B, per_row, float(scale),
+                                       _stream(moments)),
+           "ddpm_posterior_sample")
+    return x0
 
 
 def embed_rows_fwd(table, ids, out_dtype: torch.dtype):

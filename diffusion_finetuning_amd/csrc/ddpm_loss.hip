@@ -1,8 +1,9 @@
 // DDPM noise-prediction loss (forward value + gradient in one pass), the PTI mask preparation and
-// the add_noise / target prologue.
+// the add_noise / target prologue, with and without the draw of the latents from the VAE's moments.
 //   loss      : training_scripts/train_lora_dreambooth.py:855-875, lora_diffusion/cli_lora_pti.py:243-247
 //   mask prep : lora_diffusion/cli_lora_pti.py:222-241
 //   prologue  : training_scripts/train_lora_dreambooth.py:824-853 (DDPM add_noise / get_velocity)
+//   posterior : training_scripts/train_lora_dreambooth.py:818-821, lora_diffusion/cli_lora_pti.py:180-184
 // All HBM-bound elementwise/reduction work: 16-byte vector loads, wave-shuffle → LDS → one partial
 // per workgroup, and a deterministic "last workgroup sums the partials in index order" finish
 // (agent-scope release/acquire around an arrival ticket, so the result does not depend on which
@@ -344,6 +345,253 @@ extern "C" int ddpm_noise_prologue(const float* x0, const float* sqrt_acp, const
                                per_row, n_timesteps, sd, st, v_prediction);
             break;
         default: return LORA_E_BADARG;
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same prologue one step earlier: the latents themselves are drawn from the VAE encoder's moments,
+//   x0 = (mean + exp(0.5·clamp(logvar, −30, 20))·z)·scale        (`latent_dist.sample() * 0.18215`,
+//   train_lora_dreambooth.py:818-821, cli_lora_pti.py:180-184; DiagonalGaussianDistribution is diffusers', restated from its
+//   published definition)
+// with z ~ N(0,1) from Philox stream 2 — counter (g, g>>32, 2, 0) — next to eps (stream 0) and t (stream 1), which keep the
+// counters and the arithmetic of noise_prologue_kernel: for equal (seed, step) they come out bit-identical to its draw.
+// One thread per Philox group of 4 consecutive elements.  QUAD: per_row % 4 == 0 and every pointer aligned to its 4-element
+// access, so a group lies inside one row and mean / logvar / every output move as one 16-byte (fp32) or 8-byte (16-bit)
+// access; otherwise element by element, a group may straddle rows and the last one may be ragged.
+namespace {
+
+template <typename T> struct alignas(4 * sizeof(T)) Quad {
+    T v[4];
+};
+
+__device__ __forceinline__ void philox_normals4(uint64_t g, uint32_t stream, uint32_t seed, uint32_t step, float z[4]) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), stream, 0u, seed, step, r);
+    const float r0 = sqrtf(-2.f * logf(u01(r[0]))), r1 = sqrtf(-2.f * logf(u01(r[2])));
+    float s0, c0, s1, c1;
+    sincosf(6.283185307179586f * u01(r[1]), &s0, &c0);
+    sincosf(6.283185307179586f * u01(r[3]), &s1, &c1);
+    z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
+}
+
+__device__ __forceinline__ int64_t philox_timestep(uint32_t b, uint32_t seed, uint32_t step, int n_timesteps) {
+    uint32_t tr[4];
+    philox4x32_10(b, 0u, 1u, 0u, seed, step, tr);
+    return (int64_t)(((uint64_t)tr[0] * (uint64_t)n_timesteps) >> 32);
+}
+
+// torch.clamp's semantics (a NaN stays a NaN), then diffusers' std = exp(0.5·logvar)
+__device__ __forceinline__ float posterior_x0(float mean, float logvar, float z, float scale) {
+    const float lv = logvar < -30.f ? -30.f : (logvar > 20.f ? 20.f : logvar);
+    return fmaf(expf(0.5f * lv), z, mean) * scale;
+}
+
+// noisy and target with every product rounded on its own — what add_noise_kernel and noise_prologue_kernel compile to — and
+// said so here, where the compiler would otherwise fuse them: a step fed with moments then leaves the very bits of the step
+// fed with this launch's x0_out / eps_out / t_out.
+__device__ __forceinline__ float ddpm_noisy(float a, float s, float x, float e) {
+#pragma clang fp contract(off)
+    const float ax = a * x, se = s * e;
+    return ax + se;
+}
+__device__ __forceinline__ float ddpm_target(float a, float s, float x, float e, int v_pred) {
+#pragma clang fp contract(off)
+    const float ae = a * e, sx = s * x;
+    return v_pred ? ae - sx : e;
+}
+
+struct PosteriorParams {
+    const void* moments;  // [B, 2·per_row]: row b = mean | logvar
+    const float* sa;
+    const float* sb;
+    void* noisy;
+    void* target;   // nullable
+    float* x0_out;  // nullable, like z_out / eps_out / t_out
+    float* z_out;
+    float* eps_out;
+    int64_t* t_out;
+    int64_t per_row;
+    int64_t n_total;  // B · per_row
+    int n_timesteps;
+    uint32_t seed, step;
+    float scale;
+    int v_pred;
+};
+
+template <typename TM, typename TO, bool QUAD>
+__global__ __launch_bounds__(256) void posterior_prologue_kernel(PosteriorParams p) {
+    const TM* moments = static_cast<const TM*>(p.moments);
+    TO* noisy = static_cast<TO*>(p.noisy);
+    TO* target = static_cast<TO*>(p.target);
+    const int64_t groups = (p.n_total + 3) >> 2;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+        Quad<float> eps_q, z_q;
+        philox_normals4((uint64_t)g, 0u, p.seed, p.step, eps_q.v);
+        philox_normals4((uint64_t)g, 2u, p.seed, p.step, z_q.v);
+        const float* eps = eps_q.v;
+        const float* z = z_q.v;
+        const int64_t i0 = g * 4;
+        int64_t b = i0 / p.per_row;  // row of the group's first element (B is an int: b fits 32 bits)
+        // The timestep is a property of the row.  All 64 groups of a wave mostly lie in one row: its Philox call then has
+        // wave-uniform inputs and runs once per wave on the scalar unit; only the lanes of a wave that straddles a row
+        // boundary make a call of their own.
+        const uint32_t b_wave = __builtin_amdgcn_readfirstlane((uint32_t)b);
+        int64_t ti = philox_timestep(b_wave, p.seed, p.step, p.n_timesteps);
+        if ((uint32_t)b != b_wave) ti = philox_timestep((uint32_t)b, p.seed, p.step, p.n_timesteps);
+        if constexpr (QUAD) {
+            const int64_t col = i0 - b * p.per_row;
+            const TM* row = moments + b * 2 * p.per_row + col;
+            const Quad<TM> mean = *reinterpret_cast<const Quad<TM>*>(row);
+            const Quad<TM> logvar = *reinterpret_cast<const Quad<TM>*>(row + p.per_row);
+            if (col == 0 && p.t_out) p.t_out[b] = ti;
+            const float a = p.sa[ti], s = p.sb[ti];
+            Quad<float> x;
+            Quad<TO> nv, tv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                x.v[e] = posterior_x0(to_f32<TM>(mean.v[e]), to_f32<TM>(logvar.v[e]), z[e], p.scale);
+                nv.v[e] = from_f32<TO>(ddpm_noisy(a, s, x.v[e], eps[e]));
+                tv.v[e] = from_f32<TO>(ddpm_target(a, s, x.v[e], eps[e], p.v_pred));
+            }
+            *reinterpret_cast<Quad<TO>*>(noisy + i0) = nv;
+            if (target) *reinterpret_cast<Quad<TO>*>(target + i0) = tv;
+            if (p.x0_out) *reinterpret_cast<Quad<float>*>(p.x0_out + i0) = x;
+            if (p.z_out) *reinterpret_cast<Quad<float>*>(p.z_out + i0) = z_q;
+            if (p.eps_out) *reinterpret_cast<Quad<float>*>(p.eps_out + i0) = eps_q;
+        } else {
+            int64_t row_end = (b + 1) * p.per_row;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = i0 + e;
+                if (i >= p.n_total) break;
+                if (i >= row_end) {  // the group runs on into the next row(s): per_row may be below 4
+                    b = i / p.per_row;
+                    row_end = (b + 1) * p.per_row;
+                    ti = philox_timestep((uint32_t)b, p.seed, p.step, p.n_timesteps);
+                }
+                const int64_t col = i - b * p.per_row;
+                if (col == 0 && p.t_out) p.t_out[b] = ti;
+                const float a = p.sa[ti], s = p.sb[ti];
+                const TM* row = moments + b * 2 * p.per_row + col;
+                const float x = posterior_x0(to_f32<TM>(row[0]), to_f32<TM>(row[p.per_row]), z[e], p.scale);
+                noisy[i] = from_f32<TO>(ddpm_noisy(a, s, x, eps[e]));
+                if (target) target[i] = from_f32<TO>(ddpm_target(a, s, x, eps[e], p.v_pred));
+                if (p.x0_out) p.x0_out[i] = x;
+                if (p.z_out) p.z_out[i] = z[e];
+                if (p.eps_out) p.eps_out[i] = eps[e];
+            }
+        }
+    }
+}
+
+template <typename TM, bool QUAD>
+__global__ __launch_bounds__(256) void posterior_sample_kernel(const TM* moments, const float* z, float* x0, int64_t per_row,
+                                                               int64_t n_total, float scale) {
+    const int64_t groups = (n_total + 3) >> 2;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+        const int64_t i0 = g * 4;
+        if constexpr (QUAD) {
+            const int64_t b = i0 / per_row;
+            const TM* row = moments + b * 2 * per_row + (i0 - b * per_row);
+            const Quad<TM> mean = *reinterpret_cast<const Quad<TM>*>(row);
+            const Quad<TM> logvar = *reinterpret_cast<const Quad<TM>*>(row + per_row);
+            const Quad<float> zv = *reinterpret_cast<const Quad<float>*>(z + i0);
+            Quad<float> x;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                x.v[e] = posterior_x0(to_f32<TM>(mean.v[e]), to_f32<TM>(logvar.v[e]), zv.v[e], scale);
+            *reinterpret_cast<Quad<float>*>(x0 + i0) = x;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = i0 + e;
+                if (i >= n_total) break;
+                const int64_t b = i / per_row;
+                const TM* row = moments + b * 2 * per_row + (i - b * per_row);
+                x0[i] = posterior_x0(to_f32<TM>(row[0]), to_f32<TM>(row[per_row]), z[i], scale);
+            }
+        }
+    }
+}
+
+template <typename T> bool quad_aligned(const void* p) {  // null: nothing to access
+    return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(T) - 1)) == 0;
+}
+
+unsigned posterior_blocks(int64_t n_total) {
+    int64_t blocks = ((n_total + 3) / 4 + 255) / 256;
+    return (unsigned)(blocks > 2048 ? 2048 : blocks);
+}
+
+template <typename TM, typename TO>
+void launch_posterior_prologue(const PosteriorParams& p, hipStream_t s) {
+    const bool quad = (p.per_row % 4) == 0 && quad_aligned<TM>(p.moments) && quad_aligned<TO>(p.noisy) &&
+                      quad_aligned<TO>(p.target) && quad_aligned<float>(p.x0_out) && quad_aligned<float>(p.z_out) &&
+                      quad_aligned<float>(p.eps_out);
+    const dim3 grid(posterior_blocks(p.n_total));
+    if (quad)
+        hipLaunchKernelGGL((posterior_prologue_kernel<TM, TO, true>), grid, dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL((posterior_prologue_kernel<TM, TO, false>), grid, dim3(256), 0, s, p);
+}
+
+template <typename TM>
+void launch_posterior_prologue_out(const PosteriorParams& p, int dtype, hipStream_t s) {
+    switch (dtype) {
+        case LORA_F32: launch_posterior_prologue<TM, float>(p, s); break;
+        case LORA_F16: launch_posterior_prologue<TM, half_t>(p, s); break;
+        default: launch_posterior_prologue<TM, bf16_t>(p, s); break;
+    }
+}
+
+template <typename TM>
+void launch_posterior_sample(const void* moments, const float* z, float* x0, int64_t per_row, int64_t n_total, float scale,
+                             hipStream_t s) {
+    const bool quad = (per_row % 4) == 0 && quad_aligned<TM>(moments) && quad_aligned<float>(z) && quad_aligned<float>(x0);
+    const dim3 grid(posterior_blocks(n_total));
+    const TM* m = static_cast<const TM*>(moments);
+    if (quad)
+        hipLaunchKernelGGL((posterior_sample_kernel<TM, true>), grid, dim3(256), 0, s, m, z, x0, per_row, n_total, scale);
+    else
+        hipLaunchKernelGGL((posterior_sample_kernel<TM, false>), grid, dim3(256), 0, s, m, z, x0, per_row, n_total, scale);
+}
+
+bool known_dtype(int dtype) { return dtype == LORA_F32 || dtype == LORA_F16 || dtype == LORA_BF16; }
+
+}  // namespace
+
+extern "C" int ddpm_posterior_prologue(const void* moments, int moments_dtype, const float* sqrt_acp, const float* sqrt_1macp,
+                                       void* noisy, void* target, float* x0_out, float* z_out, float* eps_out, int64_t* t_out,
+                                       int B, int64_t per_row, int n_timesteps, float scale, uint64_t seed, uint64_t step,
+                                       int v_prediction, int dtype, void* stream) {
+    if (!moments || !sqrt_acp || !sqrt_1macp || !noisy || B < 1 || per_row < 1 || n_timesteps < 1) return LORA_E_BADARG;
+    if (!known_dtype(moments_dtype) || !known_dtype(dtype)) return LORA_E_BADARG;
+    PosteriorParams p{};
+    p.moments = moments; p.sa = sqrt_acp; p.sb = sqrt_1macp; p.noisy = noisy; p.target = target;
+    p.x0_out = x0_out; p.z_out = z_out; p.eps_out = eps_out; p.t_out = t_out;
+    p.per_row = per_row; p.n_total = (int64_t)B * per_row; p.n_timesteps = n_timesteps;
+    p.seed = (uint32_t)seed; p.step = (uint32_t)step; p.scale = scale; p.v_pred = v_prediction;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (moments_dtype) {
+        case LORA_F32: launch_posterior_prologue_out<float>(p, dtype, s); break;
+        case LORA_F16: launch_posterior_prologue_out<half_t>(p, dtype, s); break;
+        default: launch_posterior_prologue_out<bf16_t>(p, dtype, s); break;
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+extern "C" int ddpm_posterior_sample(const void* moments, int moments_dtype, const float* z, float* x0, int B, int64_t per_row,
+                                     float scale, void* stream) {
+    if (!moments || !z || !x0 || B < 1 || per_row < 1 || !known_dtype(moments_dtype)) return LORA_E_BADARG;
+    const int64_t n = (int64_t)B * per_row;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (moments_dtype) {
+        case LORA_F32: launch_posterior_sample<float>(moments, z, x0, per_row, n, scale, s); break;
+        case LORA_F16: launch_posterior_sample<half_t>(moments, z, x0, per_row, n, scale, s); break;
+        default: launch_posterior_sample<bf16_t>(moments, z, x0, per_row, n, scale, s); break;
     }
     LORA_LAUNCH_CHECK();
     return LORA_OK;

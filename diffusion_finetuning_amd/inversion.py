@@ -150,23 +150,24 @@ class InversionTrainer:
         return [self.lr * float(self.lr_lambda(self.scheduler_epoch))]
 
     # -- one micro-step ------------------------------------------------------------------------------
-    def step(self, latents, noise=None, timesteps=None, *, input_ids, mask=None, seed: Optional[int] = None,
-             t_multiplier: float = 1.0):
+    def step(self, latents=None, noise=None, timesteps=None, *, input_ids, mask=None, seed: Optional[int] = None,
+             t_multiplier: float = 1.0, moments=None, posterior_noise=None, latent_scale: float = 0.18215):
         """latents fp32 [B,4,h,w] on the device; input_ids int64 [B, L].  Noise: pass `noise` and `timesteps` (the caller drew
         them, as loss_step does, :186-195) or neither and a `seed` — the device draw is then keyed by (seed, micro-step), so the
-        micro-batches of one accumulation window get different noise.  `mask`: raw [B,1,8h,8w] mask (:222-247)."""
+        micro-batches of one accumulation window get different noise.  `mask`: raw [B,1,8h,8w] mask (:222-247).
+        `moments` [B,8,h,w] (the VAE encoder's mean | logvar) in place of `latents`: the micro-step draws the latents itself,
+        `latent_dist.sample() * latent_scale` (:180-184) — in the launch of the device draw, or from the caller's
+        `posterior_noise` (fp32, shaped like the latents) where the caller passes `noise` and `timesteps`."""
         if self.module is None:
             raise RuntimeError("InversionTrainer.step after close()")
-        if (noise is None) != (timesteps is None):
-            raise ValueError("pass both noise and timesteps, or neither (and a seed)")
-        if noise is None and seed is None:
-            raise ValueError("pass noise and timesteps, or a seed for the on-device draw")
+        stp.check_noise_inputs(latents, moments, noise, timesteps, posterior_noise, seed)
         if input_ids.device.type == "cpu" and input_ids.numel():
             if int(input_ids.min()) < 0 or int(input_ids.max()) >= self.V:
                 raise IndexError(f"token id out of range for the {self.V}-row embedding table")
         ids = input_ids.to(self.device, torch.int64)
         nz = stp.Noising(self.sqrt_acp, self.sqrt_1macp, self.dtype, self.v_prediction,
-                         max(1, int(self.sqrt_acp.numel() * float(t_multiplier))))
+                         max(1, int(self.sqrt_acp.numel() * float(t_multiplier))), float(latent_scale))
+        self._drawn_from = (moments, posterior_noise)
         g = self.global_step
         self.scheduler_epoch += 1  # lr_scheduler.step() comes first (:293)
         lr_g = self.lr * float(self.lr_lambda(self.scheduler_epoch))
@@ -191,8 +192,9 @@ class InversionTrainer:
         return stp.loss_backward(pred, target, raw_mask, pred.shape[0], 0, 1.0, 1.0 / self.accum_iter)
 
     def _step_eager(self, latents, noise, timesteps, ids, mask, seed, g, nz):
-        noisy, target, t = stp.noise_prologue(nz, latents, noise, timesteps, seed, g)
-        loss = self._forward_backward(noisy, target, t, ids, stp.raw_mask(mask, latents))
+        moments, posterior_noise = self._drawn_from
+        noisy, target, t = stp.noise_prologue(nz, latents, noise, timesteps, seed, g, moments, posterior_noise)
+        loss = self._forward_backward(noisy, target, t, ids, stp.raw_mask(mask, stp.latents_like(latents, moments)))
         return loss / self.accum_iter
 
     # -- the same micro-step replayed from a hipGraph ---------------------------------------------------
@@ -207,9 +209,12 @@ class InversionTrainer:
         return (self.v_prediction, self.accum_iter, self.module.weight.data_ptr())
 
     def _step_graph(self, latents, noise, timesteps, ids, mask, seed, g, nz):
-        key = (tuple(latents.shape), tuple(ids.shape), noise is None, mask is not None)
+        moments, posterior_noise = self._drawn_from
+        key = (tuple(stp.latents_like(latents, moments).shape), tuple(ids.shape), noise is None, mask is not None)
+        if moments is not None:
+            key += ("moments", moments.dtype, float(nz.scale))
         rec = self._recorder
-        if rec.load(key, self._fingerprint(), nz, latents, noise, timesteps, seed, g, ids, None, mask):
+        if rec.load(key, self._fingerprint(), nz, latents, noise, timesteps, seed, g, ids, None, mask, moments, posterior_noise):
             saved = self.grad.clone()  # the warm-up passes accumulate into the buffer: what the window holds so far is kept
             if not rec.record(self._forward_backward, undo=lambda: self.grad.copy_(saved)):
                 self.capture_graph = False  # keep training: host-launched micro-steps from here on

@@ -20,16 +20,43 @@ class Noising(NamedTuple):
     dtype: torch.dtype  # of the noisy latents and the target
     v_prediction: bool
     n_timesteps: int  # a device draw takes its timesteps from [0, n_timesteps)
+    scale: float = 0.18215  # of latents drawn from VAE moments (train_lora_dreambooth.py:821)
 
 
-def noise_prologue(nz: Noising, latents, noise, timesteps, seed, step_key):
+def noise_prologue(nz: Noising, latents, noise, timesteps, seed, step_key, moments=None, posterior_noise=None):
     """(noisy, target, timesteps): from the caller's `noise` and `timesteps`, or — `noise` None — drawn on the device in the
-    same launch, Philox keyed by (seed, step_key), timesteps uniform."""
+    same launch, Philox keyed by (seed, step_key), timesteps uniform.  `moments` [B,2C,h,w] instead of `latents`: the latents
+    are drawn from them, `latent_dist.sample() * scale` — in that same launch, or from the caller's `posterior_noise` in a
+    launch of its own in front of add_noise."""
+    if moments is not None:
+        if noise is None:
+            return nat.ddpm_posterior_prologue(moments, nz.sqrt_acp, nz.sqrt_1macp, nz.dtype, seed, step_key, nz.v_prediction,
+                                               nz.n_timesteps, nz.scale)
+        latents = nat.ddpm_posterior_sample(moments, posterior_noise, nz.scale)
     if noise is None:
         return nat.ddpm_noise_prologue(latents, nz.sqrt_acp, nz.sqrt_1macp, nz.dtype, seed, step_key, nz.v_prediction,
                                        nz.n_timesteps)
     noisy, target = nat.ddpm_add_noise(latents, noise, timesteps, nz.sqrt_acp, nz.sqrt_1macp, nz.dtype, nz.v_prediction)
     return noisy, target, timesteps
+
+
+def latents_like(latents, moments):
+    """What stands for the latents where only their shape and device are asked: themselves, or the mean half of the moments."""
+    return latents if moments is None else moments[:, : moments.shape[1] // 2]
+
+
+def check_noise_inputs(latents, moments, noise, timesteps, posterior_noise, seed):
+    """The argument rules both trainers share for a step's latents and noise."""
+    if (latents is None) == (moments is None):
+        raise ValueError("pass exactly one of latents and moments")
+    if (noise is None) != (timesteps is None):
+        raise ValueError("pass both noise and timesteps, or neither (and a seed)")
+    if noise is None and seed is None:
+        raise ValueError("pass noise and timesteps, or a seed for the on-device draw")
+    if moments is not None and noise is not None and posterior_noise is None:
+        raise ValueError("moments with the caller's noise and timesteps need the caller's posterior_noise as well")
+    if posterior_noise is not None and (moments is None or noise is None):
+        raise ValueError("posterior_noise goes with moments and the caller's noise and timesteps")
 
 
 def raw_mask(mask, like):
@@ -60,21 +87,31 @@ class StepRecorder:
 
     def drop(self):
         self.graph = self.key = self.fp = self.nz = self.drawn = self.inputs = self.cond = self.mask = None
+        self.moments = None  # moments-fed with the caller's noise: static (moments, posterior noise) the recording reads
         self.loss = None  # the loss tensor every replay writes
         self.held = None  # what `record`'s `keep` returned: alive as long as the recording is
 
-    def load(self, key, fp, nz: Noising, latents, noise, timesteps, seed, step_key, cond, cond_dtype, mask) -> bool:
+    def load(self, key, fp, nz: Noising, latents, noise, timesteps, seed, step_key, cond, cond_dtype, mask, moments=None,
+             posterior_noise=None) -> bool:
         """Copies one step's inputs into the static buffers (host-launched).  `key`: the shapes and modes of the step; `fp`:
         whatever else a recording bakes in (scalars passed as kernel arguments, addresses of frozen operands).  When either
         differs from the recording's, that recording is dropped and the buffers of this step's mode are allocated first (`cond`:
-        hidden states, kept in `cond_dtype`, or token ids); the caller then has to `record`: True."""
+        hidden states, kept in `cond_dtype`, or token ids); the caller then has to `record`: True.  `moments` in place of
+        `latents` (the key has to tell the two apart, and the moments' dtype): with the caller's noise they and the
+        `posterior_noise` get static buffers of their own, which the recording's first launch reads."""
         fresh = self.graph is None or self.key != key or self.fp != fp
+        sampled = moments is not None and noise is not None
+        if moments is not None:
+            latents = latents_like(None, moments)  # (shape and device; never read)
         if fresh:
             self.drop()  # the old recording (and the operand buffers it pins) goes before a new one is made
             self.key, self.fp, self.nz, self.drawn = key, fp, nz, noise is None
             dt = nz.dtype if self.drawn else torch.float32
-            self.inputs = (torch.empty_like(latents, dtype=dt), torch.empty_like(latents, dtype=dt),
+            new = lambda: torch.empty(latents.shape, dtype=dt, device=latents.device)
+            self.inputs = (None if sampled else new(), new(),
                            torch.empty(latents.shape[0], dtype=torch.int64, device=latents.device))
+            if sampled:
+                self.moments = (torch.empty_like(moments), new())
             self.cond = torch.empty_like(cond, dtype=cond_dtype, device=latents.device)
             if mask is not None:
                 self.mask = torch.empty_like(raw_mask(mask, latents))
@@ -82,9 +119,13 @@ class StepRecorder:
         # (noisy, target, timesteps)
         values = (latents, noise, timesteps)
         if self.drawn:
-            values = noise_prologue(nz, latents, None, None, seed, step_key)
+            values = noise_prologue(nz, latents, None, None, seed, step_key, moments=moments)
         for buffer, value in zip(self.inputs, values):
-            buffer.copy_(value)
+            if buffer is not None:
+                buffer.copy_(value)
+        if sampled:
+            self.moments[0].copy_(moments)
+            self.moments[1].copy_(posterior_noise)
         self.cond.copy_(cond)  # (hidden states: casts to the compute dtype)
         if mask is not None:
             self.mask.copy_(raw_mask(mask, latents))
@@ -92,8 +133,12 @@ class StepRecorder:
 
     def _run(self, body):
         """body(noisy, target, timesteps, cond, raw mask) on the static buffers: add_noise on the caller's noise is the first
-        launch of the recording."""
-        noised = self.inputs if self.drawn else noise_prologue(self.nz, *self.inputs, None, None)
+        launch of the recording — behind posterior_sample where the step is fed with moments."""
+        if self.drawn:
+            noised = self.inputs
+        else:
+            moments, posterior_noise = self.moments or (None, None)
+            noised = noise_prologue(self.nz, *self.inputs, None, None, moments=moments, posterior_noise=posterior_noise)
         return body(*noised, self.cond, self.mask)
 
     def _capture(self, body, before_capture):

@@ -640,9 +640,10 @@ class TokenTable:
     def begin_pass(self):
         self._pending = []
 
-    def collect(self, pg, world: int):
-        """Table gradient of the passes since begin_pass(): rows of the tokens that occurred, summed in position order."""
-        for k, (ids, rows) in enumerate(self._pending):
+    def collect(self, pg, world: int, accumulate: bool = False):
+        """Table gradient of the passes since begin_pass(): rows of the tokens that occurred, summed in position order —
+        `accumulate`: on top of what earlier micro-batches of an accumulation window left in the table's gradient."""
+        for k, (ids, rows) in enumerate(self._pending, start=int(accumulate)):
             if world > 1:
                 all_ids = [torch.empty_like(ids) for _ in range(world)]
                 all_rows = [torch.empty_like(rows) for _ in range(world)]
@@ -661,7 +662,8 @@ class LoraTrainer:
                  v_prediction=False, process_group=None, always_reduce=False, capture_graph=False,
                  group_projections=True, lr_embed: float = 5e-4, weight_decay_embed: Optional[float] = None,
                  lr_scheduler: str = "constant", lr_warmup_steps: int = 0, max_train_steps: Optional[int] = None,
-                 scheduler_steps_first: bool = False, early_bucket: bool = False, scheduler_steps_per_call: int = 1):
+                 scheduler_steps_first: bool = False, early_bucket: bool = False, scheduler_steps_per_call: int = 1,
+                 gradient_accumulation_steps: int = 1):
         """capture_graph: record add_noise → [text encoder] → UNet forward → loss → backward → factor gradients of a step
         once into a hipGraph and replay it on later steps with the same shapes (inputs are copied into static buffers).
         The gradient exchange and the optimizer stay outside the graph, so no collective is ever captured.  A step with a
@@ -689,7 +691,21 @@ class LoraTrainer:
         here: that N× rule is restated from its published AcceleratedScheduler, parity unpinned.  Not reproduced: accelerate
         also holds the scheduler back on a step its GradScaler skipped — the skip is known here only two steps later
         (LossScaler's fixed lag), so the schedule counts every step() call; it matters for none of the reference's fp16
-        defaults ("constant"; PTI has no scaler)."""
+        defaults ("constant"; PTI has no scaler).
+        `gradient_accumulation_steps` = n (train_lora_dreambooth.py:310,490,878-893): with n > 1 one `step()` is one micro-batch.
+        Its gradient, scaled by loss_scale / n (accelerate's division of the loss, :877), is added to the slab — zeroed at the
+        first micro-batch of a window only — and the exchange, clip + AdamW, the overflow flag, the re-pack and the scheduler's
+        step run at the window's last micro-batch alone (`sync_gradients`): data-parallel ranks exchange once per window, and an
+        early bucket is armed for that micro-batch only.  A recording serves every micro-batch of a window (the 1/n is baked in).
+        A non-finite micro-batch poisons the window's sum and the one norm at its end skips the step, as GradScaler does under
+        accumulation; the loss scale moves between windows only.  The schedule advances once per OPTIMIZER step: the script
+        multiplies the step counts it hands its scheduler by n (:740-741) — pass `lr_warmup_steps` / `max_train_steps` multiplied
+        like that to follow it.  Training the text encoder (LoRA or token table) with n > 1 under data parallelism is refused as
+        the script refuses it (:496-507)."""
+        self.accum = int(gradient_accumulation_steps)
+        if self.accum < 1:
+            raise ValueError("gradient_accumulation_steps must be >= 1")
+        self._micro = 0  # index of the next micro-batch inside its accumulation window
         self.unet, self.text_encoder = unet, text_encoder
         self.early_bucket = bool(early_bucket)
         self.lr_lambda = lr_lambda(lr_scheduler, lr_warmup_steps, max_train_steps, lr_init=lr)
@@ -705,6 +721,10 @@ class LoraTrainer:
             else None
         train_emb = emb is not None and emb.weight.requires_grad
         self.trains_text_encoder = len(models) > 1 or train_emb
+        self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
+        if self.trains_text_encoder and self.accum > 1 and self.world > 1:
+            raise ValueError("gradient accumulation is not supported while the text encoder trains under data parallelism "
+                             "(train_lora_dreambooth.py:496-507); set gradient_accumulation_steps to 1")
         self.slab = LoraSlab(models, [emb.weight] if train_emb else [])
         if group_projections:
             # early_bucket: the cross-attentions of the down blocks project their K/V in a launch of their own, so that the
@@ -738,7 +758,6 @@ class LoraTrainer:
         self.v_prediction = v_prediction
         self.sqrt_acp, self.sqrt_1macp = ddpm_tables(device=self.device)
         self.pg = process_group
-        self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         self.exchange = SlabExchange(self.slab.grads, self.slab.numel, process_group, always_reduce=always_reduce)
         # A recorded step exchanges the slab in one all-reduce.  Once recording was ASKED for, every step of this trainer
         # does — also the host-launched ones (recording failed on this rank only, a step that is not recordable): the
@@ -833,7 +852,7 @@ class LoraTrainer:
             ffs = self._ff_modules = [m for m in self.unet.modules()
                                       if m.__class__.__name__ == "FeedForward" and hasattr(m, "net") and len(m.net) == 3]
         ff2 = tuple((m.net[2].weight.data_ptr(), m.net[2].weight._version) for m in ffs if "forward" in m.__dict__)
-        return (self.loss_scale, self.v_prediction, tuple(float(l.scale) for l in layers),
+        return (self.loss_scale, self.accum, self.v_prediction, tuple(float(l.scale) for l in layers),
                 tuple((l.linear.weight.data_ptr(), l.linear.weight._version) for l in layers), ff2)
 
     def _scheduled_lr_factor(self) -> float:
@@ -851,32 +870,46 @@ class LoraTrainer:
         return [g["lr"] * lam for g in self.opt.groups]
 
     # -- one step ---------------------------------------------------------------------------------
-    def step(self, latents, noise, timesteps, encoder_hidden_states=None, *, with_prior_preservation=False,
-             prior_loss_weight=1.0, mask=None, seed: Optional[int] = None, input_ids=None, t_multiplier: float = 1.0):
-        """latents fp32 [B,4,h,w] on the device.  Conditioning: `encoder_hidden_states` [B,L,D] — or `input_ids` [B,L]
+    def step(self, latents=None, noise=None, timesteps=None, encoder_hidden_states=None, *, with_prior_preservation=False,
+             prior_loss_weight=1.0, mask=None, seed: Optional[int] = None, input_ids=None, t_multiplier: float = 1.0,
+             moments=None, posterior_noise=None, latent_scale: float = 0.18215):
+        """latents fp32 [B,4,h,w] on the device — or `moments` [B,8,h,w] (fp32 / f16 / bf16), the VAE encoder's mean | logvar,
+        exactly one of the two: the step then draws the latents itself, `latent_dist.sample() * latent_scale`
+        (train_lora_dreambooth.py:818-821), in the launch that draws the noise (needs a `seed`) or — with the caller's `noise`
+        and `timesteps` — from the caller's `posterior_noise` (fp32, shaped like the latents) in a launch in front of add_noise.
+        Under prior preservation the caller concatenates instance and class moments, as it does pixels.
+        Conditioning: `encoder_hidden_states` [B,L,D] — or `input_ids` [B,L]
         (int64), in which case the step itself runs `text_encoder(input_ids)[0]` as the reference's loop does
         (train_lora_dreambooth.py:840); with a LoRA text encoder that is what makes the step recordable.  Noise: either
         pass `noise` (fp32, like latents) and `timesteps` (int64 [B]) — the caller drew them, as the reference does — or
         pass None for both and a `seed`: the step then draws them on the device (Philox keyed by (seed, optimizer step),
         identical on every rank) inside the prologue kernel, timesteps uniform on [0, int(1000·t_multiplier)) — the PTI loop's
-        `t_mutliplier` (cli_lora_pti.py:176,190-195).  `mask`: raw [B,1,8h,8w] mask of cli_lora_pti.py:222-247."""
+        `t_mutliplier` (cli_lora_pti.py:176,190-195).  `mask`: raw [B,1,8h,8w] mask of cli_lora_pti.py:222-247.
+        With `gradient_accumulation_steps` = n > 1 this is one micro-batch: the device draw is keyed by (seed, optimizer step · n
+        + index of the micro-batch), so the micro-batches of a window draw differently; the loss returned is the micro-batch's
+        own, undivided, as the loop logs it."""
         self._noising = stp.Noising(self.sqrt_acp, self.sqrt_1macp, self.dtype, self.v_prediction,
-                                    max(1, int(self.sqrt_acp.numel() * float(t_multiplier))))
+                                    max(1, int(self.sqrt_acp.numel() * float(t_multiplier))), float(latent_scale))
         if (encoder_hidden_states is None) == (input_ids is None):
             raise ValueError("pass exactly one of encoder_hidden_states and input_ids")
         if input_ids is not None and self.text_encoder is None:
             raise ValueError("input_ids given but the trainer has no text encoder")
-        if noise is None and seed is None:
-            raise ValueError("pass noise and timesteps, or a seed for the on-device draw")
+        stp.check_noise_inputs(latents, moments, noise, timesteps, posterior_noise, seed)
         if self.token_table is not None and input_ids is not None and input_ids.device.type == "cpu":
             self.token_table.check_ids(input_ids)  # (free on the host; a replayed step cannot check device-resident ids)
-        self._poll_overflow()
+        if self._micro == 0:  # (one loss scale per accumulation window: its micro-batches are summed)
+            self._poll_overflow()
+        self._drawn_from = (moments, posterior_noise)
         recordable = not self.trains_text_encoder or input_ids is not None
         if self.capture_graph and recordable:
             return self._step_graph(latents, noise, timesteps, encoder_hidden_states, input_ids, mask,
                                     with_prior_preservation, prior_loss_weight, seed)
         return self._step_eager(latents, noise, timesteps, encoder_hidden_states, input_ids, with_prior_preservation,
                                 prior_loss_weight, mask, seed)
+
+    def _noise_key(self) -> int:
+        """The step half of the device draw's Philox key: one per micro-batch."""
+        return self.opt.step_count * self.accum + self._micro
 
     def _conditioning(self, encoder_hidden_states, input_ids):
         if input_ids is None:
@@ -891,13 +924,23 @@ class LoraTrainer:
         pred = self.unet(noisy, timesteps, ehs).sample
         rows = pred.shape[0]
         n_inst, n_prior = (rows // 2, rows // 2) if prior else (rows, 0)
-        loss = stp.loss_backward(pred, target, raw_mask, n_inst, n_prior, prior_weight, self.loss_scale)
+        loss = stp.loss_backward(pred, target, raw_mask, n_inst, n_prior, prior_weight, self.loss_scale / self.accum)
         self.slab.flush()  # factor gradients of every layer that ran: batched launch + ordered fold into the slab
         return loss
 
     def _finish_step(self, recorded_rows=None):
         """What follows backward, host-launched on both routes: exchange, token-table gradient, clip + AdamW, re-pack.
-        `recorded_rows`: the (ids, gradient rows) buffers a replayed recording has just written."""
+        `recorded_rows`: the (ids, gradient rows) buffers a replayed recording has just written.
+        Inside an accumulation window only the token-table gradient is gathered (world 1 there: a local, ordered sum — a
+        recording's row buffers are rewritten by the next replay, so it cannot wait for the window's end); everything else
+        waits for the window's last micro-batch."""
+        micro, self._micro = self._micro, (self._micro + 1) % self.accum
+        if self._micro != 0:
+            if self.token_table is not None:
+                if recorded_rows is not None:
+                    self.token_table._pending = list(recorded_rows)
+                self.token_table.collect(self.pg, 1, accumulate=micro > 0)
+            return
         tail = self.tail_events
         if tail is not None:  # (bench.py: device time of this tail — with an early bucket its all-reduce is behind us)
             tail.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
@@ -906,7 +949,7 @@ class LoraTrainer:
         if self.token_table is not None:
             if recorded_rows is not None:
                 self.token_table._pending = list(recorded_rows)
-            self.token_table.collect(self.pg, self.world if self.exchange.active else 1)
+            self.token_table.collect(self.pg, self.world if self.exchange.active else 1, accumulate=micro > 0)
         self.opt.step(grad_mul=1.0 / (self.world * self.loss_scale), lr_mul=self._scheduled_lr_factor())
         self._watch_overflow()
         self.slab.repack()  # forwards outside step() (sampling, evaluation, saving merged weights) see the new factors
@@ -917,15 +960,19 @@ class LoraTrainer:
                     prior_loss_weight, mask, seed):
         """Host-launched step.  Exchange: two buckets with the early one overlapping backward where that is possible
         (SlabExchange / _install_bucket_hook) — unless a recorded step was asked for (exchange.single)."""
-        self.slab.zero_grad()
+        moments, posterior_noise = self._drawn_from
+        if self._micro == 0:
+            self.slab.zero_grad()
         self.slab.repack()  # packed compute-dtype factors follow the fp32 masters (also after external edits)
-        noisy, target, timesteps = stp.noise_prologue(self._noising, latents, noise, timesteps, seed, self.opt.step_count)
-        self.exchange.arm()
+        noisy, target, timesteps = stp.noise_prologue(self._noising, latents, noise, timesteps, seed, self._noise_key(),
+                                                      moments, posterior_noise)
+        if self._micro == self.accum - 1:  # (the exchange belongs to the window's last micro-batch)
+            self.exchange.arm()
         if self.token_table is not None:
             self.token_table.begin_pass()
         ehs = self._conditioning(encoder_hidden_states, input_ids)
         loss = self._forward_backward(noisy, target, timesteps, ehs, with_prior_preservation, prior_loss_weight,
-                                      stp.raw_mask(mask, latents))
+                                      stp.raw_mask(mask, stp.latents_like(latents, moments)))
         self._finish_step()
         return loss
 
@@ -949,13 +996,22 @@ class LoraTrainer:
         return self.slab.take_recording_plans(), (list(self.token_table._pending) if self.token_table is not None else None)
 
     def _step_graph(self, latents, noise, timesteps, ehs, ids, mask, prior, prior_weight, seed):
+        moments, posterior_noise = self._drawn_from
         cond_shape = tuple(ehs.shape) if ids is None else ("ids",) + tuple(ids.shape)
-        key = (tuple(latents.shape), cond_shape, bool(prior), float(prior_weight), noise is None, mask is not None)
+        key = (tuple(stp.latents_like(latents, moments).shape), cond_shape, bool(prior), float(prior_weight), noise is None,
+               mask is not None)
+        if moments is not None:
+            key += ("moments", moments.dtype, float(self._noising.scale))
         rec = self._recorder
         cond, cond_dtype = (ehs, self.dtype) if ids is None else (ids, None)
-        fresh = rec.load(key, self._fingerprint(), self._noising, latents, noise, timesteps, seed, self.opt.step_count,
-                         cond, cond_dtype, mask)
-        self.slab.zero_grad()
+        fresh = rec.load(key, self._fingerprint(), self._noising, latents, noise, timesteps, seed, self._noise_key(),
+                         cond, cond_dtype, mask, moments, posterior_noise)
+        undo = self.slab.zero_grad
+        if self._micro == 0:
+            self.slab.zero_grad()
+        elif fresh:  # recording inside a window: what the window has summed so far survives the warm-up passes
+            summed = self.slab.grads.clone()
+            undo = lambda: (self.slab.zero_grad(), self.slab.grads.copy_(summed))
         self.slab.repack()
         if fresh:
             body = functools.partial(self._graph_body, ids is not None, bool(prior), float(prior_weight))
@@ -963,7 +1019,7 @@ class LoraTrainer:
             # warm-up passes each folded this step's gradients into the slab — clear it, then replay once so that every step
             # (including the first) is produced by the same recorded kernels
             if not rec.record(body, before_capture=self.slab.prepare_recording, keep=self._recording_owns,
-                              undo=self.slab.zero_grad):
+                              undo=undo):
                 # keep training: this trainer falls back to host-launched steps for good.  exchange.single stays set: this
                 # rank keeps issuing the one whole-slab all-reduce its peers' replays issue
                 self.capture_graph = False

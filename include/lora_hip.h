@@ -365,6 +365,32 @@ int ddpm_noise_prologue(const float* x0, const float* sqrt_acp, const float* sqr
                         int v_prediction, int dtype, void* stream);
 
 /*
+ * The prologue one step earlier: the latents are drawn from the VAE encoder's moments instead of being handed in —
+ * `vae.encode(pixels).latent_dist.sample() * 0.18215`, training_scripts/train_lora_dreambooth.py:818-821 and
+ * lora_diffusion/cli_lora_pti.py:180-184 — so a training set caches the moments and every iteration draws afresh:
+ *     lv = clamp(logvar, −30, 20);  x0 = (mean + exp(0.5·lv)·z)·scale,  z ~ N(0,1),  scale = 0.18215 in the reference
+ * (DiagonalGaussianDistribution.sample is diffusers', not vendored in the reference: restated from its published
+ * definition, parity unpinned).  moments [B, 2·per_row] in `moments_dtype` (f32 / f16 / bf16), row b = mean [per_row] |
+ * logvar [per_row] — a contiguous [B, 2C, h, w]; all arithmetic fp32.
+ *   ddpm_posterior_prologue : the device-drawn form, ONE launch for chunk + clamp + exp + randn + mul + add + mul and the
+ *       whole of ddpm_noise_prologue.  z comes from Philox stream 2 — element group g uses counter (g, g>>32, 2, 0), same
+ *       Box–Muller — next to eps (g, g>>32, 0, 0) and t (b, 0, 1, 0): for equal (seed, step) eps and t are bit-identical
+ *       to ddpm_noise_prologue's, and z is independent of both.  noisy / target (nullable) in `dtype`; x0_out, z_out,
+ *       eps_out (fp32) and t_out (int64) are optional copies.
+ *   ddpm_posterior_sample : the caller-drawn form (the reference's route: z from torch's generator), x0 fp32 from an fp32
+ *       z [B, per_row]; ddpm_add_noise follows it.
+ * 16-byte (fp32) / 8-byte (16-bit) accesses when per_row % 4 == 0 and every pointer is aligned to 4 of its elements,
+ * element by element otherwise.  No workspace, nothing retained, capturable.
+ */
+int ddpm_posterior_prologue(const void* moments, int moments_dtype, const float* sqrt_acp, const float* sqrt_1macp,
+                            void* noisy, void* target /* nullable */, float* x0_out /* nullable */,
+                            float* z_out /* nullable */, float* eps_out /* nullable */, int64_t* t_out /* nullable */,
+                            int B, int64_t per_row, int n_timesteps, float scale, uint64_t seed, uint64_t step,
+                            int v_prediction, int dtype, void* stream);
+int ddpm_posterior_sample(const void* moments, int moments_dtype, const float* z, float* x0, int B, int64_t per_row,
+                          float scale, void* stream);
+
+/*
  * The two ops sandwiched by the hot path inside a transformer block, as streaming kernels.
  *   geglu_gate_fwd : out[M,C]  = h · gelu(g)  with [h | g] = y[M,2C], exact (erf) gelu — the body of diffusers'
  *                    GEGLU.forward, the caller of the `proj` LoraInjectedLinear (target class "GEGLU", lora.py:53).
