@@ -129,6 +129,12 @@ SIGNATURES = {
     "lora_distill_rayleigh_ritz": (_i32, [_vp, _i32, _i32, _i32, ctypes.c_double, _i32, _vp, _vp]),
     "lora_distill_finalize": (_i32, [_vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
     "lora_quantile_clamp": (_i32, [_vp, _i64, _f32, _vp, _vp]),
+    "lora_distill_wide_width": (_i32, [_i32]),
+    "lora_distill_wide_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "lora_distill_wide_start": (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _vp]),
+    "lora_distill_wide_diff": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "lora_distill_wide_rayleigh_ritz": (_i32, [_vp, _i32, _i32, _i32, ctypes.c_double, _i32, _vp, _vp]),
+    "lora_distill_wide_finalize": (_i32, [_vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
     "lora_prof_enable": (_i32, [_i32]),
     "lora_prof_collect": (_i32, [ctypes.POINTER(ProfTotals)]),
     "lora_prof_null_mode": (_i32, [_i32]),
@@ -715,29 +721,58 @@ def ti_rows_adamw_decay(table, slot_ids, grad, exp_avg, exp_avg_sq, grad_mul, lr
                                      int(step), float(decay_lambda), float(target_norm), _stream(table)), "ti_rows_adamw_decay")
 
 
-def distill_workspace_bytes(N: int, K: int) -> int:
-    """Bytes of the per-layer workspace of the svd_distill kernels (include/lora_hip.h: lora_distill_*)."""
-    return int(lib().lora_distill_workspace_bytes(N, K))
+DISTILL_NARROW_MAX_RANK = 16  # the width-32 kernels (lora_distill_*); above it the lora_distill_wide_* entries
+DISTILL_MAX_RANK = 64
 
 
-def distill_start(table, n_layers: int, min_nk: int, r: int, seed: int, ws) -> None:
-    _check(lib().lora_distill_start(_ptr(table), n_layers, min_nk, r, seed, _ptr(ws), _stream(ws)), "lora_distill_start")
+def distill_width(r: int) -> int:
+    """Block width (columns of the Y, Z, V blocks) the svd_distill kernels run rank r at."""
+    if r <= DISTILL_NARROW_MAX_RANK:
+        return 32
+    w = lib().lora_distill_wide_width(r)
+    if w < 0:
+        _check(w, "lora_distill_wide_width")
+    return w
 
 
-def distill_diff(table, n_layers: int, max_rows: int, transpose: bool, dtype: torch.dtype, ws) -> None:
-    _check(lib().lora_distill_diff(_ptr(table), n_layers, max_rows, int(transpose), dtype_code(dtype), _ptr(ws), _stream(ws)),
-           "lora_distill_diff")
+class DistillKernels:
+    """The svd_distill kernel set that solves rank r (include/lora_hip.h: lora_distill_* for r <= 16, lora_distill_wide_*
+    above, whose layout depends on r).  The C entries are resolved here, once per solve, so that a launch costs what a direct
+    call of the entry costs."""
+
+    def __init__(self, r: int):
+        self.r = r = int(r)
+        wide = r > DISTILL_NARROW_MAX_RANK
+        self._prefix = "lora_distill_wide_" if wide else "lora_distill_"
+        self._r = (r,) if wide else ()  # the rank, where only the wide entry takes it
+        handle = lib()
+        self._ws_bytes, self._start, self._diff, self._rr, self._finalize = (
+            getattr(handle, self._prefix + n) for n in ("workspace_bytes", "start", "diff", "rayleigh_ritz", "finalize"))
+
+    def workspace_bytes(self, N: int, K: int) -> int:
+        """Bytes of the per-layer workspace."""
+        return int(self._ws_bytes(N, K, *self._r))
+
+    def start(self, table, n_layers: int, min_nk: int, seed: int, ws) -> None:
+        _check(self._start(_ptr(table), n_layers, min_nk, self.r, seed, _ptr(ws), _stream(ws)), self._prefix + "start")
+
+    def diff(self, table, n_layers: int, max_rows: int, transpose: bool, dtype: torch.dtype, ws) -> None:
+        _check(self._diff(_ptr(table), n_layers, max_rows, int(transpose), dtype_code(dtype), *self._r, _ptr(ws), _stream(ws)),
+               self._prefix + "diff")
+
+    def rayleigh_ritz(self, table, n_layers: int, side: int, tol: float, last: bool, ws) -> None:
+        _check(self._rr(_ptr(table), n_layers, side, self.r, float(tol), int(last), _ptr(ws), _stream(ws)),
+               self._prefix + "rayleigh_ritz")
+
+    def finalize(self, table, n_layers: int, q, ws, out) -> None:
+        """q = None: no quantile clamp."""
+        _check(self._finalize(_ptr(table), n_layers, self.r, 0.0 if q is None else float(q), int(q is not None), _ptr(ws),
+                              _ptr(out), _stream(ws)), self._prefix + "finalize")
 
 
-def distill_rayleigh_ritz(table, n_layers: int, side: int, r: int, tol: float, last: bool, ws) -> None:
-    _check(lib().lora_distill_rayleigh_ritz(_ptr(table), n_layers, side, r, float(tol), int(last), _ptr(ws), _stream(ws)),
-           "lora_distill_rayleigh_ritz")
-
-
-def distill_finalize(table, n_layers: int, r: int, q, ws, out) -> None:
-    """q = None: no quantile clamp."""
-    _check(lib().lora_distill_finalize(_ptr(table), n_layers, r, 0.0 if q is None else float(q), int(q is not None), _ptr(ws),
-                                       _ptr(out), _stream(ws)), "lora_distill_finalize")
+def distill_workspace_bytes(N: int, K: int, r: int) -> int:
+    """Bytes of the per-layer workspace of the svd_distill kernels at rank r."""
+    return DistillKernels(r).workspace_bytes(N, K)
 
 
 def quantile_clamp_(x, q: float, hi_out=None) -> None:

@@ -4,18 +4,18 @@
 //
 // Per-layer workspace (lora_distill_workspace_bytes): a state header, the Ritz data of the last left step (λ, Ũ in fp64) and
 // three fp32 blocks of width 32: Y/U [N,32], Z [K,32], V [K,32].  Columns beyond min(N,K) carry zero eigenvalues and are
-// masked, so the block width l = min(32, N, K) needs no special case.
-#include "common.h"
+// masked, so the block width l = min(32, N, K) needs no special case.  Ranks 17–64 run on distill_wide.hip; the helpers both
+// share (difference on load, start block, workgroup sum, quantile clamp) are in distill_common.h.
+#include "distill_common.h"
 
 namespace {
 
 constexpr int kW = 32;               // block width l (columns of Y, Z, V)
-constexpr int kTile = 64;            // rows of a diff-GEMM tile
 constexpr int kMaxSweeps = 24;       // Jacobi sweeps (a 32×32 matrix converges in 6–9)
-constexpr double kMaskEps = 1e-12;   // λ ≤ ε·λ_max: a dropped direction (σ below 1e-6·σ_1: fp32 noise)
 
-// workspace layout of one layer (bytes)
-constexpr int64_t kOffFlag = 0;      // int32: 0 running, 1 converged, 2 hit max_iters, 3 non-finite
+// workspace layout of one layer (bytes).  Twin: distill_wide.hip restates the header offsets, Layer, load_layer and the Jacobi
+// body at a template width; a fix to any of them here is carried there.
+constexpr int64_t kOffFlag = 0;     // int32: 0 running, 1 converged, 2 hit max_iters, 3 non-finite
 constexpr int64_t kOffIters = 4;     // int32: iterations done
 constexpr int64_t kOffRes = 8;       // double: last residual max_i ‖Dᵀu_i − σ_i v_i‖ / σ_1
 constexpr int64_t kOffLam = 64;      // double[32]: λ of the last left step, descending, masked ones 0
@@ -47,14 +47,6 @@ __device__ __forceinline__ Layer load_layer(const int64_t* table, unsigned char*
     L.out_off = row[5];
     L.id = row[6];
     return L;
-}
-
-// D = T(w1 − w0) as fp32: the reference subtracts in the weights' dtype (cli_svd.py:59-63), then .float() (:69).  The fp32
-// difference of two 16-bit values rounded once to the 16-bit type is the correctly rounded 16-bit difference (24 ≥ 2·11 + 2).
-template <typename T> __device__ __forceinline__ float diff_of(const T* w1, const T* w0, int64_t i) {
-    const float d = to_f32(w1[i]) - to_f32(w0[i]);
-    if constexpr (sizeof(T) == 4) return d;
-    else return to_f32(from_f32<T>(d));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -112,20 +104,6 @@ __global__ __launch_bounds__(256) void distill_diff_kernel(const int64_t* table,
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Workgroup helpers (256 threads).  Reductions are fixed-order LDS trees: the results do not depend on timing.
-__device__ double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // H (32×32, symmetric, LDS) → eigenvalues on its diagonal, eigenvectors in the columns of E: cyclic Jacobi in
 // parallel (round-robin) order, 16 disjoint rotations per round, 31 rounds per sweep.
 __device__ void jacobi32(double (*H)[kW + 1], double (*E)[kW + 1], double* red, double* cs) {
@@ -187,16 +165,6 @@ __device__ void jacobi32(double (*H)[kW + 1], double (*E)[kW + 1], double* red, 
             __syncthreads();
         }
     }
-}
-
-__device__ __forceinline__ float start_value(uint64_t seed, int64_t layer, int64_t e) {
-    uint64_t x = seed ^ (uint64_t)(layer + 1) * 0x9E3779B97F4A7C15ull ^ (uint64_t)e * 0xD1B54A32D192ED03ull;
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return (float)(x >> 40) * (2.0f / 16777216.0f) - 1.0f;  // uniform in [-1, 1)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -366,67 +334,6 @@ __global__ __launch_bounds__(256) void distill_rr_kernel(const int64_t* table, u
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// torch.quantile (linear interpolation) + torch.clamp(−hi, hi) over x[0..n) in place, by one workgroup.
-// Radix select on order-preserving uint32 keys (−0 counted as +0), 4 passes of 8 bits per order statistic.
-__device__ __forceinline__ uint32_t fkey(float f) {
-    uint32_t u = __float_as_uint(f);
-    if (f == 0.f) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
-__device__ float radix_select(const float* x, int64_t n, int64_t k, int* hist, int64_t* sh) {
-    const int tid = threadIdx.x;
-    uint32_t prefix = 0, pmask = 0;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        hist[tid] = 0;
-        __syncthreads();
-        for (int64_t e = tid; e < n; e += 256) {
-            const uint32_t key = fkey(x[e]);
-            if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int64_t cum = 0;
-            int b = 0;
-            for (; b < 255; ++b) {
-                if (cum + hist[b] > k) break;
-                cum += hist[b];
-            }
-            sh[0] = prefix | ((uint32_t)b << shift);
-            sh[1] = k - cum;
-        }
-        __syncthreads();
-        prefix = (uint32_t)sh[0];
-        k = sh[1];
-        pmask |= 0xFFu << shift;
-        __syncthreads();
-    }
-    return fkey_inv(prefix);
-}
-
-// returns hi (the clamp bound); x is clamped in place when `clamp`
-__device__ float quantile_clamp(float* x, int64_t n, float q, bool clamp, int* hist, int64_t* sh) {
-    // torch: ranks = q·(n−1) in the input's dtype (fp32), below = trunc, above = ceil, w = ranks − below,
-    // lerp(a, b, w) = |w| < 0.5 ? a + w·(b − a) : b − (b − a)·(1 − w), each product-sum one fused multiply-add
-    const float rank = __fmul_rn(q, (float)(n - 1));
-    const int64_t lo = (int64_t)rank;
-    const int64_t hi = (int64_t)ceilf(rank);
-    const float w = __fsub_rn(rank, (float)lo);
-    const float a = radix_select(x, n, lo, hist, sh);
-    const float b = hi == lo ? a : radix_select(x, n, hi, hist, sh);
-    const float d = __fsub_rn(b, a);
-    const float v = fabsf(w) < 0.5f ? __fmaf_rn(w, d, a) : __fmaf_rn(-d, __fsub_rn(1.f, w), b);
-    if (clamp) {
-        const float lo_v = -v;
-        for (int64_t e = threadIdx.x; e < n; e += 256) x[e] = fminf(fmaxf(x[e], lo_v), v);  // torch.clamp(min, max)
-        __syncthreads();
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(256) void quantile_clamp_kernel(float* x, int64_t n, float q, float* hi_out) {
     __shared__ int hist[256];
     __shared__ int64_t sh[2];
@@ -434,75 +341,12 @@ __global__ __launch_bounds__(256) void quantile_clamp_kernel(float* x, int64_t n
     if (threadIdx.x == 0 && hi_out) *hi_out = v;
 }
 
-// Final factors of one layer into out[out_off ..]: up [N,r] = U_r·diag(σ_r), down [r,K] = V_rᵀ; the sign of each pair
-// makes the largest-magnitude entry of the down row positive (ties: lowest index); then the quantile clamp.
+// Final factors of every layer into out[out_off ..] (finalize_layer of distill_common.h at row stride 32).
 __global__ __launch_bounds__(256) void distill_finalize_kernel(const int64_t* table, unsigned char* ws, int r, float q,
                                                                int clamp, float* out) {
     const Layer L = load_layer(table, ws, blockIdx.x);
     if (*L.flag() == 3) return;
-    const int tid = threadIdx.x;
-    __shared__ float redv[256];
-    __shared__ int64_t redi[256];
-    __shared__ float sgn[16];
-    __shared__ int hist[256];
-    __shared__ int64_t sh[2];
-    __shared__ int bad;
-    const float* V = L.V();
-    const float* U = L.Y();
-    const double* lam = L.lam();
-    for (int i = 0; i < r; ++i) {
-        float best = -1.f;
-        int64_t bi = 0;
-        for (int64_t k = tid; k < L.K; k += 256) {
-            const float a = fabsf(V[k * kW + i]);
-            if (a > best) {
-                best = a;
-                bi = k;
-            }
-        }
-        redv[tid] = best;
-        redi[tid] = bi;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (tid < s) {
-                const float o = redv[tid + s];
-                const int64_t oi = redi[tid + s];
-                if (o > redv[tid] || (o == redv[tid] && oi < redi[tid])) {
-                    redv[tid] = o;
-                    redi[tid] = oi;
-                }
-            }
-            __syncthreads();
-        }
-        if (tid == 0) sgn[i] = V[redi[0] * kW + i] < 0.f ? -1.f : 1.f;
-        __syncthreads();
-    }
-    if (tid == 0) bad = 0;
-    __syncthreads();
-    float* up = out + L.out_off;
-    float* down = up + L.N * r;
-    int my_bad = 0;
-    for (int64_t e = tid; e < L.N * r; e += 256) {
-        const int i = (int)(e % r);
-        float v = (float)((double)U[(e / r) * kW + i] * sqrt(lam[i]));
-        if (sgn[i] < 0.f) v = -v;
-        my_bad |= !isfinite(v);
-        up[e] = v;
-    }
-    for (int64_t e = tid; e < (int64_t)r * L.K; e += 256) {
-        const int i = (int)(e / L.K);
-        float v = V[(e % L.K) * kW + i];
-        if (sgn[i] < 0.f) v = -v;
-        my_bad |= !isfinite(v);
-        down[e] = v;
-    }
-    if (my_bad) atomicOr(&bad, 1);
-    __syncthreads();
-    if (bad) {
-        if (tid == 0) *L.flag() = 3;
-        return;
-    }
-    if (clamp) quantile_clamp(up, (L.N + L.K) * r, q, true, hist, sh);
+    finalize_layer<16>(L.Y(), L.V(), L.lam(), L.flag(), L.N, L.K, kW, r, q, clamp, out + L.out_off);
 }
 
 bool rank_ok(int r) { return r >= 1 && r <= 16; }

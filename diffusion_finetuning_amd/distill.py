@@ -1,8 +1,8 @@
 """`lora_distill` — lora_diffusion/cli_svd.py: a fully fine-tuned model → rank-r LoRA factors of `tuned − base`.
 
 The reference runs one full `torch.linalg.svd` per target linear (192 on SD1.5: 144 UNet + 48 CLIP-L layers).  Here every
-layer is solved at once by batched block subspace iteration with Rayleigh–Ritz in HIP kernels (csrc/distill.hip,
-DESIGN.md "svd_distill"): the difference D = float(T(W1 − W0)) is formed on load and never stored, each phase is one launch
+layer is solved at once by batched block subspace iteration with Rayleigh–Ritz in HIP kernels (csrc/distill.hip for ranks
+1–16, csrc/distill_wide.hip for ranks 17–64; DESIGN.md "svd_distill"): the difference D = float(T(W1 − W0)) is formed on load and never stored, each phase is one launch
 for all layers, converged layers leave the launch table.
 
 Contract (cli_svd.py:29-111): up = U_r·diag(S_r) [N, r], down = Vh_r [r, K], both clamped to [−hi, hi] with
@@ -29,7 +29,7 @@ UNET_TARGETS = ["CrossAttention", "Attention", "GEGLU"]  # cli_svd.py:47-48
 TEXT_TARGETS = ["CLIPAttention"]  # cli_svd.py:50
 
 _ALIGN = 256
-_STATE_ITERS, _STATE_RES, _STATE_LAM = 4, 8, 64  # per-layer workspace header (csrc/distill.hip)
+_STATE_ITERS, _STATE_RES, _STATE_LAM = 4, 8, 64  # per-layer workspace header (csrc/distill.hip, csrc/distill_wide.hip)
 
 
 def extract_linear_weights(model, target_replace_module) -> List[torch.Tensor]:
@@ -45,8 +45,9 @@ def _layer_names(model, target_replace_module) -> List[str]:
 
 def distill_lora(tuned, base, target_replace_module, rank: int = 4, clamp_quantile=0.99, *, tol: float = 1e-5,
                  max_iters: int = 200, seed: int = 0, check_every: int = 4, return_info: bool = False):
-    """Rank-`rank` factors of tuned − base for every target linear: the flat list [up0, down0, up1, down1, …] of fp32
-    device tensors (views of one slab), as cli_svd.py:66-107 builds per model.
+    """Rank-`rank` factors (1 <= rank <= 64) of tuned − base for every target linear: the flat list [up0, down0, up1,
+    down1, …] of fp32 device tensors (views of one slab), as cli_svd.py:66-107 builds per model.  Ranks up to 16 run on the
+    width-32 kernels, ranks 17–64 on the wide ones (block width 48, 64 or 80); planning, iteration and polling are the same.
 
     `clamp_quantile=None` skips the clamp (extension).  A layer is done when max_{i<=r} ‖Dᵀu_i − σ_i v_i‖ / σ_1 <= tol;
     layers still above it after `max_iters` iterations are reported with a RuntimeWarning and in info["unconverged"].
@@ -70,18 +71,19 @@ def distill_lora(tuned, base, target_replace_module, rank: int = 4, clamp_quanti
     if clamp_quantile is not None and not 0.0 <= float(clamp_quantile) <= 1.0:
         raise ValueError(f"distill_lora: clamp_quantile must be in [0, 1], got {clamp_quantile}")
     r = int(rank)
-    if r > 16:
-        raise ValueError(f"distill_lora: rank {r} > 16 is not supported")
+    if r > nat.DISTILL_MAX_RANK:
+        raise ValueError(f"distill_lora: rank {r} > {nat.DISTILL_MAX_RANK} is not supported")
     if max_iters < 1:
         raise ValueError("distill_lora: max_iters must be >= 1")
 
-    plan = _plan(w1s, w0s, r)
+    kern = nat.DistillKernels(r)
+    plan = _plan(w1s, w0s, kern)
     device, rows, ws, out, full, flag_idx = (plan[k] for k in ("device", "rows", "ws", "out", "table", "flag_idx"))
     ws_off, out_off, L = plan["ws_off"], plan["out_off"], len(rows)
     min_nk = min(min(row[2], row[3]) for row in rows)
 
     launches = 0
-    nat.distill_start(full, L, min_nk, r, int(seed), ws)
+    kern.start(full, L, min_nk, int(seed), ws)
     launches += 1
     active = list(range(L))
     table = full
@@ -90,10 +92,10 @@ def distill_lora(tuned, base, target_replace_module, rank: int = 4, clamp_quanti
         n = len(active)
         max_n = max(rows[i][2] for i in active)
         max_k = max(rows[i][3] for i in active)
-        nat.distill_diff(table, n, max_n, False, dtype, ws)
-        nat.distill_rayleigh_ritz(table, n, 1, r, tol, False, ws)
-        nat.distill_diff(table, n, max_k, True, dtype, ws)
-        nat.distill_rayleigh_ritz(table, n, 2, r, tol, last, ws)
+        kern.diff(table, n, max_n, False, dtype, ws)
+        kern.rayleigh_ritz(table, n, 1, tol, False, ws)
+        kern.diff(table, n, max_k, True, dtype, ws)
+        kern.rayleigh_ritz(table, n, 2, tol, last, ws)
         launches += 4
         if last or (it + 1) % check_every == 0:
             flags = ws.view(torch.int32)[flag_idx].cpu()
@@ -101,7 +103,7 @@ def distill_lora(tuned, base, target_replace_module, rank: int = 4, clamp_quanti
             if not active:
                 break
             table = full[torch.tensor(active, device=device)]
-    nat.distill_finalize(full, L, r, clamp_quantile, ws, out)
+    kern.finalize(full, L, clamp_quantile, ws, out)
     launches += 1
 
     flags = ws.view(torch.int32)[flag_idx].cpu().tolist()
@@ -133,8 +135,10 @@ def distill_lora(tuned, base, target_replace_module, rank: int = 4, clamp_quanti
     return loras, info
 
 
-def _plan(w1s, w0s, r: int):
-    """Device copies of the weights, the layer table, the workspace slab and the output slab of one distill_lora call."""
+def _plan(w1s, w0s, kern):
+    """Device copies of the weights, the layer table, the workspace slab and the output slab of one distill_lora call on the
+    kernel set `kern` (nat.DistillKernels)."""
+    r = kern.r
     device = nat.staging_device(*w1s, *w0s)
     w1s = [w.to(device).contiguous() for w in w1s]
     w0s = [w.to(device).contiguous() for w in w0s]
@@ -144,7 +148,7 @@ def _plan(w1s, w0s, r: int):
         ws_off.append(ws_total)
         out_off.append(out_total)
         rows.append([a.data_ptr(), b.data_ptr(), N, K, ws_total, out_total, i, 0])
-        ws_total += (nat.distill_workspace_bytes(N, K) + _ALIGN - 1) // _ALIGN * _ALIGN
+        ws_total += (kern.workspace_bytes(N, K) + _ALIGN - 1) // _ALIGN * _ALIGN
         out_total += r * (N + K)
     return {
         "device": device, "rows": rows, "ws_off": ws_off, "out_off": out_off, "weights": (w1s, w0s),

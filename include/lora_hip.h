@@ -600,7 +600,7 @@ int attn_f32_bwd(const float* Q, const float* K, const float* V, const float* O,
  * table: device memory, int64 [n_layers][8] = {W1 ptr, W0 ptr (dtype, [N,K]), N, K, workspace byte offset (256-aligned),
  * output float offset, layer index (keys the start block), 0}.  Each layer owns lora_distill_workspace_bytes(N, K) bytes of
  * `workspace` from its offset; its factors go to out[off ..] as up [N,r] then down [r,K], fp32.  r <= 16
- * (LORA_E_UNSUPPORTED above), r <= min(N,K) (LORA_E_RANK).  Sign convention (the SVD fixes none): the largest-magnitude
+ * (LORA_E_UNSUPPORTED above: ranks up to 64 run on the lora_distill_wide_* entries below), r <= min(N,K) (LORA_E_RANK).  Sign convention (the SVD fixes none): the largest-magnitude
  * entry of each down row is positive, ties to the lowest index.
  *   lora_distill_start          : resets the per-layer state, V ← orth(V₀), V₀ pseudo-random from (seed, layer index).
  *                                 min_nk = min over the table of min(N,K).
@@ -624,6 +624,29 @@ int lora_distill_rayleigh_ritz(const int64_t* table, int n_layers, int side, int
 int lora_distill_finalize(const int64_t* table, int n_layers, int r, float q, int clamp, void* workspace, float* out,
                           void* stream);
 int lora_quantile_clamp(float* x, int64_t n, float q, float* hi_out, void* stream);
+
+/*
+ * svd_distill at ranks up to 64 — lora_diffusion/cli_svd.py:71-77 slices U[:, :rank] for any rank; a full fine-tune is usually
+ * distilled at 32 or 64.  The same algorithm, table row, state header, sign convention and clamp (cli_svd.py:79-84) as the
+ * lora_distill_* entries above, at a block width W chosen from the rank: lora_distill_wide_width(r) = 48 for r <= 32,
+ * 64 for r <= 48, 80 for r <= 64 (W >= r + 16).  The workspace layout depends on W, so every entry takes r and a layer owns
+ * lora_distill_wide_workspace_bytes(N, K, r) bytes: header (λ: double[W] at +64), Ũ double[W][W] at +1280, then
+ * Y [N,W], Z [K,W], V [K,W] in fp32.  One r per workspace: the entries of one solve are called with the same r.
+ * Status, decided before any launch: LORA_E_BADARG for a null pointer, an unknown side or dtype; LORA_E_RANK for r < 1 or
+ * (start) r > min_nk; LORA_E_UNSUPPORTED for r > 64, in every entry and whatever min_nk is (the rank range is checked first).  lora_distill_wide_width returns the same codes for such r;
+ * lora_distill_wide_workspace_bytes returns 0 for them and for N < 1 or K < 1.  Ranks 1..16 are accepted here too (W = 48)
+ * but distill_lora keeps them on the width-32 entries.
+ */
+int lora_distill_wide_width(int r);
+int64_t lora_distill_wide_workspace_bytes(int64_t N, int64_t K, int r);
+int lora_distill_wide_start(const int64_t* table, int n_layers, int64_t min_nk, int r, int64_t seed, void* workspace,
+                            void* stream);
+int lora_distill_wide_diff(const int64_t* table, int n_layers, int64_t max_rows, int transpose, int dtype, int r,
+                           void* workspace, void* stream);
+int lora_distill_wide_rayleigh_ritz(const int64_t* table, int n_layers, int side, int r, double tol, int last,
+                                    void* workspace, void* stream);
+int lora_distill_wide_finalize(const int64_t* table, int n_layers, int r, float q, int clamp, void* workspace, float* out,
+                               void* stream);
 
 /*
  * Launch profiler (measurement only; off by default).  When enabled, the hot-path kernels are launched

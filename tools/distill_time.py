@@ -12,6 +12,8 @@ Reports, as one JSON line and a readable table:
   - the yardstick: the reference's loop (fp16 subtraction, .float(), torch.linalg.svd, quantile, clamp per layer) on the same GPU.
 
     python tools/distill_time.py [--rank 4] [--reps 5] [--no-yardstick]
+
+--rank takes 1..64: ranks up to 16 time the width-32 kernels, ranks 17–64 the wide ones (the JSON line carries the width).
 """
 import argparse
 import collections
@@ -91,17 +93,18 @@ def event_ms(fn, reps):
 
 
 def phases(w1s, w0s, r, reps):
-    plan = dl._plan(w1s, w0s, r)
+    kern = nat.DistillKernels(r)
+    plan = dl._plan(w1s, w0s, kern)
     t, ws, L, rows = plan["table"], plan["ws"], len(plan["rows"]), plan["rows"]
     max_n, max_k = max(x[2] for x in rows), max(x[3] for x in rows)
     min_nk = min(min(x[2], x[3]) for x in rows)
     res = {
-        "start": event_ms(lambda: nat.distill_start(t, L, min_nk, r, 0, ws), reps),
-        "diff_Y=DV": event_ms(lambda: nat.distill_diff(t, L, max_n, False, torch.float16, ws), reps),
-        "rr_left": event_ms(lambda: nat.distill_rayleigh_ritz(t, L, 1, r, 0.0, False, ws), reps),
-        "diff_Z=DtU": event_ms(lambda: nat.distill_diff(t, L, max_k, True, torch.float16, ws), reps),
-        "rr_right": event_ms(lambda: nat.distill_rayleigh_ritz(t, L, 2, r, 0.0, False, ws), reps),
-        "finalize": event_ms(lambda: nat.distill_finalize(t, L, r, 0.99, ws, plan["out"]), reps),
+        "start": event_ms(lambda: kern.start(t, L, min_nk, 0, ws), reps),
+        "diff_Y=DV": event_ms(lambda: kern.diff(t, L, max_n, False, torch.float16, ws), reps),
+        "rr_left": event_ms(lambda: kern.rayleigh_ritz(t, L, 1, 0.0, False, ws), reps),
+        "diff_Z=DtU": event_ms(lambda: kern.diff(t, L, max_k, True, torch.float16, ws), reps),
+        "rr_right": event_ms(lambda: kern.rayleigh_ritz(t, L, 2, 0.0, False, ws), reps),
+        "finalize": event_ms(lambda: kern.finalize(t, L, 0.99, ws, plan["out"]), reps),
     }
     nbytes = sum(2 * 2 * x[2] * x[3] for x in rows)
     bw = {k: nbytes / (res[k] * 1e-3) / 1e12 for k in ("diff_Y=DV", "diff_Z=DtU")}
@@ -144,7 +147,7 @@ def main():
     ap.add_argument("--no-yardstick", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    out = {"rank": a.rank, "gpu": torch.cuda.get_device_name(0)}
+    out = {"rank": a.rank, "width": nat.distill_width(a.rank), "gpu": torch.cuda.get_device_name(0)}
     for name, shapes, seed in (("unet", sd15_unet_targets(), 1), ("text_encoder", clip_l_targets(), 2)):
         w0s, w1s, fams = synth(shapes, seed, dev)
         base, tuned = model(w0s), model(w1s)
