@@ -100,6 +100,12 @@ SIGNATURES = {
     "group_norm_act_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "group_norm_act_fwd": (_i32, [_vp] * 8 + [_i32, _i32, _i32, _i32, _f32, _i32, _i32, _i32, _vp]),
     "group_norm_act_bwd": (_i32, [_vp] * 10 + [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "group_norm_act_bwd_res": (_i32, [_vp] * 11 + [_i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "residual_bias_add_supported": (_i32, [_i32, _i32, _i32, _i32]),
+    "residual_bias_add": (_i32, [_vp] * 5 + [_i32, _i32, _i32, _i32, _vp]),
+    "tokens_nchw_supported": (_i32, [_i32, _i32, _i32, _i32]),
+    "tokens_to_nchw_add": (_i32, [_vp] * 3 + [_i32, _i32, _i32, _i32, _vp]),
+    "nchw_to_tokens": (_i32, [_vp] * 2 + [_i32, _i32, _i32, _i32, _vp]),
     "add_layer_norm_max_channels": (_i32, []),
     "add_layer_norm_fwd": (_i32, [_vp] * 8 + [_i64, _i32, _f32, _i32, _vp]),
     "add_layer_norm_bwd": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _vp]),
@@ -916,6 +922,70 @@ def group_norm_act_bwd(dy, x, addend, gamma, beta, mean, rstd, groups: int, act:
                                     _ptr(da), _ptr(ws), N, C, H * W, groups, int(act), layout, dtype_code(x.dtype), _stream(x)),
            "group_norm_act_bwd")
     return dx, da
+
+
+def group_norm_act_bwd_res(dy, dh, x, addend, gamma, beta, mean, rstd, groups: int, act: bool, want_da: bool):
+    """group_norm_act_bwd for an NCHW-contiguous x with dh, the gradient that reaches x along a residual path, added into dx
+    before its one rounding; dy and dh dense like x and 16-byte aligned, dh may be None."""
+    N, C, H, W = x.shape
+    dx = torch.empty_like(x)
+    da = torch.empty((N, C), dtype=x.dtype, device=x.device) if want_da else None
+    ws = _norm_workspace(x, groups, 0, want_da)
+    _check(lib().group_norm_act_bwd_res(_ptr(dy), _ptr(dh), _ptr(x), _ptr(addend), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd),
+                                        _ptr(dx), _ptr(da), _ptr(ws), N, C, H * W, groups, int(act), dtype_code(x.dtype),
+                                        _stream(x)), "group_norm_act_bwd_res")
+    return dx, da
+
+
+def _is_dense16(t) -> bool:
+    return t.is_contiguous() and t.data_ptr() % 16 == 0
+
+
+def residual_bias_add_supported(h, res, b1, b2) -> bool:
+    """Whether csrc/trunk_edges.hip adds these: 16-bit NCHW-contiguous h and res of one shape from a 16-byte boundary, H·W a
+    multiple of 8, dense [C] biases of their type."""
+    if h.dim() != 4 or h.dtype not in (torch.float16, torch.bfloat16) or res.shape != h.shape or res.dtype != h.dtype:
+        return False
+    for b in (b1, b2):
+        if b is not None and (b.dtype != h.dtype or b.shape != h.shape[1:2] or not b.is_contiguous()):
+            return False
+    N, C, H, W = h.shape
+    return (h.numel() > 0 and _is_dense16(h) and _is_dense16(res) and
+            bool(lib().residual_bias_add_supported(N, C, H * W, dtype_code(h.dtype))))
+
+
+def residual_bias_add(h, res, b1, b2):
+    """res + h + b1[None, :, None, None] (+ b2 likewise), one pass, fp32 sum with one rounding."""
+    _require_device(h, res, b1, b2)
+    N, C, H, W = h.shape
+    out = torch.empty_like(h)
+    _check(lib().residual_bias_add(_ptr(h), _ptr(res), _ptr(b1), _ptr(b2), _ptr(out), N, C, H * W, dtype_code(h.dtype),
+                                   _stream(h)), "residual_bias_add")
+    return out
+
+
+def tokens_nchw_supported(N: int, C: int, HW: int, dtype) -> bool:
+    """Whether the transposing kernels of csrc/trunk_edges.hip cover [N, HW, C] ↔ [N, C, HW] in this dtype (no launch)."""
+    return dtype in (torch.float16, torch.bfloat16) and bool(lib().tokens_nchw_supported(N, C, HW, dtype_code(dtype)))
+
+
+def tokens_to_nchw_add(tok, res, shape):
+    """out [N,C,H,W] = tok [N, H·W, C] re-laid out (+ res, NCHW, when given); tok and res dense and 16-byte aligned."""
+    _require_device(tok, res)
+    N, C, H, W = shape
+    out = torch.empty(shape, dtype=tok.dtype, device=tok.device)
+    _check(lib().tokens_to_nchw_add(_ptr(tok), _ptr(res), _ptr(out), N, C, H * W, dtype_code(tok.dtype), _stream(tok)),
+           "tokens_to_nchw_add")
+    return out
+
+
+def nchw_to_tokens(x):
+    """tok [N, H·W, C] = x [N,C,H,W] (NCHW-contiguous, 16-byte aligned) re-laid out."""
+    _require_device(x)
+    N, C, H, W = x.shape
+    tok = torch.empty((N, H * W, C), dtype=x.dtype, device=x.device)
+    _check(lib().nchw_to_tokens(_ptr(x), _ptr(tok), N, C, H * W, dtype_code(x.dtype), _stream(x)), "nchw_to_tokens")
+    return tok
 
 
 def add_layer_norm_supported(x) -> bool:

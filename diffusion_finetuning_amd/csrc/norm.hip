@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void nchw_stats_bwd_kernel(const T* dy, const 
 template <typename T, bool SILU>
 __global__ __launch_bounds__(256) void nchw_apply_bwd_kernel(const T* dy, const T* x, const T* a, const T* gamma, const T* beta,
                                                              const float* mean_in, const float* rstd_in, T* dx, T* da,
-                                                             const float* part, int C, int HW, int G) {
+                                                             const float* part, int C, int HW, int G, const T* dh) {
     constexpr int VEC = ElemTraits<T>::kVec;
     __shared__ float st[2];
     const int ng = blockIdx.y, n = ng / G, g = ng - n * G, cpg = C / G;
@@ -204,13 +204,21 @@ __global__ __launch_bounds__(256) void nchw_apply_bwd_kernel(const T* dy, const 
         const float d = (a ? to_f32<T>(a[row0 + cl]) : 0.f) - mean;
         const int64_t off = row0 * HW + (int64_t)i * VEC;
         const Chunk<T> v = load_chunk(x + off), w = load_chunk(dy + off);
-        Chunk<T> o;
+        float r[VEC];
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float xh = (to_f32<T>(v.v[e]) + d) * rs;
             const float dz = to_f32<T>(w.v[e]) * act_grad_f<SILU>(fmaf(xh, gm, b));
-            o.v[e] = from_f32<T>(rs * (fmaf(dz, gm, -k2) - xh * k1));
+            r[e] = rs * (fmaf(dz, gm, -k2) - xh * k1);
         }
+        if (dh) {  // the gradient that reaches x along the residual path joins before the one rounding (a uniform branch)
+            const Chunk<T> u = load_chunk(dh + off);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) r[e] += to_f32<T>(u.v[e]);
+        }
+        Chunk<T> o;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) o.v[e] = from_f32<T>(r[e]);
         *reinterpret_cast<Chunk<T>*>(dx + off) = o;
     }
 }
@@ -552,8 +560,9 @@ int run_fwd(const void* x_, const void* a_, const void* gamma_, const void* beta
 
 template <typename T, bool SILU>
 int run_bwd(const void* dy_, const void* x_, const void* a_, const void* gamma_, const void* beta_, const float* mean,
-            const float* rstd, void* dx_, void* da_, void* ws, int N, int C, int HW, int G, int channels_last, hipStream_t s) {
-    const T *dy = static_cast<const T*>(dy_), *x = static_cast<const T*>(x_), *a = static_cast<const T*>(a_),
+            const float* rstd, void* dx_, void* da_, void* ws, int N, int C, int HW, int G, int channels_last, hipStream_t s,
+            const void* dh_ = nullptr) {
+    const T *dy = static_cast<const T*>(dy_), *dh = static_cast<const T*>(dh_), *x = static_cast<const T*>(x_), *a = static_cast<const T*>(a_),
             *gamma = static_cast<const T*>(gamma_), *beta = static_cast<const T*>(beta_);
     T *dx = static_cast<T*>(dx_), *da = static_cast<T*>(da_);
     float* part = static_cast<float*>(ws);
@@ -573,7 +582,7 @@ int run_bwd(const void* dy_, const void* x_, const void* a_, const void* gamma_,
         hipLaunchKernelGGL((nchw_stats_bwd_kernel<T, SILU>), dim3((rows + 3) / 4), dim3(256), 0, s, dy, x, a, gamma, beta, mean,
                            rstd, part, rows, C, HW, G);
         hipLaunchKernelGGL((nchw_apply_bwd_kernel<T, SILU>), dim3(nchw_slices(N, G, C / G * (HW / 8)), N * G), dim3(256), 0, s, dy,
-                           x, a, gamma, beta, mean, rstd, dx, da, part, C, HW, G);
+                           x, a, gamma, beta, mean, rstd, dx, da, part, C, HW, G, dh);
     }
     LORA_LAUNCH_CHECK();
     return LORA_OK;
@@ -607,22 +616,38 @@ extern "C" int group_norm_act_fwd(const void* x, const void* addend, const void*
     }
 }
 
-extern "C" int group_norm_act_bwd(const void* dy, const void* x, const void* addend, const void* gamma, const void* beta,
-                                  const float* mean, const float* rstd, void* dx, void* da, void* workspace, int N, int C, int HW,
-                                  int groups, int act, int channels_last, int dtype, void* stream) {
+namespace {
+int bwd_entry(const void* dy, const void* dh, const void* x, const void* addend, const void* gamma, const void* beta,
+              const float* mean, const float* rstd, void* dx, void* da, void* workspace, int N, int C, int HW, int groups, int act,
+              int channels_last, int dtype, void* stream) {
     if (!dy || !x || !gamma || !beta || !mean || !rstd || !dx || !workspace || (act != 0 && act != 1)) return LORA_E_BADARG;
     if (da && !addend) return LORA_E_BADARG;
     if (const int st = check_shape(N, C, HW, groups, channels_last)) return st;
-    if (!aligned16(dy) || !aligned16(x) || !aligned16(dx) || !aligned16(workspace)) return LORA_E_ALIGN;
+    if (dh && channels_last) return LORA_E_UNSUPPORTED;
+    if (!aligned16(dy) || !aligned16(dh) || !aligned16(x) || !aligned16(dx) || !aligned16(workspace)) return LORA_E_ALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (dtype) {
         case LORA_F16:
-            return act ? run_bwd<half_t, true>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s)
-                       : run_bwd<half_t, false>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s);
+            return act ? run_bwd<half_t, true>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s, dh)
+                       : run_bwd<half_t, false>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s, dh);
         case LORA_BF16:
-            return act ? run_bwd<bf16_t, true>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s)
-                       : run_bwd<bf16_t, false>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s);
+            return act ? run_bwd<bf16_t, true>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s, dh)
+                       : run_bwd<bf16_t, false>(dy, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, channels_last, s, dh);
         case LORA_F32: return LORA_E_UNSUPPORTED;
         default: return LORA_E_BADARG;
     }
+}
+}  // namespace
+
+extern "C" int group_norm_act_bwd(const void* dy, const void* x, const void* addend, const void* gamma, const void* beta,
+                                  const float* mean, const float* rstd, void* dx, void* da, void* workspace, int N, int C, int HW,
+                                  int groups, int act, int channels_last, int dtype, void* stream) {
+    return bwd_entry(dy, nullptr, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, act, channels_last, dtype,
+                     stream);
+}
+
+extern "C" int group_norm_act_bwd_res(const void* dy, const void* dh, const void* x, const void* addend, const void* gamma,
+                                      const void* beta, const float* mean, const float* rstd, void* dx, void* da, void* workspace,
+                                      int N, int C, int HW, int groups, int act, int dtype, void* stream) {
+    return bwd_entry(dy, dh, x, addend, gamma, beta, mean, rstd, dx, da, workspace, N, C, HW, groups, act, 0, dtype, stream);
 }

@@ -8,7 +8,11 @@ exactly like diffusers' `UNet2DConditionModel` does for the reference:
   * top-level registration order down_blocks, up_blocks, mid_block (pinned by the 144-entry index table of
     example_loras/lora_disney.safetensors; tests/test_finder_order.py checks it).
 Everything that is NOT the hot path (convolutions, softmax(QKᵀ)V) is stock PyTorch-ROCm; on the GPU in f16 / bf16 the
-GroupNorms run through the fused norm + addend + SiLU passes of diffusion_finetuning_amd.norm (`_norm_act` below).
+GroupNorms run through the fused norm + addend + SiLU passes of diffusion_finetuning_amd.norm (`_norm_act` below), and the
+passes at the blocks' edges that only move or add activations through its block-edge fronts: a ResNet block's tail (the biases
+of conv2 and conv_shortcut and the residual sum) is one pass, a transformer's NCHW ↔ token re-layouts run through an LDS tile
+with the exit residual added on the way, and the gradient of a block input that two branches read is joined inside the
+GroupNorm backward.  All of it sits behind `_fused_norms`.
 Weights are random-init: there are no SD checkpoints offline.
 """
 import math
@@ -95,6 +99,32 @@ def _norm_act(norm: nn.GroupNorm, x, act: bool, addend=None):
     return group_norm_act(x, norm.num_groups, norm.weight, norm.bias, norm.eps, act, addend)
 
 
+def _norm_act_res(norm: nn.GroupNorm, x, act: bool):
+    """(x handed through, act(norm(x))): what else reads x takes the first, so its gradient joins the norm's dx in one launch."""
+    from diffusion_finetuning_amd.norm import group_norm_act_res
+
+    return group_norm_act_res(x, norm.num_groups, norm.weight, norm.bias, norm.eps, act)
+
+
+def _norm_tokens(norm: nn.GroupNorm, x):
+    """(x handed through, norm(x) as tokens [B, H·W, C])."""
+    from diffusion_finetuning_amd.norm import group_norm_tokens
+
+    return group_norm_tokens(x, norm.num_groups, norm.weight, norm.bias, norm.eps)
+
+
+def _tokens_to_nchw_add(tok, res):
+    from diffusion_finetuning_amd.norm import tokens_to_nchw_add
+
+    return tokens_to_nchw_add(tok, res)
+
+
+def _residual_bias_add(h, res, b1, b2=None):
+    from diffusion_finetuning_amd.norm import residual_bias_add
+
+    return residual_bias_add(h, res, b1, b2)
+
+
 def _layer_norm(norm: nn.LayerNorm, x):
     from diffusion_finetuning_amd import norm as dnorm
 
@@ -122,6 +152,17 @@ class ResnetBlock2D(nn.Module):
         if _fused_norms(x) and type(self.conv1) is nn.Conv2d:
             # conv1's bias and the time embedding are per-(n,c) constants over the image: both ride into norm2 as its addend
             # instead of one bias pass and one broadcast-add pass over the activation
+            if type(self.conv2) is nn.Conv2d and (self.conv_shortcut is None or type(self.conv_shortcut) is nn.Conv2d):
+                # the shortcut reads the x that norm1 hands through, so its gradient joins norm1's dx; conv2 and conv_shortcut
+                # run without their biases, which go into the one pass that sums the two branches
+                xp, n = _norm_act_res(self.norm1, x, True)
+                h = F.conv2d(n, self.conv1.weight, None, padding=1)
+                n = _norm_act(self.norm2, h, True, self.time_emb_proj(F.silu(temb)) + self.conv1.bias)
+                h = F.conv2d(n, self.conv2.weight, None, padding=1)
+                if self.conv_shortcut is None:
+                    return _residual_bias_add(h, xp, self.conv2.bias)
+                return _residual_bias_add(h, F.conv2d(xp, self.conv_shortcut.weight, None), self.conv2.bias,
+                                          self.conv_shortcut.bias)
             h = F.conv2d(_norm_act(self.norm1, x, True), self.conv1.weight, None, padding=1)
             h = self.conv2(_norm_act(self.norm2, h, True, self.time_emb_proj(F.silu(temb)) + self.conv1.bias))
             return (x if self.conv_shortcut is None else self.conv_shortcut(x)) + h
@@ -236,6 +277,21 @@ class Transformer2DModel(nn.Module):
 
     def forward(self, x, context):
         b, c, h, w = x.shape
+        if _fused_norms(x):
+            # the norm writes tokens and hands x through as the residual, whose gradient joins the norm's dx; the exit brings
+            # the tokens back to NCHW and adds the residual in one pass
+            res, x = _norm_tokens(self.norm, x)
+            if self.linear_projection:
+                x = self.proj_in(x)
+            else:
+                x = F.linear(x, self.proj_in.weight.view(c, c), self.proj_in.bias)
+            for blk in self.transformer_blocks:
+                x = blk(x, context)
+            if self.linear_projection:
+                x = self.proj_out(x)
+            else:
+                x = F.linear(x, self.proj_out.weight.view(c, c), self.proj_out.bias)
+            return _tokens_to_nchw_add(x, res)
         res = x
         x = _norm_act(self.norm, x, False) if _fused_norms(x) else self.norm(x)
         if x.is_cuda and not self.linear_projection:

@@ -430,6 +430,33 @@ int group_norm_act_fwd(const void* x, const void* addend /* nullable */, const v
 int group_norm_act_bwd(const void* dy, const void* x, const void* addend /* nullable */, const void* gamma, const void* beta,
                        const float* mean, const float* rstd, void* dx, void* da /* nullable */, void* workspace, int N, int C,
                        int HW, int groups, int act, int channels_last, int dtype, void* stream);
+/* group_norm_act_bwd on NCHW tensors with the gradient that reaches x along a residual path joined in:
+ * dx = (GroupNorm's input gradient) + dh in fp32, rounded once.  dh has dx's layout and is nullable (then exactly
+ * group_norm_act_bwd with channels_last = 0); da is unaffected by it.  Same workspace, same statuses; dh 16-byte aligned. */
+int group_norm_act_bwd_res(const void* dy, const void* dh /* nullable */, const void* x, const void* addend /* nullable */,
+                           const void* gamma, const void* beta, const float* mean, const float* rstd, void* dx,
+                           void* da /* nullable */, void* workspace, int N, int C, int HW, int groups, int act, int dtype,
+                           void* stream);
+
+/*
+ * Passes at the edges of the UNet trunk's blocks that only move or add activations (trunk_edges.hip).  f16 / bf16, fp32 sums
+ * with one rounding at the store, 16-byte accesses, one launch each, no workspace, no reductions: bit-reproducible.
+ *   residual_bias_add  : out[n,c,:] = res[n,c,:] + h[n,c,:] + b1[c] (+ b2[c]) on NCHW-contiguous [N,C,HW] tensors, HW % 8 == 0;
+ *                        b1 / b2 [C] of the same dtype, b2 nullable.  out may be h or res.
+ *   tokens_to_nchw_add : out[n,c,p] = tok[n,p,c] (+ res[n,c,p]);  tok [N,HW,C] dense, res / out [N,C,HW] dense, res nullable.
+ *   nchw_to_tokens     : tok[n,p,c] = x[n,c,p].
+ *   The two re-layouts need C % 8 == 0 and HW % 8 == 0 and go through a 64 x 64 tile in LDS; out must not overlap tok / x.
+ * *_supported answer 1 / 0 for a shape and dtype without touching a device.  Statuses, decided before any launch:
+ * LORA_E_BADARG (null pointer, non-positive size, unknown dtype), LORA_E_UNSUPPORTED (f32, a shape outside the above),
+ * LORA_E_ALIGN (h, res, out, tok, x off a 16-byte boundary), in that order.
+ */
+int residual_bias_add_supported(int N, int C, int HW, int dtype);
+int residual_bias_add(const void* h, const void* res, const void* b1, const void* b2 /* nullable */, void* out, int N, int C,
+                      int HW, int dtype, void* stream);
+int tokens_nchw_supported(int N, int C, int HW, int dtype);
+int tokens_to_nchw_add(const void* tok, const void* res /* nullable */, void* out, int N, int C, int HW, int dtype,
+                       void* stream);
+int nchw_to_tokens(const void* x, void* tok, int N, int C, int HW, int dtype, void* stream);
 
 /*
  * LayerNorm of the transformer blocks with the residual add in front of it folded in (csrc/layer_norm.hip), over rows [M, C]
