@@ -5,6 +5,7 @@ tensors; safetensors = tensors `{name}:{i}:up|down` + metadata `{name}` (JSON li
 `{name}:{i}:rank`, textual-inversion embeddings stored under their token with metadata EMBED_FLAG.
 """
 import json
+import os
 from itertools import groupby
 from typing import Dict, List, Set, Tuple
 
@@ -169,6 +170,38 @@ def lerp_lora_lists(l1: List[torch.Tensor], l2: List[torch.Tensor], alpha: float
             l1[i].data = a[off:off + k].view(l1[i].shape).to(l1[i].device, copy=True)
             off += k
     return list(l1[:n])
+
+
+CHECKPOINT_KEY = "checkpoint"  # the metadata entry that holds a trainer checkpoint's scalars and layout signature (one JSON string)
+
+
+def save_checkpoint_file(path, tensors: Dict[str, torch.Tensor], meta: dict):
+    """A trainer checkpoint (`LoraTrainer.save_checkpoint`, `InversionTrainer.save_checkpoint`): one safetensors file, the
+    tensors as given (CPU), `meta` as one JSON string under CHECKPOINT_KEY.  Written to a temporary name in the target
+    directory and moved into place, so that a file already at `path` is whole at every moment, and left as it was when the
+    write fails."""
+    path = os.fspath(path)
+    tmp = os.path.join(os.path.dirname(path) or ".", f".{os.path.basename(path)}.{os.getpid()}.tmp")
+    try:
+        safe_save({k: v.contiguous() for k, v in tensors.items()}, tmp, {CHECKPOINT_KEY: json.dumps(meta)})
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def load_checkpoint_file(path) -> dict:
+    """{"meta": …, "tensors": {name: CPU tensor}} of a file `save_checkpoint_file` wrote — what the trainers' `state_dict()`
+    returns.  ValueError when the file holds no checkpoint."""
+    handle = safe_open(os.fspath(path), framework="pt", device="cpu")
+    raw = (handle.metadata() or {}).get(CHECKPOINT_KEY)
+    if raw is None:
+        raise ValueError(f"{path}: no trainer checkpoint in this file (metadata entry {CHECKPOINT_KEY!r} is missing)")
+    try:
+        meta = json.loads(raw)
+    except json.JSONDecodeError as exc:
+        raise ValueError(f"{path}: the checkpoint's metadata is not JSON ({exc})") from None
+    return {"meta": meta, "tensors": {k: handle.get_tensor(k) for k in handle.keys()}}
 
 
 def _derived_path(path: str, tag: str) -> str:

@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from . import _native as nat
 from . import step as stp
+from .formats import load_checkpoint_file, save_checkpoint_file
 from .trainer import ddpm_tables, lr_lambda
 
 TARGET_NORM = 0.4  # clip_ti_decay's target row norm (cli_lora_pti.py:333)
@@ -113,6 +114,7 @@ class InversionTrainer:
         self.V, self.D, self.P = V, D, len(ids)
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
         self.lr_lambda = lr_lambda(lr_scheduler, lr_warmup_steps, max_train_steps, lr_init=lr)
+        self._scheduler_args = (str(lr_scheduler), int(lr_warmup_steps), None if max_train_steps is None else int(max_train_steps))
         self.accum_iter, self.clip_ti_decay = int(accum_iter), bool(clip_ti_decay)
         self.v_prediction, self.capture_graph = bool(v_prediction), bool(capture_graph)
         self.device = table.device
@@ -148,6 +150,64 @@ class InversionTrainer:
     def get_last_lr(self) -> List[float]:
         """`lr_scheduler.get_last_lr()`: the rate of the last micro-step."""
         return [self.lr * float(self.lr_lambda(self.scheduler_epoch))]
+
+    # -- checkpoint and resume -------------------------------------------------------------------------
+    def _config(self) -> dict:
+        """The constructor arguments a checkpoint records (and a load compares, never restores)."""
+        name, warmup, max_steps = self._scheduler_args
+        return {"lr": self.lr, "weight_decay": self.weight_decay, "betas": [float(b) for b in self.betas], "eps": self.eps,
+                "accum_iter": self.accum_iter, "lr_scheduler": name, "lr_warmup_steps": warmup, "max_train_steps": max_steps,
+                "clip_ti_decay": self.clip_ti_decay, "v_prediction": self.v_prediction,
+                "compute_dtype": str(self.dtype).replace("torch.", "")}
+
+    def state_dict(self) -> dict:
+        """{"meta", "tensors"} like LoraTrainer's: the P placeholder rows of the table, the [P, D] gradient buffer — so a save
+        is allowed at ANY micro-step, train_inversion counts `save_steps` in micro-steps — both moments, and the three
+        counters (micro-steps: it keys the device draw; AdamW steps; scheduler epoch).  Every other row of the table is the
+        initial one and is not stored.  Raises after `close()`."""
+        if self.module is None:
+            raise RuntimeError("InversionTrainer.state_dict after close()")
+        tensors = {"rows": self.module.weight.data[self.slot_ids].cpu(), "grad": self.grad.cpu(),
+                   "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu()}
+        meta = {"format_version": stp.CHECKPOINT_VERSION, "kind": "InversionTrainer", "global_step": self.global_step,
+                "optimizer_steps": self.optimizer_steps, "scheduler_epoch": self.scheduler_epoch,
+                "placeholder_token_ids": list(self.placeholder_token_ids), "compute_dtype": str(self.dtype).replace("torch.", ""),
+                "world_size": 1, "layout": {"models": [], "dense": [[self.V, self.D]]}, "config": self._config()}
+        return {"meta": meta, "tensors": tensors}
+
+    def load_state_dict(self, sd: dict):
+        """Continue from a `state_dict()`.  All or nothing: version, kind, the placeholder ids (they must be this trainer's, in
+        this order), the table's shape, every tensor's shape, dtype and finiteness are checked first; a mismatch raises
+        ValueError and leaves the trainer as it was.  The rows are written into the module's own table and the buffers in
+        place, so a live recording is replayed by the next `step()`."""
+        if self.module is None:
+            raise RuntimeError("InversionTrainer.load_state_dict after close()")
+        meta = stp.check_checkpoint_header(sd, "InversionTrainer")
+        if meta.get("placeholder_token_ids") != list(self.placeholder_token_ids):
+            raise ValueError(f"InversionTrainer: the checkpoint's placeholder ids {meta.get('placeholder_token_ids')} are not "
+                             f"this trainer's {list(self.placeholder_token_ids)}")
+        diff = stp.layout_difference(meta.get("layout") or {}, {"models": [], "dense": [[self.V, self.D]]})
+        if diff is not None:
+            raise ValueError(f"InversionTrainer: the checkpoint does not fit this trainer — {diff}")
+        counters = stp.check_checkpoint_counters(meta, ("global_step", "optimizer_steps", "scheduler_epoch"))
+        shape = ((self.P, self.D), torch.float32)
+        tensors = sd["tensors"]
+        stp.check_checkpoint_tensors(tensors, {"rows": shape, "grad": shape, "exp_avg": shape, "exp_avg_sq": shape})
+        stp.warn_config_differences("InversionTrainer", meta.get("config"), self._config())
+        # -- validated: from here on nothing raises --
+        self.module.weight.data.index_copy_(0, self.slot_ids, tensors["rows"].to(self.device))
+        self.grad.copy_(tensors["grad"])
+        self.exp_avg.copy_(tensors["exp_avg"])
+        self.exp_avg_sq.copy_(tensors["exp_avg_sq"])
+        self.global_step, self.optimizer_steps, self.scheduler_epoch = counters
+
+    def save_checkpoint(self, path):
+        """`state_dict()` as one safetensors file, written under a temporary name and moved into place."""
+        sd = self.state_dict()
+        save_checkpoint_file(path, sd["tensors"], sd["meta"])
+
+    def load_checkpoint(self, path):
+        self.load_state_dict(load_checkpoint_file(path))
 
     # -- one micro-step ------------------------------------------------------------------------------
     def step(self, latents=None, noise=None, timesteps=None, *, input_ids, mask=None, seed: Optional[int] = None,

@@ -77,6 +77,81 @@ def loss_backward(pred, target, raw, n_inst, n_prior, prior_weight, grad_scale):
     return loss
 
 
+# -- checkpoints: what the two trainers share of validating one before anything is written ---------------------------------
+CHECKPOINT_VERSION = 1
+
+
+def check_checkpoint_header(sd, kind: str) -> dict:
+    """The metadata of a trainer's `state_dict()` after the checks that come first: it is one, of a version this code reads
+    (a newer one is refused), written by a trainer of `kind`."""
+    meta = sd.get("meta") if isinstance(sd, dict) else None
+    if not isinstance(meta, dict) or not isinstance(sd.get("tensors"), dict):
+        raise ValueError("not a trainer checkpoint: expected {'meta': {...}, 'tensors': {...}}")
+    version = meta.get("format_version")
+    if not isinstance(version, int) or isinstance(version, bool) or version < 1:
+        raise ValueError(f"checkpoint format version {version!r} is not a version number")
+    if version > CHECKPOINT_VERSION:
+        raise ValueError(f"checkpoint format version {version} is newer than this code reads ({CHECKPOINT_VERSION})")
+    if meta.get("kind") != kind:
+        raise ValueError(f"checkpoint of a {meta.get('kind')!r}, not of a {kind!r}")
+    return meta
+
+
+def layout_difference(saved, own):
+    """None when the two layout signatures agree, else one sentence naming the FIRST difference.  A signature: {"models":
+    per model the ordered list of [module name, in_features, out_features, rank], "dense": the dense tails' shapes}."""
+    s_models, o_models = saved.get("models", []), own.get("models", [])
+    for m, (s_layers, o_layers) in enumerate(zip(s_models, o_models)):
+        for i, (s, o) in enumerate(zip(s_layers, o_layers)):
+            if list(s) != list(o):
+                what = lambda l: f"{l[0]} (in {l[1]}, out {l[2]}, rank {l[3]})"
+                return f"model {m}, LoRA layer {i}: the checkpoint has {what(s)}, the trainer {what(o)}"
+        if len(s_layers) != len(o_layers):
+            longer, who = (s_layers, "checkpoint") if len(s_layers) > len(o_layers) else (o_layers, "trainer")
+            i = min(len(s_layers), len(o_layers))
+            return (f"model {m}: the checkpoint has {len(s_layers)} LoRA layers, the trainer {len(o_layers)}; the first one only "
+                    f"the {who} has is layer {i}, {longer[i][0]}")
+    if len(s_models) != len(o_models):
+        return f"the checkpoint holds LoRA layers of {len(s_models)} model(s), the trainer of {len(o_models)}"
+    s_dense, o_dense = [list(d) for d in saved.get("dense", [])], [list(d) for d in own.get("dense", [])]
+    if s_dense != o_dense:
+        return f"dense parameters: the checkpoint has shapes {s_dense}, the trainer {o_dense}"
+    return None
+
+
+def check_checkpoint_tensors(tensors, expected):
+    """`expected`: {name: (shape, dtype)}.  Every one is there with that shape and dtype, nothing else is, and every
+    floating-point one is finite."""
+    for name, (shape, dtype) in expected.items():
+        t = tensors.get(name)
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"checkpoint tensor {name!r} is missing")
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            raise ValueError(f"checkpoint tensor {name!r}: {tuple(t.shape)} {t.dtype}, expected {tuple(shape)} {dtype}")
+        if t.is_floating_point() and not bool(torch.isfinite(t).all()):
+            raise ValueError(f"checkpoint tensor {name!r} holds a non-finite value")
+    extra = sorted(set(tensors) - set(expected))
+    if extra:
+        raise ValueError(f"checkpoint tensor {extra[0]!r} is not part of this trainer's state")
+
+
+def check_checkpoint_counters(meta, names):
+    """The integer scalars `names` of the metadata, each a non-negative int."""
+    for name in names:
+        v = meta.get(name)
+        if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+            raise ValueError(f"checkpoint scalar {name!r} is {v!r}, expected a non-negative integer")
+    return [meta[name] for name in names]
+
+
+def warn_config_differences(owner: str, saved, own):
+    """Constructor arguments are the caller's and are not restored: one warning lists those the file records differently."""
+    diff = [f"{k}: checkpoint {saved[k]!r}, trainer {own[k]!r}" for k in own if k in (saved or {}) and saved[k] != own[k]]
+    if diff:
+        warnings.warn(f"{owner}.load_state_dict: the checkpoint was written with other arguments, which are NOT restored — "
+                      + "; ".join(diff))
+
+
 class StepRecorder:
     """At most one step recorded into a hipGraph, with the static buffers its kernels read.  Per step: `load` (True: the step
     must be recorded), then `record` if need be, then `replay`.  `graph` is None exactly when nothing is recorded."""

@@ -26,6 +26,7 @@ import torch.nn as nn
 from . import _native as nat
 from . import step as stp
 from .core import LoraInjectedLinear
+from .formats import load_checkpoint_file, save_checkpoint_file
 
 
 def ddpm_tables(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, device="cpu"):
@@ -576,6 +577,39 @@ class LossScaler:
                 self.scale, self.clean_steps = min(self.initial, self.scale * 2.0), 0
         return self.scale != before
 
+    def state_dict(self) -> dict:
+        """The schedule's state, the in-flight flags resolved to floats in FIFO order.  Each pending reader is called — it
+        waits on an event recorded when its step ended — and STAYS in the queue: readers give the same value every time they
+        are asked, so the scaler that saved goes on exactly as if it had not."""
+        return {"scale": self.scale, "initial": self.initial, "growth_interval": self.growth_interval,
+                "clean_steps": self.clean_steps, "inflight": [float(read()) for read in self._inflight]}
+
+    @staticmethod
+    def check_state(sd):
+        """ValueError unless `sd` is what `state_dict` returns."""
+        if not isinstance(sd, dict):
+            raise ValueError("loss scaler state: not a dict")
+        for key in ("scale", "initial"):
+            v = sd.get(key)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0.0:
+                raise ValueError(f"loss scaler state: {key} is {v!r}, expected a finite positive number")
+        for key in ("growth_interval", "clean_steps"):
+            v = sd.get(key)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"loss scaler state: {key} is {v!r}, expected a non-negative integer")
+        flags = sd.get("inflight")
+        if not isinstance(flags, list) or len(flags) > LossScaler.LAG or \
+                any(isinstance(f, bool) or not isinstance(f, (int, float)) or not math.isfinite(f) for f in flags):
+            raise ValueError(f"loss scaler state: inflight is {flags!r}, expected at most {LossScaler.LAG} finite flags")
+
+    def load_state_dict(self, sd: dict):
+        """Takes over a saved schedule.  The in-flight flags come back as constant readers in the same order, so the flag of
+        step k is still applied at the start of step k + LAG when a save and a load lie in between."""
+        self.check_state(sd)
+        self.scale, self.initial = float(sd["scale"]), float(sd["initial"])
+        self.growth_interval, self.clean_steps = int(sd["growth_interval"]), int(sd["clean_steps"])
+        self._inflight = [(lambda f=float(f): f) for f in sd["inflight"]]
+
 
 class _TokenRowsFn(torch.autograd.Function):
     """rows = table[ids] (nn.Embedding.forward of the text encoder's token table) through the HIP gather; backward hands the
@@ -709,6 +743,7 @@ class LoraTrainer:
         self.unet, self.text_encoder = unet, text_encoder
         self.early_bucket = bool(early_bucket)
         self.lr_lambda = lr_lambda(lr_scheduler, lr_warmup_steps, max_train_steps, lr_init=lr)
+        self._scheduler_args = (str(lr_scheduler), int(lr_warmup_steps), None if max_train_steps is None else int(max_train_steps))
         self.scheduler_steps_first = bool(scheduler_steps_first)
         self.scheduler_epoch = 0  # LambdaLR.last_epoch: scheduler steps taken so far
         self.scheduler_steps_per_call = int(scheduler_steps_per_call)
@@ -751,8 +786,7 @@ class LoraTrainer:
         self.scaler = LossScaler(initial, self.GROWTH_INTERVAL)
         self._warned_overflow = False
         # one pinned word + one event per step in flight (LAG + 1: the slot of step k is reused at step k + LAG + 1)
-        self._flag_slots = ([(torch.zeros(1, dtype=torch.float32).pin_memory(), torch.cuda.Event())
-                             for _ in range(LossScaler.LAG + 1)] if initial != 1.0 else None)
+        self._flag_slots = self._new_flag_slots() if initial != 1.0 else None
         self._flag_turn = 0
         self.slab.enable_packed(self.dtype)
         self.v_prediction = v_prediction
@@ -816,6 +850,10 @@ class LoraTrainer:
 
     # -- loss scale (fp16) ---------------------------------------------------------------------------
     GROWTH_INTERVAL = 2000  # torch.cuda.amp.GradScaler's default
+
+    @staticmethod
+    def _new_flag_slots():
+        return [(torch.zeros(1, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(LossScaler.LAG + 1)]
 
     def _watch_overflow(self):
         """Ship the step's overflow flag to pinned host memory without waiting for it; LossScaler.begin_step reads it
@@ -975,6 +1013,141 @@ class LoraTrainer:
                                       stp.raw_mask(mask, stp.latents_like(latents, moments)))
         self._finish_step()
         return loss
+
+    # -- checkpoint and resume ------------------------------------------------------------------------------
+    def _layout_signature(self) -> dict:
+        """Per model the ordered [module name, in_features, out_features, rank] of its slab layers, and the dense shapes."""
+        models = []
+        for model in self.slab.models:
+            name_of = {id(m): n for n, m in model.named_modules()}
+            models.append([[name_of[id(l)], l.linear.in_features, l.linear.out_features, l.lora_down.weight.shape[0]]
+                           for l in lora_layers(model)])
+        dense = [[self.token_table.V, self.token_table.D]] if self.token_table is not None else []
+        return {"models": models, "dense": dense}
+
+    def _config(self) -> dict:
+        """The constructor arguments a checkpoint records (and a load compares, never restores)."""
+        name, warmup, max_steps = self._scheduler_args
+        return {"lr": [float(g["lr"]) for g in self.opt.groups],
+                "weight_decay": [float(g.get("weight_decay", 1e-2)) for g in self.opt.groups],
+                "betas": [float(b) for b in self.opt.betas], "eps": float(self.opt.eps),
+                "max_grad_norm": float(self.opt.max_grad_norm), "gradient_accumulation_steps": self.accum,
+                "lr_scheduler": name, "lr_warmup_steps": warmup, "max_train_steps": max_steps,
+                "scheduler_steps_first": self.scheduler_steps_first, "scheduler_steps_per_call": self.scheduler_steps_per_call,
+                "v_prediction": bool(self.v_prediction),
+                "compute_dtype": str(self.dtype).replace("torch.", "")}
+
+    def state_dict(self) -> dict:
+        """Everything a continuation needs to leave the bits of the uninterrupted run, as {"meta": scalars and the layout
+        signature, "tensors": {name: CPU tensor}}: the LoRA region of the fp32 master slab and of both Adam moment slabs (slab
+        order = the `.pt` order up, down, up, …), the applied / skipped step counters, the optimizer's call count (it keys the
+        device draw of noise and timesteps), the scheduler's epoch and the loss scaler with its in-flight overflow flags.  A
+        trainable token table comes with its `active` mask and — rows that never had a gradient have exactly zero moments
+        under the row-aware AdamW, which one reduction on the device confirms — the moment rows of the active rows only; the
+        dense moments where that does not hold.  Waits for the device; never part of `step()`.  No collective: every rank may
+        call it.  Inside an accumulation window (the gradient slab holds a partial sum) it raises RuntimeError."""
+        if self._micro != 0:
+            raise RuntimeError(f"LoraTrainer: micro-batch {self._micro} of {self.accum} of an accumulation window is pending — "
+                               "a checkpoint is taken on optimizer steps only")
+        s, opt = self.slab, self.opt
+        n = s.numel
+        tensors = {"lora.params": s.params[:n].cpu(), "lora.exp_avg": opt.exp_avg[:n].cpu(),
+                   "lora.exp_avg_sq": opt.exp_avg_sq[:n].cpu(), "opt.norm": opt.norm[2:4].cpu()}
+        if self.token_table is not None:
+            tt = self.token_table
+            a, b = tt.range
+            m, v = opt.exp_avg[a:b].view(tt.V, tt.D), opt.exp_avg_sq[a:b].view(tt.V, tt.D)
+            tensors["dense.0.param"] = s.params[a:b].view(tt.V, tt.D).cpu()
+            tensors["dense.0.active"] = tt.active.cpu()
+            stray = bool((((m != 0) | (v != 0)) & (tt.active == 0)[:, None]).any().item())
+            if stray:
+                tensors["dense.0.exp_avg"], tensors["dense.0.exp_avg_sq"] = m.cpu(), v.cpu()
+            else:
+                rows = tt.active.nonzero().reshape(-1)
+                tensors["dense.0.rows"] = rows.cpu()
+                tensors["dense.0.exp_avg.rows"], tensors["dense.0.exp_avg_sq.rows"] = m[rows].cpu(), v[rows].cpu()
+        meta = {"format_version": stp.CHECKPOINT_VERSION, "kind": "LoraTrainer", "step_count": int(opt.step_count),
+                "scheduler_epoch": int(self.scheduler_epoch), "scaler": self.scaler.state_dict(),
+                "compute_dtype": str(self.dtype).replace("torch.", ""), "world_size": int(self.world),
+                "layout": self._layout_signature(), "config": self._config()}
+        return {"meta": meta, "tensors": tensors}
+
+    def load_state_dict(self, sd: dict):
+        """Continue from a `state_dict()`.  All or nothing: the version, the trainer kind, the layout signature, every tensor's
+        shape, dtype and finiteness are checked before the first write — a mismatch raises ValueError (naming the first
+        differing layer) and leaves this trainer as it was.  The writes go IN PLACE into the slab, moment, counter and `active`
+        buffers, so the Parameter views, the row-aware optimizer group and the addresses a live recording has baked in stay
+        valid: the next `step()` replays it (unless the loss scale changed — the fingerprint then asks for a new recording
+        anyway).  Constructor arguments are the caller's: those the file records differently are listed in one warning.
+        An accumulation window in progress is dropped.  No collective: under data parallelism every rank loads the same file."""
+        meta = stp.check_checkpoint_header(sd, "LoraTrainer")
+        tensors = sd["tensors"]
+        own = self._layout_signature()
+        diff = stp.layout_difference(meta.get("layout") or {}, own)
+        if diff is not None:
+            raise ValueError(f"LoraTrainer: the checkpoint does not fit this trainer — {diff}")
+        step_count, epoch = stp.check_checkpoint_counters(meta, ("step_count", "scheduler_epoch"))
+        LossScaler.check_state(meta.get("scaler"))
+        n, f32 = self.slab.numel, torch.float32
+        expected = {"lora.params": ((n,), f32), "lora.exp_avg": ((n,), f32), "lora.exp_avg_sq": ((n,), f32),
+                    "opt.norm": ((2,), f32)}
+        tt = self.token_table
+        compact = "dense.0.rows" in tensors
+        if tt is not None:
+            expected["dense.0.param"] = ((tt.V, tt.D), f32)
+            expected["dense.0.active"] = ((tt.V,), torch.uint8)
+            if compact:
+                rows = tensors["dense.0.rows"]
+                k = rows.numel() if isinstance(rows, torch.Tensor) else 0
+                expected["dense.0.rows"] = ((k,), torch.int64)
+                expected["dense.0.exp_avg.rows"] = expected["dense.0.exp_avg_sq.rows"] = ((k, tt.D), f32)
+            else:
+                expected["dense.0.exp_avg"] = expected["dense.0.exp_avg_sq"] = ((tt.V, tt.D), f32)
+        stp.check_checkpoint_tensors(tensors, expected)
+        if tt is not None and compact:
+            # (the rows are scattered on the device: an index outside the table, or one that repeats, must never get there)
+            rows = tensors["dense.0.rows"]
+            if not torch.equal(rows, tensors["dense.0.active"].nonzero().reshape(-1)):
+                raise ValueError("checkpoint tensor 'dense.0.rows' is not the list of rows that 'dense.0.active' marks")
+        stp.warn_config_differences("LoraTrainer", meta.get("config"), self._config())
+        # -- validated: from here on nothing raises --
+        s, opt, dev = self.slab, self.opt, self.device
+        s.params[:n].copy_(tensors["lora.params"])
+        opt.exp_avg[:n].copy_(tensors["lora.exp_avg"])
+        opt.exp_avg_sq[:n].copy_(tensors["lora.exp_avg_sq"])
+        opt.norm[2:4].copy_(tensors["opt.norm"])
+        if tt is not None:
+            a, b = tt.range
+            s.params[a:b].view(tt.V, tt.D).copy_(tensors["dense.0.param"])
+            tt.active.copy_(tensors["dense.0.active"])
+            for slab_moment, key in ((opt.exp_avg, "dense.0.exp_avg"), (opt.exp_avg_sq, "dense.0.exp_avg_sq")):
+                view = slab_moment[a:b].view(tt.V, tt.D)
+                if compact:
+                    view.zero_()
+                    if tensors["dense.0.rows"].numel():
+                        view.index_copy_(0, tensors["dense.0.rows"].to(dev), tensors[key + ".rows"].to(dev))
+                else:
+                    view.copy_(tensors[key])
+            tt.begin_pass()
+        opt.step_count, self.scheduler_epoch = step_count, epoch
+        self.scaler.load_state_dict(meta["scaler"])
+        if self._flag_slots is None and self.scaler.initial != 1.0:  # (a trainer built without a loss scale takes one over)
+            self._flag_slots = self._new_flag_slots()
+        self._micro = 0
+        s.zero_grad()  # (also forgets the factor-gradient problems a dropped window had deferred)
+        s.repack()
+
+    def save_checkpoint(self, path):
+        """`state_dict()` as ONE safetensors file (formats.save_checkpoint_file: scalars and signature as a JSON string in
+        the metadata, written under a temporary name and moved into place).  Raises — and writes nothing, leaving a file
+        already at `path` intact — inside an accumulation window.  Under data parallelism the caller decides which rank
+        writes, as the reference does with `is_main_process`."""
+        sd = self.state_dict()
+        save_checkpoint_file(path, sd["tensors"], sd["meta"])
+
+    def load_checkpoint(self, path):
+        """`load_state_dict` of a file `save_checkpoint` wrote.  Every data-parallel rank calls it on the same file."""
+        self.load_state_dict(load_checkpoint_file(path))
 
     # -- the same step with forward+backward replayed from a hipGraph -----------------------------------
     @property
