@@ -85,6 +85,9 @@ SIGNATURES = {
     "ddpm_posterior_prologue": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32,
                                        ctypes.c_uint64, ctypes.c_uint64, _i32, _i32, _vp]),
     "ddpm_posterior_sample": (_i32, [_vp, _i32, _vp, _vp, _i32, _i64, _f32, _vp]),
+    "ddpm_sample_init": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, ctypes.c_uint64, _i32, _vp]),
+    "ddpm_sample_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _vp]),
+    "ddpm_sample_advance": (_i32, [_vp, _i32, _vp]),
     "embed_rows_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "embed_rows_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp]),
     "lora_adamw_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
@@ -663,6 +666,66 @@ def ddpm_posterior_sample(moments, z, scale: float = 0.18215):
                                        _stream(moments)),
            "ddpm_posterior_sample")
     return x0
+
+
+class SampleState:
+    """The device buffers of one sampling run (include/lora_hip.h: ddpm_sample_*): the fp32 state `x` [B, ...], the model
+    input [rows, ...] in `dtype` and its timestep tensor [rows] (rows = 2B under guidance: the same rows twice), the cursor
+    (int32 [2]: the denoising-step index and the seed's low word, both read by the step launch from device memory), and the
+    schedule's tables.  `alloc` makes them; a caller may also hand in views of its own (tests: odd offsets)."""
+
+    def __init__(self, x, model_in, t_model, cursor, timesteps, coef, cfg: bool):
+        B, rows = x.shape[0], model_in.shape[0]
+        if rows != (2 * B if cfg else B) or model_in.shape[1:] != x.shape[1:] or t_model.shape != (rows,):
+            raise ValueError(f"sampler buffers disagree: state {tuple(x.shape)}, model input {tuple(model_in.shape)}, "
+                             f"timesteps {tuple(t_model.shape)}, guidance {cfg}")
+        S = timesteps.shape[0]
+        if (x.dtype != torch.float32 or t_model.dtype != torch.int64 or cursor.dtype != torch.int32 or cursor.numel() != 2 or
+                timesteps.dtype != torch.int64 or coef.dtype != torch.float32 or tuple(coef.shape) != (S, 3) or S < 1):
+            raise ValueError("sampler buffers: x fp32, t_model / timesteps int64, cursor int32 [2], coef fp32 [S, 3]")
+        for t in (x, model_in, t_model, timesteps, coef):
+            if not t.is_contiguous():
+                raise ValueError("sampler buffers must be contiguous")
+        _require_device(x, model_in, t_model, cursor, timesteps, coef)
+        self.x, self.model_in, self.t_model, self.cursor, self.timesteps, self.coef = x, model_in, t_model, cursor, timesteps, coef
+        self.cfg, self.B, self.per_row, self.S = bool(cfg), B, x[0].numel(), S
+
+    @classmethod
+    def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, device):
+        """`shape`: of the state, [B, C, h, w]; `timesteps` / `coef`: host or device tensors of sampler_schedule."""
+        rows = (2 if cfg else 1) * shape[0]
+        return cls(torch.empty(shape, dtype=torch.float32, device=device),
+                   torch.empty((rows, *shape[1:]), dtype=dtype, device=device),
+                   torch.empty(rows, dtype=torch.int64, device=device), torch.zeros(2, dtype=torch.int32, device=device),
+                   timesteps.to(device).contiguous(), coef.to(device).contiguous(), cfg)
+
+
+def ddpm_sample_init(st: SampleState, seed: int) -> None:
+    """x_T ~ N(0,1) (Philox stream 3, key (seed, 0)) into the state, the first model input and timestep tensor, cursor = 0."""
+    _check(lib().ddpm_sample_init(_ptr(st.x), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps), st.B,
+                                  st.per_row, st.S, int(st.cfg), int(seed) & (2**64 - 1), dtype_code(st.model_in.dtype),
+                                  _stream(st.x)),
+           "ddpm_sample_init")
+
+
+def ddpm_sample_step(st: SampleState, model_out, guidance_scale: float, z_out=None) -> None:
+    """One denoising step at the device-resident cursor (and seed): guidance, x ← a·x + b·o + σ·z in place, the next model input and
+    timestep tensor.  `model_out` [rows, ...] in the model input's dtype.  Does not move the cursor: ddpm_sample_advance."""
+    _require_device(model_out, z_out)
+    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
+        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
+                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
+    if z_out is not None and (z_out.dtype != torch.float32 or z_out.shape != st.x.shape or not z_out.is_contiguous()):
+        raise ValueError(f"z_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
+    _check(lib().ddpm_sample_step(_ptr(st.x), _ptr(model_out), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor),
+                                  _ptr(st.timesteps), _ptr(st.coef), _ptr(z_out), st.B, st.per_row, st.S, int(st.cfg),
+                                  float(guidance_scale), dtype_code(model_out.dtype), _stream(st.x)),
+           "ddpm_sample_step")
+
+
+def ddpm_sample_advance(st: SampleState) -> None:
+    """cursor += 1 (up to S), a one-thread launch behind the step that read it."""
+    _check(lib().ddpm_sample_advance(_ptr(st.cursor), st.S, _stream(st.x)), "ddpm_sample_advance")
 
 
 def embed_rows_fwd(table, ids, out_dtype: torch.dtype):

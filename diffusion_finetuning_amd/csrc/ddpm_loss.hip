@@ -596,3 +596,212 @@ extern "C" int ddpm_posterior_sample(const void* moments, int moments_dtype, con
     LORA_LAUNCH_CHECK();
     return LORA_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Latent sampler: the loop around the UNet forward of lora_diffusion/utils.py:112-163 (evaluate_pipe, guidance 5.0, 50 steps of
+// the training DDPMScheduler, cli_lora_pti.py:370-402), of the class-image generation of train_lora_dreambooth.py:512-558 and of
+// utils.py:166-214 — classifier-free guidance, the scheduler step, the variance noise and the re-assembly of the doubled model
+// input — as ONE launch per denoising step.  With SD's clip_sample=False every supported step (DDPM ancestral, DDIM with any η,
+// ε- or v-prediction) is linear in the state x and the guided model output o:
+//     o = u + g·(c − u)   (no guidance: o = out),      x ← a·x + b·o + σ·z,  z ~ N(0,1) only where σ ≠ 0
+// with (a, b, σ) per step from the host (sampling.sampler_schedule, float64 rounded once).  The step index is read from DEVICE
+// memory (`cursor[0]`, and the run's seed from `cursor[1]`), so a recorded launch serves every step and every seed of a replayed
+// hipGraph; a one-thread launch BEHIND the step advances
+// it — stream order puts it after every workgroup of the step, which have all read the cursor by then, and before the next
+// step's first.  A cursor outside [0, S) makes the step a no-op: nothing is read from the tables, nothing written.
+// Counter layout, key (seed, i) with i the denoising-step index (0 for the initial draw): element group g (4 consecutive
+// elements of the [B, per_row] state) uses counter (g, g>>32, 3, 0) for x_T and (g, g>>32, 4, 0) for the variance noise z —
+// streams of their own next to eps (0), the timesteps (1) and the posterior z (2); Box–Muller as above.  The draw depends on
+// (seed, i, B·per_row) alone: not on the dtype, the access path or guidance.
+// QUAD as in posterior_prologue_kernel: per_row % 4 == 0 and every pointer aligned to its 4-element access.
+namespace {
+
+constexpr uint32_t kStreamInit = 3u, kStreamStepNoise = 4u;
+
+struct SampleParams {
+    float* x;             // [B, per_row] fp32 state, updated in place
+    const void* out;      // model output, [rows, per_row]; rows = 2B (uncond | cond) under guidance, else B
+    void* in;             // next model input, [rows, per_row]: the new state cast, twice under guidance
+    int64_t* t_model;     // [rows] timestep tensor of the next forward
+    int* cursor;          // [2]: the denoising-step index, the seed (Philox key word) of the run
+    const int64_t* timesteps;  // [S]
+    const float* coef;         // [S, 3] = (a, b, σ)
+    float* z_out;              // nullable
+    int64_t n_total;           // B · per_row
+    int rows;
+    int S;
+    int cfg;
+    float guidance;
+    uint32_t seed;
+};
+
+__device__ __forceinline__ float sample_update(float a, float b, float sigma, float x, float o, float z) {
+#pragma clang fp contract(off)
+    const float ax = a * x, bo = b * o, sz = sigma * z;
+    return (ax + bo) + sz;
+}
+__device__ __forceinline__ float guided(float u, float c, float g) {
+#pragma clang fp contract(off)
+    const float d = c - u;
+    return u + g * d;
+}
+
+template <typename T, bool QUAD>
+__device__ __forceinline__ void store_model_input(const SampleParams& p, int64_t i0, const float* v) {
+    T* in = static_cast<T*>(p.in);
+    if constexpr (QUAD) {
+        Quad<T> q;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q.v[e] = from_f32<T>(v[e]);
+        *reinterpret_cast<Quad<T>*>(in + i0) = q;
+        if (p.cfg) *reinterpret_cast<Quad<T>*>(in + p.n_total + i0) = q;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (i0 + e >= p.n_total) break;
+            const T c = from_f32<T>(v[e]);
+            in[i0 + e] = c;
+            if (p.cfg) in[p.n_total + i0 + e] = c;
+        }
+    }
+}
+
+template <typename T, bool QUAD>
+__global__ __launch_bounds__(256) void sample_init_kernel(SampleParams p) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthreads = (int64_t)gridDim.x * 256;
+    const int64_t t0 = p.timesteps[0];
+    for (int64_t r = tid; r < p.rows; r += nthreads) p.t_model[r] = t0;
+    if (tid == 0) {
+        p.cursor[0] = 0;
+        p.cursor[1] = (int)p.seed;
+    }
+    const int64_t groups = (p.n_total + 3) >> 2;
+    for (int64_t g = tid; g < groups; g += nthreads) {
+        Quad<float> z;
+        philox_normals4((uint64_t)g, kStreamInit, p.seed, 0u, z.v);
+        const int64_t i0 = g * 4;
+        if constexpr (QUAD) {
+            *reinterpret_cast<Quad<float>*>(p.x + i0) = z;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i0 + e < p.n_total) p.x[i0 + e] = z.v[e];
+        }
+        store_model_input<T, QUAD>(p, i0, z.v);
+    }
+}
+
+template <typename T, bool QUAD>
+__global__ __launch_bounds__(256) void sample_step_kernel(SampleParams p) {
+    const int step = p.cursor[0];
+    const uint32_t seed = (uint32_t)p.cursor[1];
+    if (step < 0 || step >= p.S) return;  // (uniform over the whole launch: one replay too many touches nothing)
+    const float a = p.coef[3 * step], b = p.coef[3 * step + 1], sigma = p.coef[3 * step + 2];
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthreads = (int64_t)gridDim.x * 256;
+    const int64_t t_next = p.timesteps[step + 1 < p.S ? step + 1 : step];  // (the last step leaves its own timestep)
+    for (int64_t r = tid; r < p.rows; r += nthreads) p.t_model[r] = t_next;
+    const T* out = static_cast<const T*>(p.out);
+    const int64_t groups = (p.n_total + 3) >> 2;
+    for (int64_t g = tid; g < groups; g += nthreads) {
+        Quad<float> z;
+        if (sigma != 0.f) {
+            philox_normals4((uint64_t)g, kStreamStepNoise, seed, (uint32_t)step, z.v);
+        } else {
+            z.v[0] = z.v[1] = z.v[2] = z.v[3] = 0.f;
+        }
+        const int64_t i0 = g * 4;
+        Quad<float> xn = {};
+        if constexpr (QUAD) {
+            const Quad<float> x = *reinterpret_cast<const Quad<float>*>(p.x + i0);
+            const Quad<T> u = *reinterpret_cast<const Quad<T>*>(out + i0);
+            Quad<T> c = u;
+            if (p.cfg) c = *reinterpret_cast<const Quad<T>*>(out + p.n_total + i0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float uf = to_f32<T>(u.v[e]);
+                const float o = p.cfg ? guided(uf, to_f32<T>(c.v[e]), p.guidance) : uf;
+                xn.v[e] = sample_update(a, b, sigma, x.v[e], o, z.v[e]);
+            }
+            *reinterpret_cast<Quad<float>*>(p.x + i0) = xn;
+            if (p.z_out) *reinterpret_cast<Quad<float>*>(p.z_out + i0) = z;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = i0 + e;
+                if (i >= p.n_total) break;
+                const float uf = to_f32<T>(out[i]);
+                const float o = p.cfg ? guided(uf, to_f32<T>(out[p.n_total + i]), p.guidance) : uf;
+                xn.v[e] = sample_update(a, b, sigma, p.x[i], o, z.v[e]);
+                p.x[i] = xn.v[e];
+                if (p.z_out) p.z_out[i] = z.v[e];
+            }
+        }
+        store_model_input<T, QUAD>(p, i0, xn.v);
+    }
+}
+
+__global__ void sample_advance_kernel(int* cursor, int S) {
+    const int c = *cursor;
+    if (c >= 0 && c < S) *cursor = c + 1;  // (saturates at S: further replays stay no-ops)
+}
+
+template <typename T>
+void launch_sample(const SampleParams& p, int64_t per_row, bool init, hipStream_t s) {
+    const bool quad = (per_row % 4) == 0 && quad_aligned<float>(p.x) && quad_aligned<T>(p.out) && quad_aligned<T>(p.in) &&
+                      quad_aligned<float>(p.z_out);
+    const dim3 grid(posterior_blocks(p.n_total));
+    if (init) {
+        if (quad)
+            hipLaunchKernelGGL((sample_init_kernel<T, true>), grid, dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((sample_init_kernel<T, false>), grid, dim3(256), 0, s, p);
+    } else {
+        if (quad)
+            hipLaunchKernelGGL((sample_step_kernel<T, true>), grid, dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((sample_step_kernel<T, false>), grid, dim3(256), 0, s, p);
+    }
+}
+
+int launch_sample_dtype(const SampleParams& p, int64_t per_row, bool init, int dtype, hipStream_t s) {
+    switch (dtype) {
+        case LORA_F32: launch_sample<float>(p, per_row, init, s); break;
+        case LORA_F16: launch_sample<half_t>(p, per_row, init, s); break;
+        default: launch_sample<bf16_t>(p, per_row, init, s); break;
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+}  // namespace
+
+extern "C" int ddpm_sample_init(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps, int B,
+                                int64_t per_row, int S, int cfg, uint64_t seed, int dtype, void* stream) {
+    if (!x || !model_in || !t_model || !cursor || !timesteps || B < 1 || per_row < 1 || S < 1 || !known_dtype(dtype))
+        return LORA_E_BADARG;
+    SampleParams p{};
+    p.x = x; p.in = model_in; p.t_model = t_model; p.cursor = cursor; p.timesteps = timesteps;
+    p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = S; p.cfg = cfg ? 1 : 0; p.seed = (uint32_t)seed;
+    return launch_sample_dtype(p, per_row, true, dtype, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int ddpm_sample_step(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+                                const int64_t* timesteps, const float* coef, float* z_out, int B, int64_t per_row, int S,
+                                int cfg, float guidance_scale, int dtype, void* stream) {
+    if (!x || !model_out || !model_in || !t_model || !cursor || !timesteps || !coef || B < 1 || per_row < 1 || S < 1 ||
+        !known_dtype(dtype))
+        return LORA_E_BADARG;
+    SampleParams p{};
+    p.x = x; p.out = model_out; p.in = model_in; p.t_model = t_model; p.cursor = const_cast<int*>(cursor);
+    p.timesteps = timesteps; p.coef = coef; p.z_out = z_out;
+    p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = S; p.cfg = cfg ? 1 : 0;
+    p.guidance = guidance_scale;
+    return launch_sample_dtype(p, per_row, false, dtype, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int ddpm_sample_advance(int* cursor, int S, void* stream) {
+    if (!cursor || S < 1) return LORA_E_BADARG;
+    hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), cursor, S);
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}

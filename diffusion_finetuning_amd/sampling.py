@@ -1,0 +1,272 @@
+"""Sampling latents with the model being trained: the DDPM / DDIM loop around the UNet forward.
+
+The reference samples in three places — `evaluate_pipe(..., n_step=50)` with `guidance_scale=5.0` (lora_diffusion/utils.py:112-163)
+on a pipeline built around the TRAINING DDPMScheduler every `save_steps` (lora_diffusion/cli_lora_pti.py:370-402), the class
+images prior preservation trains on (training_scripts/train_lora_dreambooth.py:512-558; the same block in train_lora_w_ti.py:699
+and train_lora_pt_caption.py:583), and `visualize_progress` over saved checkpoints (utils.py:166-214) — each time through a
+stock diffusers pipeline.  The forward is the fused LoRA GEMMs / attention cores / fused norms of this library already; what
+is here is the loop around it: classifier-free guidance, the scheduler step, the variance noise and the re-assembly of the
+doubled model input are ONE HIP launch per denoising step (csrc/ddpm_loss.hip: ddpm_sample_step), the step index lives in
+device memory, and one denoising iteration — forward, step, cursor advance — is recorded once into a hipGraph and replayed.
+
+Every supported scheduler step is linear in the state x and the guided output o (SD's clip_sample=False, no thresholding):
+`x' = a·x + b·o + σ·z`; `sampler_schedule` computes (a, b, σ) per step in float64 on the host.  diffusers' DDPMScheduler and
+DDIMScheduler are not part of the reference tree: the formulas are restated from their published definitions, like the training
+constants of `trainer.ddpm_tables` — parity UNPINNED beyond this repository's own float64 restatement (tests/sampling_reference.py).
+Out of scope: VAE decode, prompts, PNDM / DPM-Solver, clip_sample / thresholding.
+"""
+import contextlib
+import math
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _native as nat
+from . import step as stp
+from .core import LoraInjectedLinear
+
+METHODS = ("ddpm", "ddim")
+
+
+def sampler_schedule(method: str, num_inference_steps: int, v_prediction: bool, eta: float = 0.0, num_train_timesteps: int = 1000,
+                     beta_start: float = 0.00085, beta_end: float = 0.012) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(timesteps int64 [S], coef fp32 [S, 3] = (a, b, σ) per step) of `x' = a·x + b·o + σ·z`, float64 rounded once.
+    Betas "scaled_linear" as in trainer.ddpm_tables; spacing "leading": t_i = (S−1−i)·(T//S) + offset, t_prev = t − T//S.
+    With s = √ᾱ_t, q = √(1−ᾱ_t):  ε-prediction x0 = (x − q·o)/s, ε = o;  v-prediction x0 = s·x − q·o, ε = q·x + s·o.
+      "ddpm" (ancestral, variance fixed_small; offset 0; ᾱ_p = ᾱ[t_prev], 1 below 0):  α_c = ᾱ_t/ᾱ_p, β_c = 1 − α_c,
+          x' = (√ᾱ_p·β_c/(1−ᾱ_t))·x0 + (√α_c·(1−ᾱ_p)/(1−ᾱ_t))·x + σz,  σ² = max((1−ᾱ_p)/(1−ᾱ_t)·β_c, 1e-20), σ = 0 at the last step.
+      "ddim" (offset 1, SD's steps_offset; ᾱ_p = ᾱ[t_prev], ᾱ[0] below 0):  σ = η·√((1−ᾱ_p)/(1−ᾱ_t))·√(1−ᾱ_t/ᾱ_p),
+          x' = √ᾱ_p·x0 + √(1−ᾱ_p−σ²)·ε + σz.
+    The offset is dropped where it would put t_0 past T − 1 (S·(T//S) = T, e.g. S = T): every timestep indexes the table."""
+    T, S = int(num_train_timesteps), int(num_inference_steps)
+    if method not in METHODS:
+        raise ValueError(f"unknown sampling method {method!r}: one of {METHODS}")
+    if T < 1 or S < 1 or S > T:
+        raise ValueError(f"num_inference_steps must lie in [1, num_train_timesteps = {T}]; got {S}")
+    eta = float(eta)
+    if not eta >= 0.0 or math.isinf(eta):
+        raise ValueError(f"eta must be a finite number >= 0; got {eta}")
+    betas = np.linspace(float(beta_start) ** 0.5, float(beta_end) ** 0.5, T, dtype=np.float64) ** 2
+    acp = np.cumprod(1.0 - betas)
+    ratio = T // S
+    offset = 0 if method == "ddpm" else min(1, T - 1 - (S - 1) * ratio)
+    timesteps = (S - 1 - np.arange(S, dtype=np.int64)) * ratio + offset
+    coef = np.zeros((S, 3), dtype=np.float64)
+    for i, t in enumerate(timesteps):
+        t_prev = int(t) - ratio
+        ab_t = acp[t]
+        s, q = math.sqrt(ab_t), math.sqrt(1.0 - ab_t)
+        # x0 = x0_x·x + x0_o·o,  ε = e_x·x + e_o·o
+        x0_x, x0_o, e_x, e_o = (s, -q, q, s) if v_prediction else (1.0 / s, -q / s, 0.0, 1.0)
+        if method == "ddpm":
+            ab_p = acp[t_prev] if t_prev >= 0 else 1.0
+            alpha_c = ab_t / ab_p
+            beta_c = 1.0 - alpha_c
+            c_x0 = math.sqrt(ab_p) * beta_c / (1.0 - ab_t)
+            c_x = math.sqrt(alpha_c) * (1.0 - ab_p) / (1.0 - ab_t)
+            sigma = 0.0 if i == S - 1 else math.sqrt(max((1.0 - ab_p) / (1.0 - ab_t) * beta_c, 1e-20))
+            coef[i] = (c_x0 * x0_x + c_x, c_x0 * x0_o, sigma)
+        else:
+            ab_p = acp[t_prev] if t_prev >= 0 else acp[0]
+            sigma = eta * math.sqrt((1.0 - ab_p) / (1.0 - ab_t)) * math.sqrt(1.0 - ab_t / ab_p)
+            c_x0, c_e = math.sqrt(ab_p), math.sqrt(max(1.0 - ab_p - sigma * sigma, 0.0))
+            coef[i] = (c_x0 * x0_x + c_e * e_x, c_x0 * x0_o + c_e * e_o, sigma)
+    return torch.from_numpy(timesteps.copy()), torch.from_numpy(coef.astype(np.float32))
+
+
+class _IterationRecorder(stp.StepRecorder):
+    """StepRecorder's warm-up, capture, fall-back warning and replay for a body that reads the sampler's own static buffers:
+    nothing of its training-specific `load` / input buffers is used."""
+
+    def _run(self, body):
+        return body()
+
+
+class LatentSampler:
+    """`sample(encoder_hidden_states, negative_encoder_hidden_states, seed=...)` → fp32 latents [B, C, h, w] in model space (the
+    caller divides by 0.18215 and decodes).  Defaults are evaluate_pipe's: 50 steps, guidance 5.0, the training scheduler's
+    DDPM.  `guidance_scale <= 1` or no negative conditioning: one B-row pass per step (diffusers' do_classifier_free_guidance);
+    else 2B rows, unconditional first.  Stepwise: `begin(...)`, then `step()` until it returns False, then `latents`.
+    capture_graph: one denoising iteration — UNet forward, ddpm_sample_step, ddpm_sample_advance — is recorded once per (shapes,
+    dtype, fingerprint) and replayed S times, the conditioning in a static buffer, the step index and the seed in device memory
+    (so one recording serves every step and every seed).  A failed capture warns and the sampler launches from the host from
+    then on (StepRecorder's policy).  The UNet may be driven by a LoraTrainer (slab, packed factors) or plainly injected
+    (ops.PackRegistry): the packed factors are refreshed from the fp32 masters before every run, so an optimizer step, an
+    in-place edit, `tune_lora_scale` or a `monkeypatch_*` call shows in the next sample; the trainer's own state — gradient
+    slab, recording, counters — is not touched."""
+
+    def __init__(self, unet, num_inference_steps: int = 50, guidance_scale: float = 5.0, method: str = "ddpm", eta: float = 0.0,
+                 v_prediction: bool = False, capture_graph: bool = True):
+        self.unet = unet
+        self.guidance_scale = float(guidance_scale)
+        self._schedule_args = (str(method), int(num_inference_steps), bool(v_prediction), float(eta))
+        self.timesteps, self.coef = sampler_schedule(*self._schedule_args)  # (raises for a bad method / step count / eta)
+        self.num_inference_steps = int(num_inference_steps)
+        self.capture_graph = bool(capture_graph)
+        self._recorder = _IterationRecorder("LatentSampler")
+        self._key = self._fp = self._state = self._cond = None
+        self._done = self.num_inference_steps  # nothing begun: step() has nothing to do
+        self._inside = False
+
+    # -- what a recording bakes in -------------------------------------------------------------------------------------------
+    def _refresh_packed(self, layers, dtype):
+        """The packed compute-dtype factors follow the fp32 masters: the slab's of a LoraTrainer, or the PackRegistry's of a
+        plainly injected model (both rewrite their buffers in place, so a recording stays valid)."""
+        seen = set()
+        for layer in layers:
+            sink, reg = layer.__dict__.get("_dfa_grad_sink"), layer.__dict__.get("_dfa_packreg")
+            owner = sink.slab if sink is not None else reg
+            if owner is None or id(owner) in seen:
+                continue
+            seen.add(id(owner))
+            if sink is not None:
+                owner.repack()
+            else:
+                owner.ensure(owner.modules, dtype)
+
+    def _fingerprint(self, layers):
+        """Everything a recorded iteration has baked in besides the shapes: the schedule and the guidance scale (kernel
+        arguments), per LoRA layer its identity, scale, the address of its factors and of the packed copy the kernels read (the
+        VALUES are refreshed in place: `_refresh_packed`), and the address and version of every other tensor of the model —
+        frozen weights feed the cached compute-dtype copies the kernels are handed."""
+        factors = set()
+        per_layer = []
+        for l in layers:
+            down, up = l.lora_down.weight, l.lora_up.weight
+            factors.update((id(down), id(up)))
+            packed = l.__dict__.get("_dfa_packed")
+            if packed is None and "_dfa_packreg" in l.__dict__:
+                reg = l.__dict__["_dfa_packreg"]
+                packed = None if reg.views is None or id(l) not in reg.index else reg.views[reg.index[id(l)]]
+            cache = l.__dict__.get("_dfa_cache")
+            per_layer.append((id(l), float(l.scale), down.data_ptr(), up.data_ptr(), down.dtype,
+                              0 if packed is None else packed[0].data_ptr(), 0 if cache is None else cache["w"].data_ptr()))
+        frozen = tuple((t.data_ptr(), t._version) for t in list(self.unet.parameters()) + list(self.unet.buffers())
+                       if id(t) not in factors)
+        return (self._schedule_args, self.guidance_scale, tuple(per_layer), frozen)
+
+    def _held(self):
+        """What a recording reads through addresses alone and nothing else may be keeping alive: the cached operand copies."""
+        held = []
+        for m in self.unet.modules():
+            d = m.__dict__
+            held.append(d.get("_dfa_cache"))
+            for grp in (d.get("_dfa_qkv"), (d.get("_dfa_ctx") or (None,))[0]):
+                frozen = getattr(grp, "frozen", None)
+                if frozen is not None:
+                    held.append((frozen._w, frozen._wt, getattr(frozen, "_b", None)))
+        return held
+
+    @contextlib.contextmanager
+    def _mode(self):
+        """no_grad — not inference_mode: PackRegistry and the weight caches read `_version` — and eval, restored on exit."""
+        if self._inside:
+            yield
+            return
+        was_training = self.unet.training
+        self._inside = True
+        try:
+            self.unet.eval()
+            with torch.no_grad():
+                yield
+        finally:
+            self._inside = False
+            self.unet.train(was_training)
+
+    # -- one run ---------------------------------------------------------------------------------------------------------------
+    def _iteration(self):
+        st = self._state
+        out = self.unet(st.model_in, st.t_model, self._cond).sample
+        if out.dtype != st.model_in.dtype:
+            out = out.to(st.model_in.dtype)
+        nat.ddpm_sample_step(st, out.contiguous(), self.guidance_scale)
+        nat.ddpm_sample_advance(st)
+
+    def begin(self, encoder_hidden_states, negative_encoder_hidden_states=None, *, seed: int, latent_shape=(4, 64, 64)):
+        ehs, neg = encoder_hidden_states, negative_encoder_hidden_states
+        if ehs.dim() != 3:
+            raise ValueError(f"encoder_hidden_states must be [B, L, D]; got {tuple(ehs.shape)}")
+        if neg is not None and tuple(neg.shape) != tuple(ehs.shape):
+            raise ValueError(f"negative_encoder_hidden_states {tuple(neg.shape)} does not match encoder_hidden_states "
+                             f"{tuple(ehs.shape)}: one unconditional row per conditional row")
+        latent_shape = tuple(int(n) for n in latent_shape)
+        if len(latent_shape) != 3 or min(latent_shape) < 1:
+            raise ValueError(f"latent_shape must be (C, h, w); got {latent_shape}")
+        if seed is None:
+            raise ValueError("pass a seed: the draw is Philox keyed by (seed, denoising step)")
+        nat._require_device(ehs, neg)
+        cfg = neg is not None and self.guidance_scale > 1.0
+        B = ehs.shape[0]
+        dtype = stp.compute_dtype(self.unet)
+        with self._mode():
+            layers = [m for m in self.unet.modules() if isinstance(m, LoraInjectedLinear)]
+            self._refresh_packed(layers, dtype)
+            key = (B, latent_shape, tuple(ehs.shape[1:]), cfg, dtype, ehs.device)
+            fp = self._fingerprint(layers)
+            if self._state is None or key != self._key or fp != self._fp:
+                self._recorder.drop()  # before the buffers it reads are replaced
+                self._key, self._fp = key, fp
+                self._state = nat.SampleState.alloc((B, *latent_shape), dtype, cfg, self.timesteps, self.coef, ehs.device)
+                self._cond = torch.empty(((2 if cfg else 1) * B, *ehs.shape[1:]), dtype=dtype, device=ehs.device)
+            if cfg:
+                self._cond[:B].copy_(neg)  # unconditional rows first, as the pipeline concatenates them
+                self._cond[B:].copy_(ehs)
+            else:
+                self._cond.copy_(ehs)
+            nat.ddpm_sample_init(self._state, seed)
+            if self.capture_graph and self._recorder.graph is None:
+                # the warm-up passes move the state and the cursor: the run is begun again behind them
+                if self._recorder.record(self._iteration, keep=self._held):
+                    self._fp = self._fingerprint(layers)  # (the warm-up passes built the caches whose addresses it lists)
+                else:
+                    self.capture_graph = False
+                nat.ddpm_sample_init(self._state, seed)
+        self._done = 0
+        return self
+
+    def step(self) -> bool:
+        """One denoising iteration.  True while steps remain; False from the one that completes the run on (`while s.step():
+        pass` runs all S) — a call after that launches nothing."""
+        if self._done >= self.num_inference_steps:
+            return False
+        with self._mode():
+            if self._recorder.graph is not None:
+                self._recorder.replay()
+            else:
+                self._iteration()
+        self._done += 1
+        return self._done < self.num_inference_steps
+
+    @property
+    def latents(self) -> Optional[torch.Tensor]:
+        """The fp32 state [B, C, h, w] — the sampler's own buffer, rewritten by the next step / run: clone it to keep it."""
+        return None if self._state is None else self._state.x
+
+    @property
+    def state(self):
+        """The run's device buffers (`_native.SampleState`: state, next model input and timestep tensor, cursor) — None before
+        the first `begin`."""
+        return self._state
+
+    @property
+    def conditioning(self) -> Optional[torch.Tensor]:
+        """The static conditioning buffer of the forward, [rows, L, D] in the compute dtype: unconditional rows first."""
+        return self._cond
+
+    @property
+    def replaying(self) -> bool:
+        """True while a recorded iteration serves `step()`."""
+        return self._recorder.graph is not None
+
+    def sample(self, encoder_hidden_states, negative_encoder_hidden_states=None, *, seed: int, latent_shape=(4, 64, 64),
+               callback=None) -> torch.Tensor:
+        """All S steps; `callback(i, timestep, latents)` after step i, if given (reading the latents synchronises).  Returns a
+        copy of the final state."""
+        with self._mode():
+            self.begin(encoder_hidden_states, negative_encoder_hidden_states, seed=seed, latent_shape=latent_shape)
+            for i in range(self.num_inference_steps):
+                self.step()
+                if callback is not None:
+                    callback(i, int(self.timesteps[i]), self._state.x)
+            return self._state.x.clone()

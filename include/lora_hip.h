@@ -391,6 +391,43 @@ int ddpm_posterior_sample(const void* moments, int moments_dtype, const float* z
                           float scale, void* stream);
 
 /*
+ * Latent sampler: the loop AROUND the UNet forward when one samples with the model being trained —
+ * lora_diffusion/utils.py:112-163 (evaluate_pipe: 50 steps, guidance_scale 5.0) on the pipeline cli_lora_pti.py:370-402
+ * builds around the training DDPMScheduler, the class images of training_scripts/train_lora_dreambooth.py:512-558 (the same
+ * block in train_lora_w_ti.py:699 and train_lora_pt_caption.py:583) and utils.py:166-214 (visualize_progress).  Stock, that
+ * is chunk + classifier-free guidance + scheduler.step + randn + cat + cast: some 25 tiny launches and host work per step;
+ * here one launch per step, with no host value in it that changes from step to step.
+ * With SD's clip_sample = False every supported scheduler step is linear in the state x and the guided model output o:
+ *     o  = u + g·(c − u)             cfg != 0: model_out [2B, per_row] = uncond rows | cond rows;  cfg == 0: o = model_out [B, per_row]
+ *     x ← a·x + b·o + σ·z            (a, b, σ) = coef[i], z ~ N(0,1) drawn only where σ != 0
+ * coef fp32 [S, 3] and timesteps int64 [S] come from the host (sampling.sampler_schedule: diffusers' DDPMScheduler /
+ * DDIMScheduler are not vendored in the reference — restated from their published definitions in float64, parity unpinned,
+ * like ddpm_add_noise above).  All arithmetic fp32, every product rounded on its own.
+ *   ddpm_sample_init : x = x_T ~ N(0,1) fp32 [B, per_row]; model_in [rows, per_row] in `dtype` = x cast (rows = 2B under cfg:
+ *       the same rows twice; else B); t_model int64 [rows] = timesteps[0]; cursor (int32 [2], device) = {0, seed's low word}.
+ *   ddpm_sample_step : i = cursor[0] and the seed = cursor[1], read from DEVICE memory — a recorded launch serves every step
+ *       and every seed.  i outside [0, S): nothing is read from the tables and nothing
+ *       written (one replay too many is a no-op).  Else the update above on x in place, model_in = the NEW x cast (twice
+ *       under cfg) and t_model = timesteps[min(i + 1, S − 1)] — the next forward's inputs, so no "prepare" launch exists;
+ *       z_out (nullable, fp32 [B, per_row]) gets the draw, zeros where σ == 0.  model_out is read in `dtype`.
+ *   ddpm_sample_advance : cursor[0] = i + 1 for i in [0, S), one thread.  A launch of its own BEHIND the step: stream order (an
+ *       edge in a captured graph) puts it after every workgroup of that step — all of which have read the cursor — and
+ *       before the first of the next.
+ * Counter layout (Philox4x32-10, key (seed, i); i = 0 for x_T): element group g = 4 consecutive elements of [B, per_row] uses
+ * counter (g, g>>32, 3, 0) for x_T and (g, g>>32, 4, 0) for z — streams of their own next to eps (0), t (1) and the posterior
+ * z (2), same Box–Muller.  For equal (seed, i, B, per_row) the draw does not depend on dtype, access path or cfg.
+ * 16-byte (fp32) / 8-byte (16-bit) accesses when per_row % 4 == 0 and every pointer is aligned to 4 of its elements, element
+ * by element otherwise.  LORA_E_BADARG for a null pointer (z_out excepted), an unknown dtype, B, per_row or S < 1 — before
+ * any HIP call.  No workspace, nothing retained, capturable.
+ */
+int ddpm_sample_init(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps, int B,
+                     int64_t per_row, int S, int cfg, uint64_t seed, int dtype, void* stream);
+int ddpm_sample_step(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+                     const int64_t* timesteps, const float* coef, float* z_out /* nullable */, int B, int64_t per_row,
+                     int S, int cfg, float guidance_scale, int dtype, void* stream);
+int ddpm_sample_advance(int* cursor, int S, void* stream);
+
+/*
  * The two ops sandwiched by the hot path inside a transformer block, as streaming kernels.
  *   geglu_gate_fwd : out[M,C]  = h · gelu(g)  with [h | g] = y[M,2C], exact (erf) gelu — the body of diffusers'
  *                    GEGLU.forward, the caller of the `proj` LoraInjectedLinear (target class "GEGLU", lora.py:53).
