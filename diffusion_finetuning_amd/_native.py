@@ -88,6 +88,7 @@ SIGNATURES = {
     "ddpm_sample_init": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, ctypes.c_uint64, _i32, _vp]),
     "ddpm_sample_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _vp]),
     "ddpm_sample_advance": (_i32, [_vp, _i32, _vp]),
+    "ddpm_sample_multistep": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _vp]),
     "embed_rows_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "embed_rows_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp]),
     "lora_adamw_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
@@ -726,6 +727,60 @@ def ddpm_sample_step(st: SampleState, model_out, guidance_scale: float, z_out=No
 def ddpm_sample_advance(st: SampleState) -> None:
     """cursor += 1 (up to S), a one-thread launch behind the step that read it."""
     _check(lib().ddpm_sample_advance(_ptr(st.cursor), st.S, _stream(st.x)), "ddpm_sample_advance")
+
+
+class MultistepState(SampleState):
+    """SampleState for the linear multistep methods (include/lora_hip.h: ddpm_sample_multistep): next to its buffers the saved
+    state `xs` (fp32, like x), the history ring `hist` (fp32 [4, B, ...]), `coef` fp32 [I, 7] = (p, q, a, c0..c3) and `plan`
+    int32 [I, 5] = (w, s1, s2, s3, flags) of sampling.multistep_schedule.  `S` is I, the number of model evaluations, so
+    ddpm_sample_init and ddpm_sample_advance serve it as they are.  `xs` and `hist` need no clearing."""
+
+    def __init__(self, x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan, cfg: bool):
+        B, rows = x.shape[0], model_in.shape[0]
+        if (rows != (2 * B if cfg else B) or model_in.shape[1:] != x.shape[1:] or t_model.shape != (rows,) or
+                xs.shape != x.shape or tuple(hist.shape) != (4, *x.shape)):
+            raise ValueError(f"sampler buffers disagree: state {tuple(x.shape)}, saved state {tuple(xs.shape)}, history "
+                             f"{tuple(hist.shape)}, model input {tuple(model_in.shape)}, timesteps {tuple(t_model.shape)}, "
+                             f"guidance {cfg}")
+        n = timesteps.shape[0]
+        if (x.dtype != torch.float32 or xs.dtype != torch.float32 or hist.dtype != torch.float32 or
+                t_model.dtype != torch.int64 or cursor.dtype != torch.int32 or cursor.numel() != 2 or
+                timesteps.dtype != torch.int64 or coef.dtype != torch.float32 or tuple(coef.shape) != (n, 7) or
+                plan.dtype != torch.int32 or tuple(plan.shape) != (n, 5) or n < 1):
+            raise ValueError("sampler buffers: x / xs / hist fp32, t_model / timesteps int64, cursor int32 [2], coef fp32 "
+                             "[I, 7], plan int32 [I, 5]")
+        for t in (x, xs, hist, model_in, t_model, timesteps, coef, plan):
+            if not t.is_contiguous():
+                raise ValueError("sampler buffers must be contiguous")
+        _require_device(x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan)
+        self.x, self.model_in, self.t_model, self.cursor, self.timesteps, self.coef = x, model_in, t_model, cursor, timesteps, coef
+        self.xs, self.hist, self.plan = xs, hist, plan
+        self.cfg, self.B, self.per_row, self.S = bool(cfg), B, x[0].numel(), n
+
+    @classmethod
+    def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, plan, device):
+        """`shape`: of the state, [B, C, h, w]; `timesteps` / `coef` / `plan`: host or device tensors of multistep_schedule."""
+        rows = (2 if cfg else 1) * shape[0]
+        return cls(torch.empty(shape, dtype=torch.float32, device=device), torch.empty(shape, dtype=torch.float32, device=device),
+                   torch.empty((4, *shape), dtype=torch.float32, device=device),
+                   torch.empty((rows, *shape[1:]), dtype=dtype, device=device),
+                   torch.empty(rows, dtype=torch.int64, device=device), torch.zeros(2, dtype=torch.int32, device=device),
+                   timesteps.to(device).contiguous(), coef.to(device).contiguous(), plan.to(device).contiguous(), cfg)
+
+
+def ddpm_sample_multistep(st: MultistepState, model_out, guidance_scale: float) -> None:
+    """One multistep iteration at the device-resident cursor: guidance, h = p·x + q·o, x ← a·base + c0·h + Σ c_k·H[s_k] in
+    place, the saved state and the pushed history slot as plan[i] says, the next model input and timestep tensor.  `model_out`
+    [rows, ...] in the model input's dtype.  Does not move the cursor: ddpm_sample_advance."""
+    _require_device(model_out)
+    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
+        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
+                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
+    _check(lib().ddpm_sample_multistep(_ptr(st.x), _ptr(st.xs), _ptr(st.hist), _ptr(model_out), _ptr(st.model_in),
+                                       _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps), _ptr(st.coef), _ptr(st.plan),
+                                       st.B, st.per_row, st.S, int(st.cfg), float(guidance_scale),
+                                       dtype_code(model_out.dtype), _stream(st.x)),
+           "ddpm_sample_multistep")
 
 
 def embed_rows_fwd(table, ids, out_dtype: torch.dtype):

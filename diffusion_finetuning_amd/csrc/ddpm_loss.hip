@@ -773,7 +773,143 @@ int launch_sample_dtype(const SampleParams& p, int64_t per_row, bool init, int d
     return LORA_OK;
 }
 
+// Linear multistep step (PLMS = PNDM with skip_prk_steps, the scheduler of the class-image pipeline of
+// train_lora_dreambooth.py:512-558 and of visualize_progress, utils.py:191-211; DPM-Solver++(2M)).  Per iteration i = cursor[0]:
+//     h    = p·x + q·o                          the quantity the method keeps history of (o guided as above)
+//     base = USE_SAVED ? xs : x
+//     x'   = a·base + c0·h + c1·H[s1] + c2·H[s2] + c3·H[s3]          summed left to right, every product rounded on its own
+//     SAVE: xs ← x (the state before the update);   PUSH: H[w] ← h;   x ← x'
+// (p, q, a, c0..c3) = coef[i] and (w, s1, s2, s3, flags) = plan[i] come from the host (sampling.multistep_schedule), which knows
+// the ring's whole future: no ring arithmetic here.  A term whose coefficient is exactly 0 is neither loaded nor added — the
+// history slots and xs are uninitialised memory during warm-up and 0·NaN must not reach the state; the branch is uniform over
+// the launch.  Each thread reads and writes its own elements of x, xs and H[*] only, every read before the first write.
+constexpr int kMultistepPush = 1, kMultistepSave = 2, kMultistepUseSaved = 4;
+
+struct MultistepParams {
+    SampleParams s;   // x, out, in, t_model, cursor, timesteps, coef = [I, 7], n_total, rows, S = I, cfg, guidance
+    float* xs;        // [B, per_row] fp32: the saved state
+    float* hist;      // [4, B·per_row] fp32: the history ring
+    const int* plan;  // [I, 5]
+};
+
+__device__ __forceinline__ float multistep_history(float p, float q, float x, float o) {
+#pragma clang fp contract(off)
+    const float px = p * x, qo = q * o;
+    return px + qo;
+}
+__device__ __forceinline__ float multistep_update(float a, float c0, float c1, float c2, float c3, float base, float h, float h1,
+                                                  float h2, float h3) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+    if (a != 0.f) acc = a * base;
+    if (c0 != 0.f) { const float t = c0 * h; acc = acc + t; }
+    if (c1 != 0.f) { const float t = c1 * h1; acc = acc + t; }
+    if (c2 != 0.f) { const float t = c2 * h2; acc = acc + t; }
+    if (c3 != 0.f) { const float t = c3 * h3; acc = acc + t; }
+    return acc;
+}
+
+template <typename T, bool QUAD>
+__global__ __launch_bounds__(256) void sample_multistep_kernel(MultistepParams m) {
+    const SampleParams& p = m.s;
+    const int it = p.cursor[0];
+    if (it < 0 || it >= p.S) return;  // (uniform over the whole launch: one replay too many touches nothing)
+    const float* cf = p.coef + 7 * it;
+    const float kp = cf[0], kq = cf[1], a = cf[2], c0 = cf[3], c1 = cf[4], c2 = cf[5], c3 = cf[6];
+    const int* pl = m.plan + 5 * it;
+    const int flags = pl[4];
+    // (slot numbers masked to the ring: a wrong plan reads a wrong slot, never memory outside the ring)
+    float* hw = m.hist + (int64_t)(pl[0] & 3) * p.n_total;
+    const float* hs1 = m.hist + (int64_t)(pl[1] & 3) * p.n_total;
+    const float* hs2 = m.hist + (int64_t)(pl[2] & 3) * p.n_total;
+    const float* hs3 = m.hist + (int64_t)(pl[3] & 3) * p.n_total;
+    const bool push = (flags & kMultistepPush) != 0, save = (flags & kMultistepSave) != 0;
+    const bool saved_base = (flags & kMultistepUseSaved) != 0 && a != 0.f;
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthreads = (int64_t)gridDim.x * 256;
+    const int64_t t_next = p.timesteps[it + 1 < p.S ? it + 1 : it];
+    for (int64_t r = tid; r < p.rows; r += nthreads) p.t_model[r] = t_next;
+    const T* out = static_cast<const T*>(p.out);
+    const int64_t groups = (p.n_total + 3) >> 2;
+    for (int64_t g = tid; g < groups; g += nthreads) {
+        const int64_t i0 = g * 4;
+        Quad<float> xn = {};
+        if constexpr (QUAD) {
+            const Quad<float> x = *reinterpret_cast<const Quad<float>*>(p.x + i0);
+            const Quad<T> u = *reinterpret_cast<const Quad<T>*>(out + i0);
+            Quad<T> c = u;
+            if (p.cfg) c = *reinterpret_cast<const Quad<T>*>(out + p.n_total + i0);
+            Quad<float> base = x, h1 = {}, h2 = {}, h3 = {}, h;
+            if (saved_base) base = *reinterpret_cast<const Quad<float>*>(m.xs + i0);
+            if (c1 != 0.f) h1 = *reinterpret_cast<const Quad<float>*>(hs1 + i0);
+            if (c2 != 0.f) h2 = *reinterpret_cast<const Quad<float>*>(hs2 + i0);
+            if (c3 != 0.f) h3 = *reinterpret_cast<const Quad<float>*>(hs3 + i0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float uf = to_f32<T>(u.v[e]);
+                const float o = p.cfg ? guided(uf, to_f32<T>(c.v[e]), p.guidance) : uf;
+                h.v[e] = multistep_history(kp, kq, x.v[e], o);
+                xn.v[e] = multistep_update(a, c0, c1, c2, c3, base.v[e], h.v[e], h1.v[e], h2.v[e], h3.v[e]);
+            }
+            if (save) *reinterpret_cast<Quad<float>*>(m.xs + i0) = x;
+            if (push) *reinterpret_cast<Quad<float>*>(hw + i0) = h;
+            *reinterpret_cast<Quad<float>*>(p.x + i0) = xn;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = i0 + e;
+                if (i >= p.n_total) break;
+                const float x = p.x[i];
+                const float uf = to_f32<T>(out[i]);
+                const float o = p.cfg ? guided(uf, to_f32<T>(out[p.n_total + i]), p.guidance) : uf;
+                const float base = saved_base ? m.xs[i] : x;
+                const float h1 = c1 != 0.f ? hs1[i] : 0.f, h2 = c2 != 0.f ? hs2[i] : 0.f, h3 = c3 != 0.f ? hs3[i] : 0.f;
+                const float h = multistep_history(kp, kq, x, o);
+                xn.v[e] = multistep_update(a, c0, c1, c2, c3, base, h, h1, h2, h3);
+                if (save) m.xs[i] = x;
+                if (push) hw[i] = h;
+                p.x[i] = xn.v[e];
+            }
+        }
+        store_model_input<T, QUAD>(p, i0, xn.v);
+    }
+}
+
+template <typename T>
+void launch_multistep(const MultistepParams& m, int64_t per_row, hipStream_t s) {
+    const SampleParams& p = m.s;
+    const bool quad = (per_row % 4) == 0 && quad_aligned<float>(p.x) && quad_aligned<T>(p.out) && quad_aligned<T>(p.in) &&
+                      quad_aligned<float>(m.xs) && quad_aligned<float>(m.hist);  // (n_total % 4 == 0: every slot as hist)
+    const dim3 grid(posterior_blocks(p.n_total));
+    if (quad)
+        hipLaunchKernelGGL((sample_multistep_kernel<T, true>), grid, dim3(256), 0, s, m);
+    else
+        hipLaunchKernelGGL((sample_multistep_kernel<T, false>), grid, dim3(256), 0, s, m);
+}
+
 }  // namespace
+
+extern "C" int ddpm_sample_multistep(float* x, float* xs, float* hist, const void* model_out, void* model_in, int64_t* t_model,
+                                     const int* cursor, const int64_t* timesteps, const float* coef, const int* plan, int B,
+                                     int64_t per_row, int I, int cfg, float guidance_scale, int dtype, void* stream) {
+    if (!x || !xs || !hist || !model_out || !model_in || !t_model || !cursor || !timesteps || !coef || !plan || B < 1 ||
+        per_row < 1 || I < 1 || !known_dtype(dtype))
+        return LORA_E_BADARG;
+    MultistepParams m{};
+    SampleParams& p = m.s;
+    p.x = x; p.out = model_out; p.in = model_in; p.t_model = t_model; p.cursor = const_cast<int*>(cursor);
+    p.timesteps = timesteps; p.coef = coef;
+    p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = I; p.cfg = cfg ? 1 : 0;
+    p.guidance = guidance_scale;
+    m.xs = xs; m.hist = hist; m.plan = plan;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case LORA_F32: launch_multistep<float>(m, per_row, s); break;
+        case LORA_F16: launch_multistep<half_t>(m, per_row, s); break;
+        default: launch_multistep<bf16_t>(m, per_row, s); break;
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
 
 extern "C" int ddpm_sample_init(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps, int B,
                                 int64_t per_row, int S, int cfg, uint64_t seed, int dtype, void* stream) {

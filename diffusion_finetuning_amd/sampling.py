@@ -1,4 +1,4 @@
-"""Sampling latents with the model being trained: the DDPM / DDIM loop around the UNet forward.
+"""Sampling latents with the model being trained: the DDPM / DDIM / PLMS / DPM-Solver++(2M) loop around the UNet forward.
 
 The reference samples in three places — `evaluate_pipe(..., n_step=50)` with `guidance_scale=5.0` (lora_diffusion/utils.py:112-163)
 on a pipeline built around the TRAINING DDPMScheduler every `save_steps` (lora_diffusion/cli_lora_pti.py:370-402), the class
@@ -13,7 +13,17 @@ Every supported scheduler step is linear in the state x and the guided output o 
 `x' = a·x + b·o + σ·z`; `sampler_schedule` computes (a, b, σ) per step in float64 on the host.  diffusers' DDPMScheduler and
 DDIMScheduler are not part of the reference tree: the formulas are restated from their published definitions, like the training
 constants of `trainer.ddpm_tables` — parity UNPINNED beyond this repository's own float64 restatement (tests/sampling_reference.py).
-Out of scope: VAE decode, prompts, PNDM / DPM-Solver, clip_sample / thresholding.
+
+The class images (train_lora_dreambooth.py:512-558, train_lora_w_ti.py:675-699, train_lora_pt_caption.py:559-583) and
+`visualize_progress` (utils.py:191-211) come from `StableDiffusionPipeline.from_pretrained` with the model's OWN scheduler —
+for SD 1.x PNDM run as PLMS — and a preview during training is usually a second-order solver at 20 steps.  Both are linear
+multistep methods: `h = p·x + q·o; x' = a·base + c0·h + c1·H[s1] + c2·H[s2] + c3·H[s3]` with a ring H of earlier h and a saved
+state; `multistep_schedule` computes the coefficients and the ring's plan on the host, ddpm_sample_multistep is the one launch
+per iteration, and history, plan and coefficients live in device memory, indexed by the same device-resident cursor.  PNDM and
+DPM-Solver++ are restated from their papers (Liu et al. 2022; Lu et al. 2022), parity UNPINNED in the same sense
+(tests/multistep_reference.py).
+Out of scope: VAE decode, prompts, clip_sample / thresholding, image-to-image starts, PRK steps, Euler / Heun, the SDE variants,
+Karras sigmas.
 """
 import contextlib
 import math
@@ -27,6 +37,8 @@ from . import step as stp
 from .core import LoraInjectedLinear
 
 METHODS = ("ddpm", "ddim")
+MULTISTEP_METHODS = ("plms", "dpmpp_2m")
+PUSH, SAVE, USE_SAVED = 1, 2, 4  # plan flags of ddpm_sample_multistep (include/lora_hip.h)
 
 
 def sampler_schedule(method: str, num_inference_steps: int, v_prediction: bool, eta: float = 0.0, num_train_timesteps: int = 1000,
@@ -75,6 +87,97 @@ def sampler_schedule(method: str, num_inference_steps: int, v_prediction: bool, 
     return torch.from_numpy(timesteps.copy()), torch.from_numpy(coef.astype(np.float32))
 
 
+_AB_WEIGHTS = ((1.0,), (1.5, -0.5), (23.0 / 12.0, -16.0 / 12.0, 5.0 / 12.0), (55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0))
+
+
+def multistep_schedule(method: str, num_inference_steps: int, v_prediction: bool, num_train_timesteps: int = 1000,
+                       beta_start: float = 0.00085, beta_end: float = 0.012,
+                       coef_dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(timesteps int64 [I], coef fp32 [I, 7] = (p, q, a, c0, c1, c2, c3), plan int32 [I, 5] = (w, s1, s2, s3, flags)) of
+        h = p·x + q·o;  base = xs if USE_SAVED else x;  x' = a·base + c0·h + c1·H[s1] + c2·H[s2] + c3·H[s3];
+        SAVE: xs ← x;  PUSH: H[w] ← h
+    for the I model evaluations of a run — float64 rounded once (`coef_dtype=torch.float64`: not rounded).  Betas and T as in
+    `sampler_schedule`; the grid is its "ddim" grid, t_j = j·(T//S) + offset with SD's steps_offset = 1 where the table has
+    room, and ᾱ_prev = ᾱ[0] below timestep 0 (set_alpha_to_one = False).  The k-th push goes to slot k mod 4, s_k names the
+    slot of k pushes ago; the coefficient of history that does not exist yet is exactly 0 (the kernel then reads nothing).
+      "plms": PNDM with skip_prk_steps (Liu et al. 2022) as SD's pipeline runs it.  The transfer is DDIM's η = 0 step,
+          φ(x, e, t, t') = √(ᾱ_t'/ᾱ_t)·x − (ᾱ_t' − ᾱ_t)·e / (ᾱ_t·√(1−ᾱ_t') + √(ᾱ_t·(1−ᾱ_t)·ᾱ_t')),
+          history holds the raw guided output (p = 0, q = 1), I = S + 1 for S ≥ 2 (S = 1: one first-order step) and the
+          timesteps are t_{S−1}, t_{S−2}, t_{S−2}, t_{S−3}, …, t_0.  Iteration 0: e = o, pushed, x saved,
+          t_{S−1} → t_{S−2}; iteration 1 (the corrected first step): e = (o + e_1)/2, NOT pushed, base = the saved x,
+          t_{S−1} → t_{S−2} again; then every output is pushed and e = (3e_0 − e_1)/2, (23e_0 − 16e_1 + 5e_2)/12,
+          (55e_0 − 59e_1 + 37e_2 − 9e_3)/24 from iteration 4 on.  v-prediction converts AFTER the combination, with the base
+          sample at the transfer's t: e ← √ᾱ_t·e + √(1−ᾱ_t)·base — the pipeline's behaviour, folded into a and the c_k.
+      "dpmpp_2m": DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2: data prediction, midpoint form).  α = √ᾱ, σ = √(1−ᾱ),
+          λ = ln(α/σ); history holds x0 = p·x + q·o (ε: p = 1/α_s, q = −σ_s/α_s; v: p = α_s, q = −σ_s); I = S, every
+          iteration pushes.  Stepping s → t, h = λ_t − λ_s: the first iteration, and the last when S < 15 (lower-order final), is
+          x_t = (σ_t/σ_s)·x − α_t·(e^{−h} − 1)·x0_s; the others, with r = h_prev/h,
+          x_t = (σ_t/σ_s)·x − α_t·(e^{−h} − 1)·[(1 + 1/(2r))·x0_s − (1/(2r))·x0_{s−1}].
+    diffusers is not part of the reference tree: both are restated from the papers and from the pipeline's published
+    behaviour, parity UNPINNED beyond this repository's own stateful float64 restatement (tests/multistep_reference.py)."""
+    T, S = int(num_train_timesteps), int(num_inference_steps)
+    if method not in MULTISTEP_METHODS:
+        raise ValueError(f"unknown multistep sampling method {method!r}: one of {MULTISTEP_METHODS}")
+    if T < 1 or S < 1 or S > T:
+        raise ValueError(f"num_inference_steps must lie in [1, num_train_timesteps = {T}]; got {S}")
+    if coef_dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"coef_dtype must be torch.float32 or torch.float64; got {coef_dtype}")
+    betas = np.linspace(float(beta_start) ** 0.5, float(beta_end) ** 0.5, T, dtype=np.float64) ** 2
+    acp = np.cumprod(1.0 - betas)
+    ratio = T // S
+    offset = min(1, T - 1 - (S - 1) * ratio)
+    grid = [(S - 1 - j) * ratio + offset for j in range(S)]  # descending: grid[0] = t_{S−1}
+
+    def ab(t):
+        return float(acp[t]) if t >= 0 else float(acp[0])
+
+    if method == "plms":
+        # (model timestep, transfer's t, pushes before this iteration, pushed?) per iteration
+        its = [(grid[0], grid[0], 0, True)]
+        if S >= 2:
+            its.append((grid[1], grid[0], 1, False))
+            its += [(grid[j], grid[j], j, True) for j in range(1, S)]
+    else:
+        its = [(t, t, j, True) for j, t in enumerate(grid)]
+    n_it = len(its)
+    timesteps = np.array([it[0] for it in its], dtype=np.int64)
+    coef = np.zeros((n_it, 7), dtype=np.float64)
+    plan = np.zeros((n_it, 5), dtype=np.int32)
+    lam = lambda a_bar: 0.5 * math.log(a_bar / (1.0 - a_bar))  # noqa: E731  (ln(α/σ))
+    for i, (_, t, pushed, push) in enumerate(its):
+        ab_t, ab_p = ab(t), ab(t - ratio)
+        cur = pushed % 4  # the slot this iteration's h takes if it is pushed: s_k counts back from it
+        plan[i, 0] = cur
+        plan[i, 1:4] = [(cur - k) % 4 for k in (1, 2, 3)]
+        if method == "plms":
+            if i == 1 and not push:
+                weights = (0.5, 0.5)
+            else:
+                weights = _AB_WEIGHTS[min(pushed, 3)]
+            phi_x = math.sqrt(ab_p / ab_t)
+            phi_e = (ab_p - ab_t) / (ab_t * math.sqrt(1.0 - ab_p) + math.sqrt(ab_t * (1.0 - ab_t) * ab_p))
+            # v-prediction: e ← √ᾱ_t·e + √(1−ᾱ_t)·base after the combination
+            e_e, e_base = (math.sqrt(ab_t), math.sqrt(1.0 - ab_t)) if v_prediction else (1.0, 0.0)
+            coef[i, 0], coef[i, 1] = 0.0, 1.0
+            coef[i, 2] = phi_x - phi_e * e_base
+            coef[i, 3:3 + len(weights)] = [-phi_e * e_e * w for w in weights]
+            plan[i, 4] = (PUSH | SAVE) if i == 0 else ((USE_SAVED if i == 1 else 0) | (PUSH if push else 0))
+        else:
+            a_s, s_s, a_t, s_t = math.sqrt(ab_t), math.sqrt(1.0 - ab_t), math.sqrt(ab_p), math.sqrt(1.0 - ab_p)
+            h = lam(ab_p) - lam(ab_t)
+            coef[i, 0], coef[i, 1] = (a_s, -s_s) if v_prediction else (1.0 / a_s, -s_s / a_s)
+            coef[i, 2] = s_t / s_s
+            c_d = -a_t * math.expm1(-h)
+            if i == 0 or (i == n_it - 1 and S < 15) or h == 0.0:  # (h = 0: the step from t = 0 where the offset has no room)
+                coef[i, 3] = c_d
+            else:
+                r = (lam(ab_t) - lam(ab(its[i - 1][1]))) / h
+                coef[i, 3], coef[i, 4] = c_d * (1.0 + 0.5 / r), -c_d * 0.5 / r
+            plan[i, 4] = PUSH
+    return torch.from_numpy(timesteps), torch.from_numpy(coef.astype(np.float32) if coef_dtype == torch.float32 else coef), \
+        torch.from_numpy(plan)
+
+
 class _IterationRecorder(stp.StepRecorder):
     """StepRecorder's warm-up, capture, fall-back warning and replay for a body that reads the sampler's own static buffers:
     nothing of its training-specific `load` / input buffers is used."""
@@ -86,7 +189,10 @@ class _IterationRecorder(stp.StepRecorder):
 class LatentSampler:
     """`sample(encoder_hidden_states, negative_encoder_hidden_states, seed=...)` → fp32 latents [B, C, h, w] in model space (the
     caller divides by 0.18215 and decodes).  Defaults are evaluate_pipe's: 50 steps, guidance 5.0, the training scheduler's
-    DDPM.  `guidance_scale <= 1` or no negative conditioning: one B-row pass per step (diffusers' do_classifier_free_guidance);
+    DDPM.  `method`: "ddpm", "ddim" (any η), or the deterministic multistep "plms" (SD 1.x's own scheduler: the class images,
+    visualize_progress) and "dpmpp_2m" (η must be 0); those run `num_model_evaluations` iterations — S + 1 for plms — of
+    ddpm_sample_multistep, and `timesteps`, `step()` and the callback count iterations, not grid steps.
+    `guidance_scale <= 1` or no negative conditioning: one B-row pass per step (diffusers' do_classifier_free_guidance);
     else 2B rows, unconditional first.  Stepwise: `begin(...)`, then `step()` until it returns False, then `latents`.
     capture_graph: one denoising iteration — UNet forward, ddpm_sample_step, ddpm_sample_advance — is recorded once per (shapes,
     dtype, fingerprint) and replayed S times, the conditioning in a static buffer, the step index and the seed in device memory
@@ -101,13 +207,27 @@ class LatentSampler:
         self.unet = unet
         self.guidance_scale = float(guidance_scale)
         self._schedule_args = (str(method), int(num_inference_steps), bool(v_prediction), float(eta))
-        self.timesteps, self.coef = sampler_schedule(*self._schedule_args)  # (raises for a bad method / step count / eta)
+        if method not in METHODS + MULTISTEP_METHODS:
+            raise ValueError(f"unknown sampling method {method!r}: one of {METHODS + MULTISTEP_METHODS}")
+        self._multistep = method in MULTISTEP_METHODS
+        if self._multistep:
+            if float(eta) != 0.0:
+                raise ValueError(f"{method!r} is deterministic: eta must be 0; got {eta}")
+            self.timesteps, self.coef, self.plan = multistep_schedule(str(method), int(num_inference_steps), bool(v_prediction))
+        else:
+            self.timesteps, self.coef = sampler_schedule(*self._schedule_args)  # (raises for a bad method / step count / eta)
+            self.plan = None
         self.num_inference_steps = int(num_inference_steps)
         self.capture_graph = bool(capture_graph)
         self._recorder = _IterationRecorder("LatentSampler")
         self._key = self._fp = self._state = self._cond = None
-        self._done = self.num_inference_steps  # nothing begun: step() has nothing to do
+        self._done = self.num_model_evaluations  # nothing begun: step() has nothing to do
         self._inside = False
+
+    @property
+    def num_model_evaluations(self) -> int:
+        """I: the iterations (UNet forwards) of one run — `num_inference_steps`, plus one for "plms" with two steps or more."""
+        return int(self.timesteps.shape[0])
 
     # -- what a recording bakes in -------------------------------------------------------------------------------------------
     def _refresh_packed(self, layers, dtype):
@@ -180,7 +300,10 @@ class LatentSampler:
         out = self.unet(st.model_in, st.t_model, self._cond).sample
         if out.dtype != st.model_in.dtype:
             out = out.to(st.model_in.dtype)
-        nat.ddpm_sample_step(st, out.contiguous(), self.guidance_scale)
+        if self._multistep:
+            nat.ddpm_sample_multistep(st, out.contiguous(), self.guidance_scale)
+        else:
+            nat.ddpm_sample_step(st, out.contiguous(), self.guidance_scale)
         nat.ddpm_sample_advance(st)
 
     def begin(self, encoder_hidden_states, negative_encoder_hidden_states=None, *, seed: int, latent_shape=(4, 64, 64)):
@@ -207,7 +330,12 @@ class LatentSampler:
             if self._state is None or key != self._key or fp != self._fp:
                 self._recorder.drop()  # before the buffers it reads are replaced
                 self._key, self._fp = key, fp
-                self._state = nat.SampleState.alloc((B, *latent_shape), dtype, cfg, self.timesteps, self.coef, ehs.device)
+                if self._multistep:
+                    # (history ring and saved state stay uninitialised: a coefficient of exactly 0 keeps them unread)
+                    self._state = nat.MultistepState.alloc((B, *latent_shape), dtype, cfg, self.timesteps, self.coef, self.plan,
+                                                           ehs.device)
+                else:
+                    self._state = nat.SampleState.alloc((B, *latent_shape), dtype, cfg, self.timesteps, self.coef, ehs.device)
                 self._cond = torch.empty(((2 if cfg else 1) * B, *ehs.shape[1:]), dtype=dtype, device=ehs.device)
             if cfg:
                 self._cond[:B].copy_(neg)  # unconditional rows first, as the pipeline concatenates them
@@ -226,9 +354,9 @@ class LatentSampler:
         return self
 
     def step(self) -> bool:
-        """One denoising iteration.  True while steps remain; False from the one that completes the run on (`while s.step():
-        pass` runs all S) — a call after that launches nothing."""
-        if self._done >= self.num_inference_steps:
+        """One denoising iteration.  True while iterations remain; False from the one that completes the run on (`while
+        s.step(): pass` runs all `num_model_evaluations`) — a call after that launches nothing."""
+        if self._done >= self.num_model_evaluations:
             return False
         with self._mode():
             if self._recorder.graph is not None:
@@ -236,7 +364,7 @@ class LatentSampler:
             else:
                 self._iteration()
         self._done += 1
-        return self._done < self.num_inference_steps
+        return self._done < self.num_model_evaluations
 
     @property
     def latents(self) -> Optional[torch.Tensor]:
@@ -261,11 +389,11 @@ class LatentSampler:
 
     def sample(self, encoder_hidden_states, negative_encoder_hidden_states=None, *, seed: int, latent_shape=(4, 64, 64),
                callback=None) -> torch.Tensor:
-        """All S steps; `callback(i, timestep, latents)` after step i, if given (reading the latents synchronises).  Returns a
-        copy of the final state."""
+        """All iterations; `callback(i, timestep, latents)` after iteration i, if given (reading the latents synchronises).
+        Returns a copy of the final state."""
         with self._mode():
             self.begin(encoder_hidden_states, negative_encoder_hidden_states, seed=seed, latent_shape=latent_shape)
-            for i in range(self.num_inference_steps):
+            for i in range(self.num_model_evaluations):
                 self.step()
                 if callback is not None:
                     callback(i, int(self.timesteps[i]), self._state.x)

@@ -428,6 +428,35 @@ int ddpm_sample_step(float* x, const void* model_out, void* model_in, int64_t* t
 int ddpm_sample_advance(int* cursor, int S, void* stream);
 
 /*
+ * Linear multistep step of the latent sampler.  The class images of prior preservation
+ * (training_scripts/train_lora_dreambooth.py:512-558, train_lora_w_ti.py:675-699, train_lora_pt_caption.py:559-583) and
+ * visualize_progress (lora_diffusion/utils.py:191-211) come from StableDiffusionPipeline.from_pretrained with the model's own
+ * scheduler — for SD 1.x PNDM run as PLMS (skip_prk_steps), a fourth-order method over the last four model outputs; a
+ * second-order solver at 20 steps (DPM-Solver++(2M)) is the usual preview.  Both are instances of one contract; per iteration
+ * i = cursor[0] of I model evaluations, all fp32, every product rounded on its own, summed left to right:
+ *     o    = u + g·(c − u)                                         (cfg == 0: o = model_out), as ddpm_sample_step
+ *     h    = p·x + q·o                                             what the method keeps history of
+ *     base = (flags & USE_SAVED) ? xs : x
+ *     x'   = a·base + c0·h + c1·H[s1] + c2·H[s2] + c3·H[s3]
+ *     flags & SAVE: xs ← x (the state BEFORE the update);   flags & PUSH: H[w] ← h;   x ← x'
+ *     model_in = x' cast (twice under cfg);  t_model = timesteps[min(i + 1, I − 1)]
+ * coef fp32 [I, 7] = (p, q, a, c0, c1, c2, c3) and plan int32 [I, 5] = (w, s1, s2, s3, flags), flags = PUSH 1 | SAVE 2 |
+ * USE_SAVED 4, come from the host (sampling.multistep_schedule: float64 rounded once; formulas restated from the papers,
+ * parity unpinned like ddpm_sample_step's).  The host knows which slot is pushed and which slots hold h of one, two and three
+ * pushes ago: the kernel does no ring arithmetic (slot numbers are taken modulo 4).  hist = fp32 [4, B·per_row], xs = fp32
+ * [B, per_row]; neither needs clearing: a term whose coefficient is exactly 0.0f is neither loaded nor added (xs likewise
+ * unless USE_SAVED with a != 0), so uninitialised history never reaches the state.  No noise term.  Each thread touches its own
+ * elements of x, xs and H[*] only and reads before it writes: the pushed slot may be one that is read.  i outside [0, I):
+ * nothing is read from the tables and nothing written, hist and xs included.  The cursor is not moved: ddpm_sample_advance
+ * with S = I; ddpm_sample_init with S = I starts a run.  4-element accesses when per_row % 4 == 0 and x, xs, hist, model_out
+ * and model_in are aligned to 4 of their elements, element by element otherwise — the same bits.  LORA_E_BADARG for a null
+ * pointer, an unknown dtype, B, per_row or I < 1 — before any HIP call.  No workspace, nothing retained, capturable.
+ */
+int ddpm_sample_multistep(float* x, float* xs, float* hist, const void* model_out, void* model_in, int64_t* t_model,
+                          const int* cursor, const int64_t* timesteps, const float* coef, const int* plan, int B,
+                          int64_t per_row, int I, int cfg, float guidance_scale, int dtype, void* stream);
+
+/*
  * The two ops sandwiched by the hot path inside a transformer block, as streaming kernels.
  *   geglu_gate_fwd : out[M,C]  = h · gelu(g)  with [h | g] = y[M,2C], exact (erf) gelu — the body of diffusers'
  *                    GEGLU.forward, the caller of the `proj` LoraInjectedLinear (target class "GEGLU", lora.py:53).

@@ -1,16 +1,24 @@
-"""Time of one 50-step sample at SD1.5 shape — batch 4 with classifier-free guidance (8 UNet rows), 64×64 latents, f16 — on
-three routes through the same UNet (harness SD1.5 topology, random weights, LoRA rank 4 injected, HIP attention and GEGLU on):
+"""Time of one sample (50 DDPM steps unless --method / --steps say otherwise) at SD1.5 shape — batch 4 with classifier-free
+guidance (8 UNet rows), 64×64 latents, f16 — on three routes through the same UNet (harness SD1.5 topology, random weights,
+LoRA rank 4 injected, HIP attention and GEGLU on):
 
   replayed      LatentSampler(capture_graph=True): one recorded iteration (forward, ddpm_sample_step, advance) replayed 50 times
   host          LatentSampler(capture_graph=False): the same launches issued from the host
   stock         the loop a diffusers pipeline runs around the forward, written out in torch ops: torch.randn, cat of the doubled
                 input, cast, chunk, guidance, the same linear update with host scalars, randn for the variance noise
 
-The parent commit has no sampler, so the stock loop is the baseline.  All three routes run in ONE process, alternating, --reps
+The stock loop is the baseline.  All three routes run in ONE process, alternating, --reps
 times after one untimed round (recording, solver searches, allocator); each sample ends in a device synchronise and is timed with
 a host clock.  Prints one readable line per repetition, the medians, and one JSON line.
 
+--method and --steps take one value or several, paired in order ("ddpm" / "ddim" / "plms" / "dpmpp_2m"): every pair is a
+configuration with its own three routes, and all of them alternate in the same process — so a replayed PLMS or DPM-Solver++(2M)
+iteration (ddpm_sample_multistep) is timed next to a replayed DDPM iteration (ddpm_sample_step).  The multistep methods run
+num_model_evaluations iterations (plms: steps + 1); their stock route keeps the history in a Python list of tensors, as a
+diffusers scheduler does.  One readable line per repetition and configuration, medians and one JSON line per configuration.
+
     python tools/sample_time.py [--reps 5] [--steps 50] [--batch 4]
+    python tools/sample_time.py --batch 1 --method ddpm plms dpmpp_2m --steps 50 50 20
 """
 import argparse
 import json
@@ -64,6 +72,33 @@ def stock_loop(unet, cond, neg, steps, guidance, latent_shape, timesteps, coef, 
     return x
 
 
+def stock_multistep_loop(unet, cond, neg, guidance, latent_shape, timesteps, coef, plan, gen):
+    """The same loop around a multistep scheduler: earlier outputs in a list of tensors, the saved sample, host scalars."""
+    B = cond.shape[0]
+    ctx = torch.cat([neg, cond]).half()
+    x = torch.randn((B, *latent_shape), generator=gen, device="cuda", dtype=torch.float32)
+    ring, saved = [None] * 4, None
+    with torch.no_grad():
+        for i in range(len(coef)):
+            p, q, a, *c = coef[i]
+            w, s1, s2, s3, flags = plan[i]
+            model_in = torch.cat([x] * 2).half()
+            out = unet(model_in, timesteps[i].expand(2 * B), ctx).sample
+            u, cc = out.float().chunk(2)
+            o = u + guidance * (cc - u)
+            h = q * o if p == 0.0 else p * x + q * o
+            nxt = a * (saved if flags & dfa.sampling.USE_SAVED else x) + c[0] * h
+            for ck, sk in zip(c[1:], (s1, s2, s3)):
+                if ck != 0.0:
+                    nxt = nxt + ck * ring[sk]
+            if flags & dfa.sampling.SAVE:
+                saved = x
+            if flags & dfa.sampling.PUSH:
+                ring[w] = h
+            x = nxt
+    return x
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -72,47 +107,71 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
+def routes_for(unet, method, steps, guidance, cond, neg, shape, gen):
+    """(replayed sampler, {route: callable}, iterations of one run) of one configuration."""
+    replayed = dfa.LatentSampler(unet, steps, guidance, method=method)
+    host = dfa.LatentSampler(unet, steps, guidance, method=method, capture_graph=False)
+    if method in dfa.sampling.MULTISTEP_METHODS:
+        ts, coef, plan = dfa.multistep_schedule(method, steps, False)
+        ts_dev, coef_host, plan_host = ts.to("cuda"), [tuple(float(v) for v in row) for row in coef], plan.tolist()
+        stock = lambda: stock_multistep_loop(unet, cond, neg, guidance, shape, ts_dev, coef_host, plan_host, gen)  # noqa: E731
+    else:
+        ts, coef = dfa.sampler_schedule(method, steps, False)
+        ts_dev, coef_host = ts.to("cuda"), [tuple(float(v) for v in row) for row in coef]
+        stock = lambda: stock_loop(unet, cond, neg, steps, guidance, shape, ts_dev, coef_host, gen)  # noqa: E731
+    return replayed, {
+        "replayed": lambda: replayed.sample(cond, neg, seed=7, latent_shape=shape),
+        "host": lambda: host.sample(cond, neg, seed=7, latent_shape=shape),
+        "stock": stock,
+    }, replayed.num_model_evaluations
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, nargs="+", default=[50])
+    ap.add_argument("--method", nargs="+", default=["ddpm"], choices=dfa.sampling.METHODS + dfa.sampling.MULTISTEP_METHODS)
     ap.add_argument("--batch", type=int, default=4)
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps must be at least 5")
+    if len(a.steps) == 1:
+        a.steps = a.steps * len(a.method)
+    if len(a.steps) != len(a.method):
+        ap.error("--steps takes one value, or one per --method")
     unet, ctx_dim = build_unet()
     shape = (4, 64, 64)
     g = torch.Generator().manual_seed(2)
     cond = torch.randn(a.batch, 77, ctx_dim, generator=g).to("cuda")
     neg = torch.randn(a.batch, 77, ctx_dim, generator=g).to("cuda")
     guidance = 5.0
-    replayed = dfa.LatentSampler(unet, a.steps, guidance)
-    host = dfa.LatentSampler(unet, a.steps, guidance, capture_graph=False)
-    ts, coef = dfa.sampler_schedule("ddpm", a.steps, False)
-    ts_dev, coef_host = ts.to("cuda"), [tuple(float(v) for v in row) for row in coef]
     gen = torch.Generator(device="cuda").manual_seed(3)
-    routes = {
-        "replayed": lambda: replayed.sample(cond, neg, seed=7, latent_shape=shape),
-        "host": lambda: host.sample(cond, neg, seed=7, latent_shape=shape),
-        "stock": lambda: stock_loop(unet, cond, neg, a.steps, guidance, shape, ts_dev, coef_host, gen),
-    }
-    first = {name: timed(fn) for name, fn in routes.items()}  # untimed round: recording, solver searches, allocator
-    assert replayed.replaying, "the recording failed: the replayed route would measure host launches"
-    same = bool(torch.equal(first["replayed"][1], first["host"][1]))
-    print(f"first (untimed) round, ms: " + ", ".join(f"{k} {v[0]:.1f}" for k, v in first.items()) +
-          f"; replayed == host-launched bit for bit: {same}", flush=True)
-    times = {name: [] for name in routes}
+    configs = {}
+    for method, steps in zip(a.method, a.steps):
+        configs[f"{method} {steps}"] = (method, steps, *routes_for(unet, method, steps, guidance, cond, neg, shape, gen))
+    first, same = {}, {}
+    for label, (_, _, replayed, routes, _) in configs.items():  # untimed round: recording, solver searches, allocator
+        first[label] = {name: timed(fn) for name, fn in routes.items()}
+        assert replayed.replaying, "the recording failed: the replayed route would measure host launches"
+        same[label] = bool(torch.equal(first[label]["replayed"][1], first[label]["host"][1]))
+        print(f"[{label}] first (untimed) round, ms: " + ", ".join(f"{k} {v[0]:.1f}" for k, v in first[label].items()) +
+              f"; replayed == host-launched bit for bit: {same[label]}", flush=True)
+    times = {label: {name: [] for name in cfg[3]} for label, cfg in configs.items()}
     for rep in range(a.reps):
-        for name, fn in routes.items():
-            times[name].append(timed(fn)[0])
-        print(f"rep {rep}: " + ", ".join(f"{k} {times[k][-1]:.1f} ms" for k in routes), flush=True)
-    med = {k: statistics.median(v) for k, v in times.items()}
-    print("medians: " + ", ".join(f"{k} {v:.1f} ms ({v / a.steps:.2f} ms/step)" for k, v in med.items()), flush=True)
-    print(json.dumps({"gpu": torch.cuda.get_device_name(0), "unet": "sd15", "batch": a.batch,
-                      "rows": 2 * a.batch, "steps": a.steps, "dtype": "f16", "guidance": guidance, "reps": a.reps,
-                      "median_ms": med, "all_ms": times, "first_round_ms": {k: v[0] for k, v in first.items()},
-                      "replayed_equals_host": same, "stock_over_replayed": med["stock"] / med["replayed"],
-                      "host_over_replayed": med["host"] / med["replayed"]}), flush=True)
+        for label, (_, _, _, routes, _) in configs.items():
+            for name, fn in routes.items():
+                times[label][name].append(timed(fn)[0])
+            print(f"[{label}] rep {rep}: " + ", ".join(f"{k} {times[label][k][-1]:.1f} ms" for k in routes), flush=True)
+    for label, (method, steps, _, _, n_it) in configs.items():
+        med = {k: statistics.median(v) for k, v in times[label].items()}
+        print(f"[{label}] medians over {n_it} iterations: " +
+              ", ".join(f"{k} {v:.1f} ms ({v / n_it:.2f} ms/iteration)" for k, v in med.items()), flush=True)
+        print(json.dumps({"gpu": torch.cuda.get_device_name(0), "unet": "sd15", "batch": a.batch, "rows": 2 * a.batch,
+                          "method": method, "steps": steps, "iterations": n_it, "dtype": "f16", "guidance": guidance,
+                          "reps": a.reps, "median_ms": med, "all_ms": times[label],
+                          "first_round_ms": {k: v[0] for k, v in first[label].items()}, "replayed_equals_host": same[label],
+                          "stock_over_replayed": med["stock"] / med["replayed"],
+                          "host_over_replayed": med["host"] / med["replayed"]}), flush=True)
 
 
 if __name__ == "__main__":
