@@ -89,6 +89,10 @@ SIGNATURES = {
     "ddpm_sample_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _vp]),
     "ddpm_sample_advance": (_i32, [_vp, _i32, _vp]),
     "ddpm_sample_multistep": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _vp]),
+    "ddpm_sample_init_from": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _f32, _i32, ctypes.c_uint64,
+                                     _i32, _vp]),
+    "ddpm_sample_step_keep": (_i32, [_vp] * 11 + [_i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp]),
+    "ddpm_sample_multistep_keep": (_i32, [_vp] * 13 + [_i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp]),
     "embed_rows_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "embed_rows_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp]),
     "lora_adamw_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
@@ -673,9 +677,33 @@ class SampleState:
     """The device buffers of one sampling run (include/lora_hip.h: ddpm_sample_*): the fp32 state `x` [B, ...], the model
     input [rows, ...] in `dtype` and its timestep tensor [rows] (rows = 2B under guidance: the same rows twice), the cursor
     (int32 [2]: the denoising-step index and the seed's low word, both read by the step launch from device memory), and the
-    schedule's tables.  `alloc` makes them; a caller may also hand in views of its own (tests: odd offsets)."""
+    schedule's tables.  `alloc` makes them; a caller may also hand in views of its own (tests: odd offsets).
+    Optional, for image-to-image runs (ddpm_sample_init_from, ddpm_sample_*_keep): `init` fp32 like x, the start image's latents
+    in model space; `mask` fp32 [B, 1, h, w] (any [B, ...] of hw elements with per_row % hw == 0) and `keep_coef` fp32 [S, 2] =
+    (k, n) per table row (sampling.keep_schedule) — a mask needs both others."""
 
-    def __init__(self, x, model_in, t_model, cursor, timesteps, coef, cfg: bool):
+    init = mask = keep_coef = None
+
+    def _set_keep(self, x, S, init, mask, keep_coef):
+        B, per_row = x.shape[0], x[0].numel()
+        if init is not None and (init.dtype != torch.float32 or init.shape != x.shape or not init.is_contiguous()):
+            raise ValueError(f"sampler buffers: init must be a contiguous fp32 {tuple(x.shape)} tensor; got {init.dtype} "
+                             f"{tuple(init.shape)}")
+        if mask is not None:
+            if init is None or keep_coef is None:
+                raise ValueError("sampler buffers: a keep mask needs init and keep_coef")
+            if (mask.dtype != torch.float32 or mask.dim() < 2 or mask.shape[0] != B or not mask.is_contiguous() or
+                    per_row % mask[0].numel() != 0):
+                raise ValueError(f"sampler buffers: mask must be a contiguous fp32 [B, 1, h, w] tensor for the state "
+                                 f"{tuple(x.shape)}; got {mask.dtype} {tuple(mask.shape)}")
+        if keep_coef is not None and (keep_coef.dtype != torch.float32 or tuple(keep_coef.shape) != (S, 2) or
+                                      not keep_coef.is_contiguous()):
+            raise ValueError(f"sampler buffers: keep_coef must be a contiguous fp32 [{S}, 2] tensor")
+        _require_device(init, mask, keep_coef)
+        self.init, self.mask, self.keep_coef = init, mask, keep_coef
+        self.hw = None if mask is None else mask[0].numel()
+
+    def __init__(self, x, model_in, t_model, cursor, timesteps, coef, cfg: bool, init=None, mask=None, keep_coef=None):
         B, rows = x.shape[0], model_in.shape[0]
         if rows != (2 * B if cfg else B) or model_in.shape[1:] != x.shape[1:] or t_model.shape != (rows,):
             raise ValueError(f"sampler buffers disagree: state {tuple(x.shape)}, model input {tuple(model_in.shape)}, "
@@ -687,18 +715,30 @@ class SampleState:
         for t in (x, model_in, t_model, timesteps, coef):
             if not t.is_contiguous():
                 raise ValueError("sampler buffers must be contiguous")
+        self._set_keep(x, S, init, mask, keep_coef)
         _require_device(x, model_in, t_model, cursor, timesteps, coef)
         self.x, self.model_in, self.t_model, self.cursor, self.timesteps, self.coef = x, model_in, t_model, cursor, timesteps, coef
         self.cfg, self.B, self.per_row, self.S = bool(cfg), B, x[0].numel(), S
 
+    @staticmethod
+    def _alloc_keep(shape, n_rows, device, with_init, with_mask):
+        """(init, mask, keep_coef) buffers of an image-to-image run, None where not asked for."""
+        if with_mask and not with_init:
+            raise ValueError("sampler buffers: a keep mask needs init")
+        return (torch.empty(shape, dtype=torch.float32, device=device) if with_init else None,
+                torch.empty((shape[0], 1, *shape[2:]), dtype=torch.float32, device=device) if with_mask else None,
+                torch.zeros((n_rows, 2), dtype=torch.float32, device=device) if with_mask else None)
+
     @classmethod
-    def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, device):
+    def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, device, with_init: bool = False,
+              with_mask: bool = False):
         """`shape`: of the state, [B, C, h, w]; `timesteps` / `coef`: host or device tensors of sampler_schedule."""
         rows = (2 if cfg else 1) * shape[0]
         return cls(torch.empty(shape, dtype=torch.float32, device=device),
                    torch.empty((rows, *shape[1:]), dtype=dtype, device=device),
                    torch.empty(rows, dtype=torch.int64, device=device), torch.zeros(2, dtype=torch.int32, device=device),
-                   timesteps.to(device).contiguous(), coef.to(device).contiguous(), cfg)
+                   timesteps.to(device).contiguous(), coef.to(device).contiguous(), cfg,
+                   *cls._alloc_keep(shape, timesteps.shape[0], device, with_init, with_mask))
 
 
 def ddpm_sample_init(st: SampleState, seed: int) -> None:
@@ -724,6 +764,42 @@ def ddpm_sample_step(st: SampleState, model_out, guidance_scale: float, z_out=No
            "ddpm_sample_step")
 
 
+def ddpm_sample_init_from(st: SampleState, seed: int, start: int, k: float, n: float, eps_out=None) -> None:
+    """x = fp32(k·init) + fp32(n·ε) with ε the x_T draw of `ddpm_sample_init` at equal seed, from `st.init`; the first model input,
+    t_model = timesteps[start], cursor = {start, seed}.  `eps_out` (fp32 like x) gets ε."""
+    if st.init is None:
+        raise ValueError("ddpm_sample_init_from: the state has no init buffer")
+    _require_device(eps_out)
+    if eps_out is not None and (eps_out.dtype != torch.float32 or eps_out.shape != st.x.shape or not eps_out.is_contiguous()):
+        raise ValueError(f"eps_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
+    _check(lib().ddpm_sample_init_from(_ptr(st.x), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps),
+                                       _ptr(st.init), _ptr(eps_out), st.B, st.per_row, st.S, int(start), float(k), float(n),
+                                       int(st.cfg), int(seed) & (2**64 - 1), dtype_code(st.model_in.dtype), _stream(st.x)),
+           "ddpm_sample_init_from")
+
+
+def _require_mask(st, what: str) -> None:
+    if st.mask is None:
+        raise ValueError(f"{what}: the state has no keep mask")
+
+
+def ddpm_sample_step_keep(st: SampleState, model_out, guidance_scale: float, z_out=None) -> None:
+    """`ddpm_sample_step`, then x ← fp32(m·y) + fp32((1−m)·x') with y = fp32(k_i·init) + fp32(n_i·ε) from `st.mask`, `st.init`,
+    `st.keep_coef` and the run's start draw; the model input is the blended state."""
+    _require_mask(st, "ddpm_sample_step_keep")
+    _require_device(model_out, z_out)
+    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
+        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
+                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
+    if z_out is not None and (z_out.dtype != torch.float32 or z_out.shape != st.x.shape or not z_out.is_contiguous()):
+        raise ValueError(f"z_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
+    _check(lib().ddpm_sample_step_keep(_ptr(st.x), _ptr(model_out), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor),
+                                       _ptr(st.timesteps), _ptr(st.coef), _ptr(z_out), _ptr(st.mask), _ptr(st.init),
+                                       _ptr(st.keep_coef), st.B, st.per_row, st.hw, st.S, int(st.cfg), float(guidance_scale),
+                                       dtype_code(model_out.dtype), _stream(st.x)),
+           "ddpm_sample_step_keep")
+
+
 def ddpm_sample_advance(st: SampleState) -> None:
     """cursor += 1 (up to S), a one-thread launch behind the step that read it."""
     _check(lib().ddpm_sample_advance(_ptr(st.cursor), st.S, _stream(st.x)), "ddpm_sample_advance")
@@ -735,7 +811,8 @@ class MultistepState(SampleState):
     int32 [I, 5] = (w, s1, s2, s3, flags) of sampling.multistep_schedule.  `S` is I, the number of model evaluations, so
     ddpm_sample_init and ddpm_sample_advance serve it as they are.  `xs` and `hist` need no clearing."""
 
-    def __init__(self, x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan, cfg: bool):
+    def __init__(self, x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan, cfg: bool, init=None, mask=None,
+                 keep_coef=None):
         B, rows = x.shape[0], model_in.shape[0]
         if (rows != (2 * B if cfg else B) or model_in.shape[1:] != x.shape[1:] or t_model.shape != (rows,) or
                 xs.shape != x.shape or tuple(hist.shape) != (4, *x.shape)):
@@ -752,20 +829,23 @@ class MultistepState(SampleState):
         for t in (x, xs, hist, model_in, t_model, timesteps, coef, plan):
             if not t.is_contiguous():
                 raise ValueError("sampler buffers must be contiguous")
+        self._set_keep(x, n, init, mask, keep_coef)
         _require_device(x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan)
         self.x, self.model_in, self.t_model, self.cursor, self.timesteps, self.coef = x, model_in, t_model, cursor, timesteps, coef
         self.xs, self.hist, self.plan = xs, hist, plan
         self.cfg, self.B, self.per_row, self.S = bool(cfg), B, x[0].numel(), n
 
     @classmethod
-    def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, plan, device):
+    def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, plan, device, with_init: bool = False,
+              with_mask: bool = False):
         """`shape`: of the state, [B, C, h, w]; `timesteps` / `coef` / `plan`: host or device tensors of multistep_schedule."""
         rows = (2 if cfg else 1) * shape[0]
         return cls(torch.empty(shape, dtype=torch.float32, device=device), torch.empty(shape, dtype=torch.float32, device=device),
                    torch.empty((4, *shape), dtype=torch.float32, device=device),
                    torch.empty((rows, *shape[1:]), dtype=dtype, device=device),
                    torch.empty(rows, dtype=torch.int64, device=device), torch.zeros(2, dtype=torch.int32, device=device),
-                   timesteps.to(device).contiguous(), coef.to(device).contiguous(), plan.to(device).contiguous(), cfg)
+                   timesteps.to(device).contiguous(), coef.to(device).contiguous(), plan.to(device).contiguous(), cfg,
+                   *cls._alloc_keep(shape, timesteps.shape[0], device, with_init, with_mask))
 
 
 def ddpm_sample_multistep(st: MultistepState, model_out, guidance_scale: float) -> None:
@@ -781,6 +861,22 @@ def ddpm_sample_multistep(st: MultistepState, model_out, guidance_scale: float) 
                                        st.B, st.per_row, st.S, int(st.cfg), float(guidance_scale),
                                        dtype_code(model_out.dtype), _stream(st.x)),
            "ddpm_sample_multistep")
+
+
+def ddpm_sample_multistep_keep(st: MultistepState, model_out, guidance_scale: float) -> None:
+    """`ddpm_sample_multistep`, then the keep blend of `ddpm_sample_step_keep` on the state it produced (SAVE and PUSH read the
+    state before the update, as they do without a mask)."""
+    _require_mask(st, "ddpm_sample_multistep_keep")
+    _require_device(model_out)
+    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
+        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
+                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
+    _check(lib().ddpm_sample_multistep_keep(_ptr(st.x), _ptr(st.xs), _ptr(st.hist), _ptr(model_out), _ptr(st.model_in),
+                                            _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps), _ptr(st.coef),
+                                            _ptr(st.plan), _ptr(st.mask), _ptr(st.init), _ptr(st.keep_coef), st.B, st.per_row,
+                                            st.hw, st.S, int(st.cfg), float(guidance_scale), dtype_code(model_out.dtype),
+                                            _stream(st.x)),
+           "ddpm_sample_multistep_keep")
 
 
 def embed_rows_fwd(table, ids, out_dtype: torch.dtype):

@@ -666,6 +666,58 @@ __device__ __forceinline__ void store_model_input(const SampleParams& p, int64_t
     }
 }
 
+// Keep mask (image-to-image with part of the latent held): after the method's own update x', the state becomes
+//     x = m·y + (1 − m)·x',   y = k·init + n·ε       every product rounded on its own, each sum rounded once
+// with m = mask[b, pixel] broadcast over channels, (k, n) = keep_coef[i] = (√ᾱ, √(1−ᾱ)) at the timestep of the NEXT evaluation
+// ((1, 0) in the last row: sampling.keep_schedule) and ε the run's start draw, regenerated from (cursor[1], stream 3) — no noise
+// buffer exists.  m == 1 leaves y, m == 0 leaves x', bit for bit.  The step kernels are templates over their parameter block: with
+// SampleParams / MultistepParams they are the kernels they were, with the Keep* blocks below the blend is compiled in.
+struct KeepParams {
+    const float* mask;       // [B, hw]
+    const float* init;       // [B, per_row] fp32, model space
+    const float* keep_coef;  // [S, 2] = (k, n)
+    int64_t per_row, hw;
+};
+
+struct KeepSampleParams : SampleParams {
+    KeepParams k;
+};
+template <typename P> constexpr bool kHasKeep = false;
+template <> constexpr bool kHasKeep<KeepSampleParams> = true;
+
+__device__ __forceinline__ float keep_blend(float m, float y, float xn) {
+#pragma clang fp contract(off)
+    const float my = m * y, rest = (1.f - m) * xn;
+    return my + rest;
+}
+
+// xn[0..3] of element group g (first element i0) blended in place.  QUAD: hw % 4 == 0 too, so the group lies inside one channel
+// of one row and its four mask values are consecutive; otherwise the mask index is computed per element.
+template <bool QUAD>
+__device__ __forceinline__ void keep_apply(const KeepParams& k, int64_t n_total, uint32_t seed, int step, int64_t g, float* xn) {
+    const float kk = k.keep_coef[2 * step], kn = k.keep_coef[2 * step + 1];
+    Quad<float> eps;
+    philox_normals4((uint64_t)g, kStreamInit, seed, 0u, eps.v);
+    const int64_t i0 = g * 4;
+    if constexpr (QUAD) {
+        const int64_t b = i0 / k.per_row;
+        const int64_t pix = (i0 - b * k.per_row) % k.hw;
+        const Quad<float> init = *reinterpret_cast<const Quad<float>*>(k.init + i0);
+        const Quad<float> m = *reinterpret_cast<const Quad<float>*>(k.mask + b * k.hw + pix);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xn[e] = keep_blend(m.v[e], ddpm_noisy(kk, kn, init.v[e], eps.v[e]), xn[e]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t i = i0 + e;
+            if (i >= n_total) break;
+            const int64_t b = i / k.per_row;
+            const int64_t pix = (i - b * k.per_row) % k.hw;
+            xn[e] = keep_blend(k.mask[b * k.hw + pix], ddpm_noisy(kk, kn, k.init[i], eps.v[e]), xn[e]);
+        }
+    }
+}
+
 template <typename T, bool QUAD>
 __global__ __launch_bounds__(256) void sample_init_kernel(SampleParams p) {
     const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthreads = (int64_t)gridDim.x * 256;
@@ -691,8 +743,9 @@ __global__ __launch_bounds__(256) void sample_init_kernel(SampleParams p) {
     }
 }
 
-template <typename T, bool QUAD>
-__global__ __launch_bounds__(256) void sample_step_kernel(SampleParams p) {
+template <typename T, bool QUAD, typename P>
+__global__ __launch_bounds__(256) void sample_step_kernel(P p) {
+    constexpr bool KEEP = kHasKeep<P>;
     const int step = p.cursor[0];
     const uint32_t seed = (uint32_t)p.cursor[1];
     if (step < 0 || step >= p.S) return;  // (uniform over the whole launch: one replay too many touches nothing)
@@ -722,6 +775,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(SampleParams p) {
                 const float o = p.cfg ? guided(uf, to_f32<T>(c.v[e]), p.guidance) : uf;
                 xn.v[e] = sample_update(a, b, sigma, x.v[e], o, z.v[e]);
             }
+            if constexpr (KEEP) keep_apply<true>(p.k, p.n_total, seed, step, g, xn.v);
             *reinterpret_cast<Quad<float>*>(p.x + i0) = xn;
             if (p.z_out) *reinterpret_cast<Quad<float>*>(p.z_out + i0) = z;
         } else {
@@ -732,8 +786,14 @@ __global__ __launch_bounds__(256) void sample_step_kernel(SampleParams p) {
                 const float uf = to_f32<T>(out[i]);
                 const float o = p.cfg ? guided(uf, to_f32<T>(out[p.n_total + i]), p.guidance) : uf;
                 xn.v[e] = sample_update(a, b, sigma, p.x[i], o, z.v[e]);
-                p.x[i] = xn.v[e];
+                if constexpr (!KEEP) p.x[i] = xn.v[e];
                 if (p.z_out) p.z_out[i] = z.v[e];
+            }
+            if constexpr (KEEP) {
+                keep_apply<false>(p.k, p.n_total, seed, step, g, xn.v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (i0 + e < p.n_total) p.x[i0 + e] = xn.v[e];
             }
         }
         store_model_input<T, QUAD>(p, i0, xn.v);
@@ -757,9 +817,9 @@ void launch_sample(const SampleParams& p, int64_t per_row, bool init, hipStream_
             hipLaunchKernelGGL((sample_init_kernel<T, false>), grid, dim3(256), 0, s, p);
     } else {
         if (quad)
-            hipLaunchKernelGGL((sample_step_kernel<T, true>), grid, dim3(256), 0, s, p);
+            hipLaunchKernelGGL((sample_step_kernel<T, true, SampleParams>), grid, dim3(256), 0, s, p);
         else
-            hipLaunchKernelGGL((sample_step_kernel<T, false>), grid, dim3(256), 0, s, p);
+            hipLaunchKernelGGL((sample_step_kernel<T, false, SampleParams>), grid, dim3(256), 0, s, p);
     }
 }
 
@@ -791,6 +851,10 @@ struct MultistepParams {
     float* hist;      // [4, B·per_row] fp32: the history ring
     const int* plan;  // [I, 5]
 };
+struct KeepMultistepParams : MultistepParams {
+    KeepParams k;
+};
+template <> constexpr bool kHasKeep<KeepMultistepParams> = true;
 
 __device__ __forceinline__ float multistep_history(float p, float q, float x, float o) {
 #pragma clang fp contract(off)
@@ -809,8 +873,9 @@ __device__ __forceinline__ float multistep_update(float a, float c0, float c1, f
     return acc;
 }
 
-template <typename T, bool QUAD>
-__global__ __launch_bounds__(256) void sample_multistep_kernel(MultistepParams m) {
+template <typename T, bool QUAD, typename P>
+__global__ __launch_bounds__(256) void sample_multistep_kernel(P m) {
+    constexpr bool KEEP = kHasKeep<P>;
     const SampleParams& p = m.s;
     const int it = p.cursor[0];
     if (it < 0 || it >= p.S) return;  // (uniform over the whole launch: one replay too many touches nothing)
@@ -850,6 +915,7 @@ __global__ __launch_bounds__(256) void sample_multistep_kernel(MultistepParams m
                 h.v[e] = multistep_history(kp, kq, x.v[e], o);
                 xn.v[e] = multistep_update(a, c0, c1, c2, c3, base.v[e], h.v[e], h1.v[e], h2.v[e], h3.v[e]);
             }
+            if constexpr (KEEP) keep_apply<true>(m.k, p.n_total, (uint32_t)p.cursor[1], it, g, xn.v);
             if (save) *reinterpret_cast<Quad<float>*>(m.xs + i0) = x;
             if (push) *reinterpret_cast<Quad<float>*>(hw + i0) = h;
             *reinterpret_cast<Quad<float>*>(p.x + i0) = xn;
@@ -867,12 +933,19 @@ __global__ __launch_bounds__(256) void sample_multistep_kernel(MultistepParams m
                 xn.v[e] = multistep_update(a, c0, c1, c2, c3, base, h, h1, h2, h3);
                 if (save) m.xs[i] = x;
                 if (push) hw[i] = h;
-                p.x[i] = xn.v[e];
+                if constexpr (!KEEP) p.x[i] = xn.v[e];
+            }
+            if constexpr (KEEP) {
+                keep_apply<false>(m.k, p.n_total, (uint32_t)p.cursor[1], it, g, xn.v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (i0 + e < p.n_total) p.x[i0 + e] = xn.v[e];
             }
         }
         store_model_input<T, QUAD>(p, i0, xn.v);
     }
 }
+
 
 template <typename T>
 void launch_multistep(const MultistepParams& m, int64_t per_row, hipStream_t s) {
@@ -881,9 +954,9 @@ void launch_multistep(const MultistepParams& m, int64_t per_row, hipStream_t s) 
                       quad_aligned<float>(m.xs) && quad_aligned<float>(m.hist);  // (n_total % 4 == 0: every slot as hist)
     const dim3 grid(posterior_blocks(p.n_total));
     if (quad)
-        hipLaunchKernelGGL((sample_multistep_kernel<T, true>), grid, dim3(256), 0, s, m);
+        hipLaunchKernelGGL((sample_multistep_kernel<T, true, MultistepParams>), grid, dim3(256), 0, s, m);
     else
-        hipLaunchKernelGGL((sample_multistep_kernel<T, false>), grid, dim3(256), 0, s, m);
+        hipLaunchKernelGGL((sample_multistep_kernel<T, false, MultistepParams>), grid, dim3(256), 0, s, m);
 }
 
 }  // namespace
@@ -938,6 +1011,167 @@ extern "C" int ddpm_sample_step(float* x, const void* model_out, void* model_in,
 extern "C" int ddpm_sample_advance(int* cursor, int S, void* stream) {
     if (!cursor || S < 1) return LORA_E_BADARG;
     hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), cursor, S);
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Image-to-image starts and keep-mask steps of the latent sampler ("Making Img2Img Inference with LoRA", README.md:287-289 and
+// scripts/run_img2img.ipynb of the reference: `pipe(image=init_image, strength=0.75)`).  A run that starts part-way down the grid
+// is the same recorded iteration with another cursor: ddpm_sample_init_from writes the noised start state
+//     x = k·init + n·ε,   ε the x_T draw of ddpm_sample_init (stream 3, key (seed, 0)),   (k, n) = (√ᾱ, √(1−ᾱ)) at timesteps[start]
+// and cursor = {start, seed}; the keep entries are the two step kernels with KEEP on (keep_apply above).
+namespace {
+
+struct InitFromParams {
+    const float* init;  // [B, per_row] fp32
+    float* eps_out;     // nullable
+    int start;
+    float k, n;
+};
+
+template <typename T, bool QUAD>
+__global__ __launch_bounds__(256) void sample_init_from_kernel(SampleParams p, InitFromParams f) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthreads = (int64_t)gridDim.x * 256;
+    const int64_t t0 = p.timesteps[f.start];
+    for (int64_t r = tid; r < p.rows; r += nthreads) p.t_model[r] = t0;
+    if (tid == 0) {
+        p.cursor[0] = f.start;
+        p.cursor[1] = (int)p.seed;
+    }
+    const int64_t groups = (p.n_total + 3) >> 2;
+    for (int64_t g = tid; g < groups; g += nthreads) {
+        Quad<float> z, x = {};
+        philox_normals4((uint64_t)g, kStreamInit, p.seed, 0u, z.v);
+        const int64_t i0 = g * 4;
+        if constexpr (QUAD) {
+            const Quad<float> init = *reinterpret_cast<const Quad<float>*>(f.init + i0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x.v[e] = ddpm_noisy(f.k, f.n, init.v[e], z.v[e]);
+            *reinterpret_cast<Quad<float>*>(p.x + i0) = x;
+            if (f.eps_out) *reinterpret_cast<Quad<float>*>(f.eps_out + i0) = z;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = i0 + e;
+                if (i >= p.n_total) break;
+                x.v[e] = ddpm_noisy(f.k, f.n, f.init[i], z.v[e]);
+                p.x[i] = x.v[e];
+                if (f.eps_out) f.eps_out[i] = z.v[e];
+            }
+        }
+        store_model_input<T, QUAD>(p, i0, x.v);
+    }
+}
+
+template <typename T>
+void launch_init_from(const SampleParams& p, const InitFromParams& f, int64_t per_row, hipStream_t s) {
+    const bool quad = (per_row % 4) == 0 && quad_aligned<float>(p.x) && quad_aligned<T>(p.in) && quad_aligned<float>(f.init) &&
+                      quad_aligned<float>(f.eps_out);
+    const dim3 grid(posterior_blocks(p.n_total));
+    if (quad)
+        hipLaunchKernelGGL((sample_init_from_kernel<T, true>), grid, dim3(256), 0, s, p, f);
+    else
+        hipLaunchKernelGGL((sample_init_from_kernel<T, false>), grid, dim3(256), 0, s, p, f);
+}
+
+// (hw % 4 == 0: a group of four then lies inside one channel and its mask values are four consecutive, aligned floats)
+template <typename T>
+bool keep_quad(const SampleParams& p, const KeepParams& k) {
+    return (k.per_row % 4) == 0 && (k.hw % 4) == 0 && quad_aligned<float>(p.x) && quad_aligned<T>(p.out) && quad_aligned<T>(p.in) &&
+           quad_aligned<float>(p.z_out) && quad_aligned<float>(k.init) && quad_aligned<float>(k.mask);
+}
+
+template <typename T>
+void launch_step_keep(const KeepSampleParams& p, hipStream_t s) {
+    const dim3 grid(posterior_blocks(p.n_total));
+    if (keep_quad<T>(p, p.k))
+        hipLaunchKernelGGL((sample_step_kernel<T, true, KeepSampleParams>), grid, dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL((sample_step_kernel<T, false, KeepSampleParams>), grid, dim3(256), 0, s, p);
+}
+
+template <typename T>
+void launch_multistep_keep(const KeepMultistepParams& m, hipStream_t s) {
+    const dim3 grid(posterior_blocks(m.s.n_total));
+    if (keep_quad<T>(m.s, m.k) && quad_aligned<float>(m.xs) && quad_aligned<float>(m.hist))
+        hipLaunchKernelGGL((sample_multistep_kernel<T, true, KeepMultistepParams>), grid, dim3(256), 0, s, m);
+    else
+        hipLaunchKernelGGL((sample_multistep_kernel<T, false, KeepMultistepParams>), grid, dim3(256), 0, s, m);
+}
+
+bool keep_args_ok(const float* mask, const float* init, const float* keep_coef, int64_t per_row, int64_t hw) {
+    return mask && init && keep_coef && per_row >= 1 && hw >= 1 && per_row % hw == 0;
+}
+
+}  // namespace
+
+extern "C" int ddpm_sample_init_from(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps,
+                                     const float* init, float* eps_out, int B, int64_t per_row, int S, int start, float k,
+                                     float n, int cfg, uint64_t seed, int dtype, void* stream) {
+    if (!x || !model_in || !t_model || !cursor || !timesteps || !init || B < 1 || per_row < 1 || S < 1 || start < 0 ||
+        start >= S || !known_dtype(dtype))
+        return LORA_E_BADARG;
+    SampleParams p{};
+    p.x = x; p.in = model_in; p.t_model = t_model; p.cursor = cursor; p.timesteps = timesteps;
+    p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = S; p.cfg = cfg ? 1 : 0; p.seed = (uint32_t)seed;
+    InitFromParams f{};
+    f.init = init; f.eps_out = eps_out; f.start = start; f.k = k; f.n = n;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case LORA_F32: launch_init_from<float>(p, f, per_row, s); break;
+        case LORA_F16: launch_init_from<half_t>(p, f, per_row, s); break;
+        default: launch_init_from<bf16_t>(p, f, per_row, s); break;
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+extern "C" int ddpm_sample_step_keep(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+                                     const int64_t* timesteps, const float* coef, float* z_out, const float* mask,
+                                     const float* init, const float* keep_coef, int B, int64_t per_row, int64_t hw, int S, int cfg,
+                                     float guidance_scale, int dtype, void* stream) {
+    if (!x || !model_out || !model_in || !t_model || !cursor || !timesteps || !coef || B < 1 || S < 1 ||
+        !keep_args_ok(mask, init, keep_coef, per_row, hw) || !known_dtype(dtype))
+        return LORA_E_BADARG;
+    KeepSampleParams p{};
+    p.x = x; p.out = model_out; p.in = model_in; p.t_model = t_model; p.cursor = const_cast<int*>(cursor);
+    p.timesteps = timesteps; p.coef = coef; p.z_out = z_out;
+    p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = S; p.cfg = cfg ? 1 : 0;
+    p.guidance = guidance_scale;
+    p.k = KeepParams{mask, init, keep_coef, per_row, hw};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case LORA_F32: launch_step_keep<float>(p, s); break;
+        case LORA_F16: launch_step_keep<half_t>(p, s); break;
+        default: launch_step_keep<bf16_t>(p, s); break;
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+extern "C" int ddpm_sample_multistep_keep(float* x, float* xs, float* hist, const void* model_out, void* model_in,
+                                          int64_t* t_model, const int* cursor, const int64_t* timesteps, const float* coef,
+                                          const int* plan, const float* mask, const float* init, const float* keep_coef, int B,
+                                          int64_t per_row, int64_t hw, int I, int cfg, float guidance_scale, int dtype,
+                                          void* stream) {
+    if (!x || !xs || !hist || !model_out || !model_in || !t_model || !cursor || !timesteps || !coef || !plan || B < 1 || I < 1 ||
+        !keep_args_ok(mask, init, keep_coef, per_row, hw) || !known_dtype(dtype))
+        return LORA_E_BADARG;
+    KeepMultistepParams m{};
+    SampleParams& p = m.s;
+    p.x = x; p.out = model_out; p.in = model_in; p.t_model = t_model; p.cursor = const_cast<int*>(cursor);
+    p.timesteps = timesteps; p.coef = coef;
+    p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = I; p.cfg = cfg ? 1 : 0;
+    p.guidance = guidance_scale;
+    m.xs = xs; m.hist = hist; m.plan = plan;
+    m.k = KeepParams{mask, init, keep_coef, per_row, hw};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case LORA_F32: launch_multistep_keep<float>(m, s); break;
+        case LORA_F16: launch_multistep_keep<half_t>(m, s); break;
+        default: launch_multistep_keep<bf16_t>(m, s); break;
+    }
     LORA_LAUNCH_CHECK();
     return LORA_OK;
 }

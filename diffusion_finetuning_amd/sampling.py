@@ -22,8 +22,25 @@ state; `multistep_schedule` computes the coefficients and the ring's plan on the
 per iteration, and history, plan and coefficients live in device memory, indexed by the same device-resident cursor.  PNDM and
 DPM-Solver++ are restated from their papers (Liu et al. 2022; Lu et al. 2022), parity UNPINNED in the same sense
 (tests/multistep_reference.py).
-Out of scope: VAE decode, prompts, clip_sample / thresholding, image-to-image starts, PRK steps, Euler / Heun, the SDE variants,
-Karras sigmas.
+
+Image-to-image ("Making Img2Img Inference with LoRA", README.md:287-289 and scripts/run_img2img.ipynb of the reference:
+`pipe(image=init_image, strength=0.75)`, repeated at equal seed under `tune_lora_scale(unet, 0.0 / 0.7 / 1.0)`).  With S =
+num_inference_steps and `strength` in (0, 1], n = min(int(S·strength), S) grid steps are run (n == 0 is an error), from k0 = S − n
+and t0 = grid[k0]; the start state is x = fp32(√ᾱ[t0]·init) + fp32(√(1−ᾱ[t0])·ε), ε the x_T draw of the same seed, `init` the
+caller's `vae.encode(...).sample() * 0.18215` (csrc/ddpm_loss.hip: ddpm_sample_init_from).  "ddpm" / "ddim" run iterations
+k0 … S−1 of their tables unchanged, the variance noise keyed by the absolute index; "plms" / "dpmpp_2m" start FRESH on grid[k0:]
+with empty history (`multistep_schedule(first_step=k0)`: plms warms up there, n + 1 evaluations for n ≥ 2; dpmpp_2m's first
+iteration is first order, its last when S < 15).  The cursor lives in device memory, so a partial run is the same recorded
+iteration started at another row: a shorter multistep run's tables go to the TAIL rows of the static tables.
+Keep mask: m fp32 [B, 1, h, w] in [0, 1], 1 = hold the original, 0 = resample.  After every iteration the state the method
+produced, x' (variance noise included), becomes x = fp32(m·y) + fp32((1−m)·x'), y = fp32(k_j·init) + fp32(n_j·ε), (k_j, n_j) =
+(√ᾱ[τ], √(1−ᾱ[τ])) at the model timestep τ of the NEXT evaluation — the noise level the state is at — and (1, 0) after the last
+(`keep_schedule`), ε the same start draw, regenerated in the kernel (ddpm_sample_step_keep / ddpm_sample_multistep_keep).  Where
+m == 1 the final latents are `init` bit for bit; where m == 0 every iteration's result is the unmasked entry's.  diffusers'
+img2img / inpaint pipelines are not part of the reference tree: restated from their published behaviour, parity UNPINNED beyond
+this repository's own float64 restatement (tests/partial_reference.py).
+Out of scope: VAE encode / decode, starting from cached moments, 9-channel inpainting UNets, per-row strengths, prompts,
+clip_sample / thresholding, PRK steps, Euler / Heun, the SDE variants, Karras sigmas.
 """
 import contextlib
 import math
@@ -87,12 +104,18 @@ def sampler_schedule(method: str, num_inference_steps: int, v_prediction: bool, 
     return torch.from_numpy(timesteps.copy()), torch.from_numpy(coef.astype(np.float32))
 
 
+def trainer_acp(t: int, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012) -> float:
+    """ᾱ[t] of the training table (float64), as `sampler_schedule` builds it."""
+    betas = np.linspace(float(beta_start) ** 0.5, float(beta_end) ** 0.5, int(num_train_timesteps), dtype=np.float64) ** 2
+    return float(np.cumprod(1.0 - betas)[int(t)])
+
+
 _AB_WEIGHTS = ((1.0,), (1.5, -0.5), (23.0 / 12.0, -16.0 / 12.0, 5.0 / 12.0), (55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0))
 
 
 def multistep_schedule(method: str, num_inference_steps: int, v_prediction: bool, num_train_timesteps: int = 1000,
-                       beta_start: float = 0.00085, beta_end: float = 0.012,
-                       coef_dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                       beta_start: float = 0.00085, beta_end: float = 0.012, coef_dtype: torch.dtype = torch.float32, *,
+                       first_step: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(timesteps int64 [I], coef fp32 [I, 7] = (p, q, a, c0, c1, c2, c3), plan int32 [I, 5] = (w, s1, s2, s3, flags)) of
         h = p·x + q·o;  base = xs if USE_SAVED else x;  x' = a·base + c0·h + c1·H[s1] + c2·H[s2] + c3·H[s3];
         SAVE: xs ← x;  PUSH: H[w] ← h
@@ -113,8 +136,12 @@ def multistep_schedule(method: str, num_inference_steps: int, v_prediction: bool
           iteration pushes.  Stepping s → t, h = λ_t − λ_s: the first iteration, and the last when S < 15 (lower-order final), is
           x_t = (σ_t/σ_s)·x − α_t·(e^{−h} − 1)·x0_s; the others, with r = h_prev/h,
           x_t = (σ_t/σ_s)·x − α_t·(e^{−h} − 1)·[(1 + 1/(2r))·x0_s − (1/(2r))·x0_{s−1}].
+    `first_step = k` (image-to-image): the tables of the method started FRESH on grid[k:], history empty — plms warms up there
+    (n + 1 evaluations for n = S − k ≥ 2, one for n = 1), dpmpp_2m's first iteration is first order; the lower-order-final rule
+    stays keyed on the full S.  `first_step = 0` is the full run.
     diffusers is not part of the reference tree: both are restated from the papers and from the pipeline's published
-    behaviour, parity UNPINNED beyond this repository's own stateful float64 restatement (tests/multistep_reference.py)."""
+    behaviour, parity UNPINNED beyond this repository's own stateful float64 restatement (tests/multistep_reference.py,
+    tests/partial_reference.py)."""
     T, S = int(num_train_timesteps), int(num_inference_steps)
     if method not in MULTISTEP_METHODS:
         raise ValueError(f"unknown multistep sampling method {method!r}: one of {MULTISTEP_METHODS}")
@@ -126,7 +153,11 @@ def multistep_schedule(method: str, num_inference_steps: int, v_prediction: bool
     acp = np.cumprod(1.0 - betas)
     ratio = T // S
     offset = min(1, T - 1 - (S - 1) * ratio)
-    grid = [(S - 1 - j) * ratio + offset for j in range(S)]  # descending: grid[0] = t_{S−1}
+    first_step = int(first_step)
+    if not 0 <= first_step < S:
+        raise ValueError(f"first_step must lie in [0, num_inference_steps = {S}); got {first_step}")
+    grid = [(S - 1 - j) * ratio + offset for j in range(first_step, S)]  # descending: grid[0] = t_{S−1} of a full run
+    n_grid = len(grid)
 
     def ab(t):
         return float(acp[t]) if t >= 0 else float(acp[0])
@@ -134,9 +165,9 @@ def multistep_schedule(method: str, num_inference_steps: int, v_prediction: bool
     if method == "plms":
         # (model timestep, transfer's t, pushes before this iteration, pushed?) per iteration
         its = [(grid[0], grid[0], 0, True)]
-        if S >= 2:
+        if n_grid >= 2:
             its.append((grid[1], grid[0], 1, False))
-            its += [(grid[j], grid[j], j, True) for j in range(1, S)]
+            its += [(grid[j], grid[j], j, True) for j in range(1, n_grid)]
     else:
         its = [(t, t, j, True) for j, t in enumerate(grid)]
     n_it = len(its)
@@ -178,6 +209,34 @@ def multistep_schedule(method: str, num_inference_steps: int, v_prediction: bool
         torch.from_numpy(plan)
 
 
+def partial_start(num_inference_steps: int, strength: float) -> Tuple[int, int]:
+    """(n, k0) of an image-to-image run: n = min(int(S·strength), S) grid steps, from grid index k0 = S − n.  ValueError for a
+    strength outside (0, 1] or not finite, and for n == 0 — the noised image after zero steps is not a sample."""
+    S = int(num_inference_steps)
+    strength = float(strength)
+    if not (math.isfinite(strength) and 0.0 < strength <= 1.0):
+        raise ValueError(f"strength must lie in (0, 1]; got {strength}")
+    n = min(int(S * strength), S)
+    if n == 0:
+        raise ValueError(f"num_inference_steps = {S} at strength = {strength} leaves no step to run (int(S·strength) == 0): "
+                         "raise one of them")
+    return n, S - n
+
+
+def keep_schedule(timesteps, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012) -> torch.Tensor:
+    """fp32 [I, 2] = (k_j, n_j) for the model timesteps [I] of a run: (√ᾱ[τ], √(1−ᾱ[τ])) with τ = timesteps[j + 1], the timestep
+    of the NEXT evaluation — the noise level the state is at after iteration j, for every method here — and (1, 0) in the last
+    row.  float64 rounded once; ᾱ as in `sampler_schedule`."""
+    T = int(num_train_timesteps)
+    betas = np.linspace(float(beta_start) ** 0.5, float(beta_end) ** 0.5, T, dtype=np.float64) ** 2
+    acp = np.cumprod(1.0 - betas)
+    ts = [int(t) for t in timesteps]
+    out = np.zeros((len(ts), 2), dtype=np.float64)
+    for j in range(len(ts)):
+        out[j] = (math.sqrt(acp[ts[j + 1]]), math.sqrt(1.0 - acp[ts[j + 1]])) if j + 1 < len(ts) else (1.0, 0.0)
+    return torch.from_numpy(out.astype(np.float32))
+
+
 class _IterationRecorder(stp.StepRecorder):
     """StepRecorder's warm-up, capture, fall-back warning and replay for a body that reads the sampler's own static buffers:
     nothing of its training-specific `load` / input buffers is used."""
@@ -200,7 +259,13 @@ class LatentSampler:
     then on (StepRecorder's policy).  The UNet may be driven by a LoraTrainer (slab, packed factors) or plainly injected
     (ops.PackRegistry): the packed factors are refreshed from the fp32 masters before every run, so an optimizer step, an
     in-place edit, `tune_lora_scale` or a `monkeypatch_*` call shows in the next sample; the trainer's own state — gradient
-    slab, recording, counters — is not touched."""
+    slab, recording, counters — is not touched.
+    Image-to-image: `init_latents` [B, C, h, w] (model space, fp32 or the compute dtype; its shape decides, `latent_shape` is not
+    read) with `strength` in (0, 1] starts the run at grid step S − min(int(S·strength), S) from the noised image; `keep_mask`
+    (fp32 [B, 1, h, w] in [0, 1] — the VALUES are not checked: that would synchronise) holds the masked part at the re-noised
+    original.  `run_evaluations` / `run_timesteps` describe the run begun; `step()` and the callback count its iterations
+    from 0.  A recording depends on WHETHER there is an init and a mask only: strength, seed and the init / mask values replay
+    the same graph (static buffers rewritten in place, the run's first table row in the device cursor)."""
 
     def __init__(self, unet, num_inference_steps: int = 50, guidance_scale: float = 5.0, method: str = "ddpm", eta: float = 0.0,
                  v_prediction: bool = False, capture_graph: bool = True):
@@ -221,8 +286,37 @@ class LatentSampler:
         self.capture_graph = bool(capture_graph)
         self._recorder = _IterationRecorder("LatentSampler")
         self._key = self._fp = self._state = self._cond = None
-        self._done = self.num_model_evaluations  # nothing begun: step() has nothing to do
+        self._run_len, self._run_timesteps = self.num_model_evaluations, self.timesteps
+        self._done = self._run_len  # nothing begun: step() has nothing to do
         self._inside = False
+        self._partial = {}  # first grid step → that run's multistep tables, placed in the tail rows
+
+    @property
+    def run_evaluations(self) -> int:
+        """The iterations (UNet forwards) of the run begun: `num_model_evaluations` unless it started part-way (`strength`)."""
+        return self._run_len
+
+    @property
+    def run_timesteps(self) -> torch.Tensor:
+        """int64 [run_evaluations]: the model timestep of every evaluation of the run begun."""
+        return self._run_timesteps
+
+    def _run_tables(self, k0: int):
+        """(first table row, run length, timesteps, coef, plan) of the run that starts at grid step k0, as full-size tables.
+        "ddpm" / "ddim": the tables as they are, from row k0.  Multistep: the fresh sub-run's I' rows in the tail rows
+        [I − I', I) — the recorded I stays valid — the rows before them as in the full run (never reached)."""
+        n_it = self.num_model_evaluations
+        if not self._multistep:
+            return k0, n_it - k0, self.timesteps, self.coef, None
+        if k0 not in self._partial:
+            method, S, v, _ = self._schedule_args
+            ts, coef, plan = multistep_schedule(method, S, v, first_step=k0)
+            start = n_it - ts.shape[0]
+            full = [self.timesteps.clone(), self.coef.clone(), self.plan.clone()]
+            for dst, src in zip(full, (ts, coef, plan)):
+                dst[start:] = src
+            self._partial[k0] = (start, int(ts.shape[0]), *full)
+        return self._partial[k0]
 
     @property
     def num_model_evaluations(self) -> int:
@@ -300,32 +394,58 @@ class LatentSampler:
         out = self.unet(st.model_in, st.t_model, self._cond).sample
         if out.dtype != st.model_in.dtype:
             out = out.to(st.model_in.dtype)
+        keep = st.mask is not None
         if self._multistep:
-            nat.ddpm_sample_multistep(st, out.contiguous(), self.guidance_scale)
+            (nat.ddpm_sample_multistep_keep if keep else nat.ddpm_sample_multistep)(st, out.contiguous(), self.guidance_scale)
         else:
-            nat.ddpm_sample_step(st, out.contiguous(), self.guidance_scale)
+            (nat.ddpm_sample_step_keep if keep else nat.ddpm_sample_step)(st, out.contiguous(), self.guidance_scale)
         nat.ddpm_sample_advance(st)
 
-    def begin(self, encoder_hidden_states, negative_encoder_hidden_states=None, *, seed: int, latent_shape=(4, 64, 64)):
+    def _check_partial(self, B, dtype, init, strength, mask):
+        """The checks of an image-to-image call — all before anything is written.  (n, k0), or None without init."""
+        if init is None:
+            if mask is not None:
+                raise ValueError("keep_mask needs init_latents: the mask holds part of a start image")
+            if strength is not None:
+                raise ValueError("strength needs init_latents")
+            return None
+        if strength is None:
+            raise ValueError("init_latents needs a strength in (0, 1]")
+        start = partial_start(self.num_inference_steps, strength)
+        if not torch.is_tensor(init) or init.dim() != 4 or init.shape[0] != B or min(init.shape) < 1:
+            raise ValueError(f"init_latents must be [B = {B}, C, h, w]; got {tuple(getattr(init, 'shape', ()))}")
+        if init.dtype not in (torch.float32, dtype):
+            raise ValueError(f"init_latents must be float32 or the compute dtype {dtype}; got {init.dtype}")
+        if mask is not None:
+            want = (B, 1, *init.shape[2:])
+            if not torch.is_tensor(mask) or tuple(mask.shape) != want or mask.dtype != torch.float32:
+                raise ValueError(f"keep_mask must be a float32 {want} tensor; got {getattr(mask, 'dtype', None)} "
+                                 f"{tuple(getattr(mask, 'shape', ()))}")
+        return start
+
+    def begin(self, encoder_hidden_states, negative_encoder_hidden_states=None, *, seed: int, latent_shape=(4, 64, 64),
+              init_latents=None, strength: Optional[float] = None, keep_mask=None):
         ehs, neg = encoder_hidden_states, negative_encoder_hidden_states
         if ehs.dim() != 3:
             raise ValueError(f"encoder_hidden_states must be [B, L, D]; got {tuple(ehs.shape)}")
         if neg is not None and tuple(neg.shape) != tuple(ehs.shape):
             raise ValueError(f"negative_encoder_hidden_states {tuple(neg.shape)} does not match encoder_hidden_states "
                              f"{tuple(ehs.shape)}: one unconditional row per conditional row")
-        latent_shape = tuple(int(n) for n in latent_shape)
+        B = ehs.shape[0]
+        dtype = stp.compute_dtype(self.unet)
+        partial = self._check_partial(B, dtype, init_latents, strength, keep_mask)
+        has_init, has_mask = partial is not None, keep_mask is not None
+        latent_shape = tuple(int(n) for n in (init_latents.shape[1:] if has_init else latent_shape))
         if len(latent_shape) != 3 or min(latent_shape) < 1:
             raise ValueError(f"latent_shape must be (C, h, w); got {latent_shape}")
         if seed is None:
             raise ValueError("pass a seed: the draw is Philox keyed by (seed, denoising step)")
-        nat._require_device(ehs, neg)
+        nat._require_device(ehs, neg, init_latents, keep_mask)
         cfg = neg is not None and self.guidance_scale > 1.0
-        B = ehs.shape[0]
-        dtype = stp.compute_dtype(self.unet)
         with self._mode():
             layers = [m for m in self.unet.modules() if isinstance(m, LoraInjectedLinear)]
             self._refresh_packed(layers, dtype)
-            key = (B, latent_shape, tuple(ehs.shape[1:]), cfg, dtype, ehs.device)
+            key = (B, latent_shape, tuple(ehs.shape[1:]), cfg, dtype, ehs.device, has_init, has_mask)
             fp = self._fingerprint(layers)
             if self._state is None or key != self._key or fp != self._fp:
                 self._recorder.drop()  # before the buffers it reads are replaced
@@ -333,30 +453,49 @@ class LatentSampler:
                 if self._multistep:
                     # (history ring and saved state stay uninitialised: a coefficient of exactly 0 keeps them unread)
                     self._state = nat.MultistepState.alloc((B, *latent_shape), dtype, cfg, self.timesteps, self.coef, self.plan,
-                                                           ehs.device)
+                                                           ehs.device, with_init=has_init, with_mask=has_mask)
                 else:
-                    self._state = nat.SampleState.alloc((B, *latent_shape), dtype, cfg, self.timesteps, self.coef, ehs.device)
+                    self._state = nat.SampleState.alloc((B, *latent_shape), dtype, cfg, self.timesteps, self.coef, ehs.device,
+                                                        with_init=has_init, with_mask=has_mask)
                 self._cond = torch.empty(((2 if cfg else 1) * B, *ehs.shape[1:]), dtype=dtype, device=ehs.device)
             if cfg:
                 self._cond[:B].copy_(neg)  # unconditional rows first, as the pipeline concatenates them
                 self._cond[B:].copy_(ehs)
             else:
                 self._cond.copy_(ehs)
-            nat.ddpm_sample_init(self._state, seed)
+            st = self._state
+            if has_init:
+                # static buffers rewritten in place: a recording reads them through their addresses
+                row, self._run_len, ts, coef, plan = self._run_tables(partial[1])
+                self._run_timesteps = ts[row:row + self._run_len]
+                st.init.copy_(init_latents)
+                if self._multistep:
+                    st.timesteps.copy_(ts)
+                    st.coef.copy_(coef)
+                    st.plan.copy_(plan)
+                if has_mask:
+                    st.mask.copy_(keep_mask)
+                    st.keep_coef[row:row + self._run_len].copy_(keep_schedule(self._run_timesteps))
+                ab = float(trainer_acp(int(self._run_timesteps[0])))
+                start = lambda: nat.ddpm_sample_init_from(st, seed, row, math.sqrt(ab), math.sqrt(1.0 - ab))  # noqa: E731
+            else:
+                self._run_len, self._run_timesteps = self.num_model_evaluations, self.timesteps
+                start = lambda: nat.ddpm_sample_init(st, seed)  # noqa: E731
+            start()
             if self.capture_graph and self._recorder.graph is None:
                 # the warm-up passes move the state and the cursor: the run is begun again behind them
                 if self._recorder.record(self._iteration, keep=self._held):
                     self._fp = self._fingerprint(layers)  # (the warm-up passes built the caches whose addresses it lists)
                 else:
                     self.capture_graph = False
-                nat.ddpm_sample_init(self._state, seed)
+                start()
         self._done = 0
         return self
 
     def step(self) -> bool:
         """One denoising iteration.  True while iterations remain; False from the one that completes the run on (`while
-        s.step(): pass` runs all `num_model_evaluations`) — a call after that launches nothing."""
-        if self._done >= self.num_model_evaluations:
+        s.step(): pass` runs all `run_evaluations`) — a call after that launches nothing."""
+        if self._done >= self._run_len:
             return False
         with self._mode():
             if self._recorder.graph is not None:
@@ -364,7 +503,7 @@ class LatentSampler:
             else:
                 self._iteration()
         self._done += 1
-        return self._done < self.num_model_evaluations
+        return self._done < self._run_len
 
     @property
     def latents(self) -> Optional[torch.Tensor]:
@@ -388,13 +527,14 @@ class LatentSampler:
         return self._recorder.graph is not None
 
     def sample(self, encoder_hidden_states, negative_encoder_hidden_states=None, *, seed: int, latent_shape=(4, 64, 64),
-               callback=None) -> torch.Tensor:
-        """All iterations; `callback(i, timestep, latents)` after iteration i, if given (reading the latents synchronises).
-        Returns a copy of the final state."""
+               callback=None, init_latents=None, strength: Optional[float] = None, keep_mask=None) -> torch.Tensor:
+        """All iterations of the run; `callback(i, timestep, latents)` after iteration i, if given (reading the latents
+        synchronises).  Returns a copy of the final state."""
         with self._mode():
-            self.begin(encoder_hidden_states, negative_encoder_hidden_states, seed=seed, latent_shape=latent_shape)
-            for i in range(self.num_model_evaluations):
+            self.begin(encoder_hidden_states, negative_encoder_hidden_states, seed=seed, latent_shape=latent_shape,
+                       init_latents=init_latents, strength=strength, keep_mask=keep_mask)
+            for i in range(self._run_len):
                 self.step()
                 if callback is not None:
-                    callback(i, int(self.timesteps[i]), self._state.x)
+                    callback(i, int(self._run_timesteps[i]), self._state.x)
             return self._state.x.clone()

@@ -457,6 +457,45 @@ int ddpm_sample_multistep(float* x, float* xs, float* hist, const void* model_ou
                           int64_t per_row, int I, int cfg, float guidance_scale, int dtype, void* stream);
 
 /*
+ * Image-to-image starts and keep-mask steps of the latent sampler — "Making Img2Img Inference with LoRA" (README.md:287-289,
+ * scripts/run_img2img.ipynb of the reference: `pipe(image=init_image, strength=0.75)` under tune_lora_scale 0.0 / 0.7 / 1.0).
+ * diffusers' img2img / inpaint pipelines are not part of the reference tree: the definitions are restated, parity unpinned
+ * beyond this repository's own float64 restatement (tests/partial_reference.py).
+ *   ddpm_sample_init_from : the noised start of a run that begins at table row `start`:
+ *           x = fp32(k·init) + fp32(n·ε)                       (each product rounded on its own, the sum once: no fma)
+ *       ε = the x_T draw of ddpm_sample_init at equal seed (Philox stream 3, key (seed, 0), same counters and Box–Muller),
+ *       init fp32 [B, per_row] in model space, (k, n) = (√ᾱ, √(1−ᾱ)) at timesteps[start] — HOST arguments, like `start`: this
+ *       launch stays outside a recording, as ddpm_sample_init does.  model_in = x cast (twice under cfg), t_model =
+ *       timesteps[start], cursor = {start, seed's low word}; eps_out (nullable, fp32 [B, per_row]) gets ε.
+ *   ddpm_sample_step_keep / ddpm_sample_multistep_keep : the contracts of ddpm_sample_step / ddpm_sample_multistep with x' —
+ *       the state the method produced, variance noise included — replaced by
+ *           x = fp32(m·y) + fp32((1 − m)·x'),      y = fp32(k_i·init) + fp32(n_i·ε)
+ *       before model_in is written (model_in is the blended state; SAVE and PUSH read the state before the update, as they
+ *       did).  m = mask fp32 [B, hw] in [0, 1] (not checked), broadcast over the per_row / hw channels: 1 holds the original, 0
+ *       resamples; (k_i, n_i) = keep_coef[i], fp32 [S, 2] next to coef: (√ᾱ, √(1−ᾱ)) at the model timestep of the NEXT
+ *       evaluation, (1, 0) in the last row (sampling.keep_schedule, float64 rounded once); ε regenerated from cursor[1] — no
+ *       noise buffer, nothing extra read per step.  Where m == 1 the result is y, where m == 0 it is the bits of the entry
+ *       without a mask.  The same kernels as the plain entries, instantiated over a parameter block that carries the three
+ *       pointers: the plain instantiations are unchanged.
+ * 4-element accesses when per_row % 4 == 0, hw % 4 == 0 (a group of four then lies inside one channel: its mask values are
+ * consecutive) and every pointer is aligned to 4 of its elements; element by element, mask index per element, otherwise — the
+ * same bits.  A cursor outside [0, S) reads and writes nothing.  LORA_E_BADARG for a null pointer (eps_out, z_out excepted),
+ * an unknown dtype, B, per_row, hw or S < 1, per_row % hw != 0, start outside [0, S) — before any HIP call.  No workspace,
+ * nothing retained, capturable.
+ */
+int ddpm_sample_init_from(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps, const float* init,
+                          float* eps_out /* nullable */, int B, int64_t per_row, int S, int start, float k, float n, int cfg,
+                          uint64_t seed, int dtype, void* stream);
+int ddpm_sample_step_keep(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+                          const int64_t* timesteps, const float* coef, float* z_out /* nullable */, const float* mask,
+                          const float* init, const float* keep_coef, int B, int64_t per_row, int64_t hw, int S, int cfg,
+                          float guidance_scale, int dtype, void* stream);
+int ddpm_sample_multistep_keep(float* x, float* xs, float* hist, const void* model_out, void* model_in, int64_t* t_model,
+                               const int* cursor, const int64_t* timesteps, const float* coef, const int* plan,
+                               const float* mask, const float* init, const float* keep_coef, int B, int64_t per_row, int64_t hw,
+                               int I, int cfg, float guidance_scale, int dtype, void* stream);
+
+/*
  * The two ops sandwiched by the hot path inside a transformer block, as streaming kernels.
  *   geglu_gate_fwd : out[M,C]  = h · gelu(g)  with [h | g] = y[M,2C], exact (erf) gelu — the body of diffusers'
  *                    GEGLU.forward, the caller of the `proj` LoraInjectedLinear (target class "GEGLU", lora.py:53).

@@ -17,8 +17,14 @@ iteration (ddpm_sample_multistep) is timed next to a replayed DDPM iteration (dd
 num_model_evaluations iterations (plms: steps + 1); their stock route keeps the history in a Python list of tensors, as a
 diffusers scheduler does.  One readable line per repetition and configuration, medians and one JSON line per configuration.
 
+--strength S adds an image-to-image route per configuration — `img2img`: a replayed LatentSampler begun from a random start
+image at that strength, min(int(steps·S), steps) grid steps — and --keep-mask a second one, `img2img+mask`, with a keep mask of
+8×8 blocks (ddpm_sample_*_keep).  They alternate with the full run's routes in the same process; every route is reported per
+iteration of ITS run (a partial run has fewer), with the spread (min – max) of its repetitions.
+
     python tools/sample_time.py [--reps 5] [--steps 50] [--batch 4]
     python tools/sample_time.py --batch 1 --method ddpm plms dpmpp_2m --steps 50 50 20
+    python tools/sample_time.py --batch 1 --method plms --steps 50 --strength 0.75 --keep-mask
 """
 import argparse
 import json
@@ -107,8 +113,8 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
-def routes_for(unet, method, steps, guidance, cond, neg, shape, gen):
-    """(replayed sampler, {route: callable}, iterations of one run) of one configuration."""
+def routes_for(unet, method, steps, guidance, cond, neg, shape, gen, strength=None, keep_mask=False):
+    """(replayed sampler, {route: callable}, {route: iterations of its run}) of one configuration."""
     replayed = dfa.LatentSampler(unet, steps, guidance, method=method)
     host = dfa.LatentSampler(unet, steps, guidance, method=method, capture_graph=False)
     if method in dfa.sampling.MULTISTEP_METHODS:
@@ -119,11 +125,25 @@ def routes_for(unet, method, steps, guidance, cond, neg, shape, gen):
         ts, coef = dfa.sampler_schedule(method, steps, False)
         ts_dev, coef_host = ts.to("cuda"), [tuple(float(v) for v in row) for row in coef]
         stock = lambda: stock_loop(unet, cond, neg, steps, guidance, shape, ts_dev, coef_host, gen)  # noqa: E731
-    return replayed, {
+    routes = {
         "replayed": lambda: replayed.sample(cond, neg, seed=7, latent_shape=shape),
         "host": lambda: host.sample(cond, neg, seed=7, latent_shape=shape),
         "stock": stock,
-    }, replayed.num_model_evaluations
+    }
+    iterations = {name: replayed.num_model_evaluations for name in routes}
+    if strength is not None:
+        g = torch.Generator().manual_seed(4)
+        init = torch.randn(cond.shape[0], *shape, generator=g).to("cuda")
+        yy, xx = torch.arange(shape[1]).view(-1, 1) // 8, torch.arange(shape[2]).view(1, -1) // 8
+        mask = ((yy + xx) % 2).float().expand(cond.shape[0], 1, -1, -1).contiguous().to("cuda")
+        for name, m in (("img2img", None),) + ((("img2img+mask", mask),) if keep_mask else ()):
+            sampler = dfa.LatentSampler(unet, steps, guidance, method=method)  # (a sampler each: the recording depends on the mask)
+            routes[name] = lambda sampler=sampler, m=m: sampler.sample(cond, neg, seed=7, init_latents=init, strength=strength,
+                                                                       keep_mask=m)
+            sampler.begin(cond, neg, seed=7, init_latents=init, strength=strength, keep_mask=m)  # (records; counts the run)
+            assert sampler.replaying, "the recording failed: the image-to-image route would measure host launches"
+            iterations[name] = sampler.run_evaluations
+    return replayed, routes, iterations
 
 
 def main():
@@ -132,6 +152,8 @@ def main():
     ap.add_argument("--steps", type=int, nargs="+", default=[50])
     ap.add_argument("--method", nargs="+", default=["ddpm"], choices=dfa.sampling.METHODS + dfa.sampling.MULTISTEP_METHODS)
     ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--strength", type=float, default=None, help="add a replayed image-to-image route at this strength")
+    ap.add_argument("--keep-mask", action="store_true", help="with --strength: add the route with a keep mask too")
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps must be at least 5")
@@ -139,6 +161,8 @@ def main():
         a.steps = a.steps * len(a.method)
     if len(a.steps) != len(a.method):
         ap.error("--steps takes one value, or one per --method")
+    if a.keep_mask and a.strength is None:
+        ap.error("--keep-mask needs --strength")
     unet, ctx_dim = build_unet()
     shape = (4, 64, 64)
     g = torch.Generator().manual_seed(2)
@@ -148,7 +172,7 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(3)
     configs = {}
     for method, steps in zip(a.method, a.steps):
-        configs[f"{method} {steps}"] = (method, steps, *routes_for(unet, method, steps, guidance, cond, neg, shape, gen))
+        configs[f"{method} {steps}"] = (method, steps, *routes_for(unet, method, steps, guidance, cond, neg, shape, gen, a.strength, a.keep_mask))
     first, same = {}, {}
     for label, (_, _, replayed, routes, _) in configs.items():  # untimed round: recording, solver searches, allocator
         first[label] = {name: timed(fn) for name, fn in routes.items()}
@@ -162,13 +186,17 @@ def main():
             for name, fn in routes.items():
                 times[label][name].append(timed(fn)[0])
             print(f"[{label}] rep {rep}: " + ", ".join(f"{k} {times[label][k][-1]:.1f} ms" for k in routes), flush=True)
-    for label, (method, steps, _, _, n_it) in configs.items():
+    for label, (method, steps, _, _, its) in configs.items():
         med = {k: statistics.median(v) for k, v in times[label].items()}
-        print(f"[{label}] medians over {n_it} iterations: " +
-              ", ".join(f"{k} {v:.1f} ms ({v / n_it:.2f} ms/iteration)" for k, v in med.items()), flush=True)
+        print(f"[{label}] medians: " + ", ".join(f"{k} {v:.1f} ms over {its[k]} iterations = {v / its[k]:.3f} ms/iteration "
+                                                 f"(spread {min(times[label][k]) / its[k]:.3f} – {max(times[label][k]) / its[k]:.3f})"
+                                                 for k, v in med.items()), flush=True)
+        n_it = its["replayed"]
         print(json.dumps({"gpu": torch.cuda.get_device_name(0), "unet": "sd15", "batch": a.batch, "rows": 2 * a.batch,
-                          "method": method, "steps": steps, "iterations": n_it, "dtype": "f16", "guidance": guidance,
+                          "method": method, "steps": steps, "iterations": n_it, "route_iterations": its, "strength": a.strength,
+                          "dtype": "f16", "guidance": guidance,
                           "reps": a.reps, "median_ms": med, "all_ms": times[label],
+                          "ms_per_iteration": {k: v / its[k] for k, v in med.items()},
                           "first_round_ms": {k: v[0] for k, v in first[label].items()}, "replayed_equals_host": same[label],
                           "stock_over_replayed": med["stock"] / med["replayed"],
                           "host_over_replayed": med["host"] / med["replayed"]}), flush=True)
