@@ -53,6 +53,10 @@ SIGNATURES = {
     "lora_linear_fwd_ws": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _i64,
                                   _vp]),
     "lora_linear_geglu_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "lora_linear_fwd_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp, _i32, _i32,
+                                    _i32, _vp, _i64, _vp]),
+    "lora_linear_geglu_fwd_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp, _i32,
+                                          _i32, _i32, _vp]),
     "lora_linear_bwd_input": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
     "lora_linear_bwd_params": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
     "lora_reduce_partials": (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp]),
@@ -93,6 +97,12 @@ SIGNATURES = {
                                      _i32, _vp]),
     "ddpm_sample_step_keep": (_i32, [_vp] * 11 + [_i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp]),
     "ddpm_sample_multistep_keep": (_i32, [_vp] * 13 + [_i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp]),
+    "ddpm_sample_init_shared": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, ctypes.c_uint64, _i32, _vp]),
+    "ddpm_sample_step_shared": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _vp]),
+    "ddpm_sample_init_from_shared": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _f32, _i32,
+                                            ctypes.c_uint64, _i32, _vp]),
+    "ddpm_sample_step_keep_shared": (_i32, [_vp] * 11 + [_i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp]),
+    "ddpm_sample_multistep_keep_shared": (_i32, [_vp] * 13 + [_i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp]),
     "embed_rows_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "embed_rows_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp]),
     "lora_adamw_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
@@ -295,6 +305,58 @@ def lora_linear_geglu_fwd(x2, w, bias, r: int, scale: float, packs, want_y: bool
     if st == -5:
         return None
     _check(st, "lora_linear_geglu_fwd")
+    return out, y, t
+
+
+def _require_row_scales(table, M: int, r: int, what: str) -> None:
+    """The gate table of a `_rows` entry: fp32 [n_samples, R >= r] on the device, rows dense, M a multiple of n_samples."""
+    _require_device(table)
+    if table.dtype != torch.float32 or table.dim() != 2 or table.stride(1) != 1:
+        raise ValueError(f"{what}: the gate table must be a float32 [n_samples, R] tensor with dense rows")
+    if table.shape[0] < 1 or M % table.shape[0] != 0 or table.shape[1] < r:
+        raise ValueError(f"{what}: a [{table.shape[0]}, {table.shape[1]}] gate table does not fit {M} rows at rank {r}")
+
+
+def lora_linear_fwd_rows(x2, w, bias, a, b, scale: float, row_scales, packs=None):
+    """`lora_linear_fwd` with per-sample, per-rank-slot gates: row_scales fp32 [n_samples, R >= r], sample b = rows
+    [b·M/n_samples, (b+1)·M/n_samples) of x2, effective factor scale·row_scales[b, j].  Inference only.  Returns (y, T)."""
+    _require_device(x2, w, bias, a, b)
+    M, K = x2.shape
+    N, r = b.shape
+    _require_row_scales(row_scales, M, r, "lora_linear_fwd_rows")
+    if packs is None:
+        packs = lora_pack_factors(a, b, x2.dtype)
+    y = torch.empty((M, N), dtype=x2.dtype, device=x2.device)
+    t = torch.empty((M, r), dtype=torch.float32, device=x2.device)
+    ws = _splitk_workspace(M, K, N, x2)
+    _check(
+        lib().lora_linear_fwd_rows(_ptr(x2), _ptr(w), _ptr(bias), _ptr(a), _ptr(b), _ptr(packs[0]), _ptr(packs[1]), _ptr(y),
+                                   _ptr(t), M, K, N, r, float(scale), _ptr(row_scales), row_scales.shape[0],
+                                   row_scales.stride(0), dtype_code(x2.dtype), _ptr(ws), 0 if ws is None else ws.numel() * 4,
+                                   _stream(x2)),
+        "lora_linear_fwd_rows",
+    )
+    return y, t
+
+
+def lora_linear_geglu_fwd_rows(x2, w, bias, r: int, scale: float, row_scales, packs, want_y: bool):
+    """`lora_linear_geglu_fwd` with the gates of `lora_linear_fwd_rows`; None when the library has no fused kernel for the
+    shape / dtype."""
+    _require_device(x2, w, bias)
+    M, K = x2.shape
+    N = w.shape[0]
+    _require_row_scales(row_scales, M, r, "lora_linear_geglu_fwd_rows")
+    if packs is None or packs[0] is None:
+        return None
+    out = torch.empty((M, N // 2), dtype=x2.dtype, device=x2.device)
+    y = torch.empty((M, N), dtype=x2.dtype, device=x2.device) if want_y else None
+    t = torch.empty((M, r), dtype=torch.float32, device=x2.device)
+    st = lib().lora_linear_geglu_fwd_rows(_ptr(x2), _ptr(w), _ptr(bias), _ptr(packs[0]), _ptr(packs[1]), _ptr(y), _ptr(out),
+                                          _ptr(t), M, K, N, r, float(scale), _ptr(row_scales), row_scales.shape[0],
+                                          row_scales.stride(0), dtype_code(x2.dtype), _stream(x2))
+    if st == -5:
+        return None
+    _check(st, "lora_linear_geglu_fwd_rows")
     return out, y, t
 
 
@@ -683,6 +745,11 @@ class SampleState:
     (k, n) per table row (sampling.keep_schedule) — a mask needs both others."""
 
     init = mask = keep_coef = None
+    shared_noise = False  # True: the `_shared` entries — every sample takes the draws of the B = 1 run of the same seed
+
+    def _entry(self, name: str):
+        """The library entry `name`, or its `_shared` form when the state draws shared noise."""
+        return getattr(lib(), name + "_shared" if self.shared_noise else name)
 
     def _set_keep(self, x, S, init, mask, keep_coef):
         B, per_row = x.shape[0], x[0].numel()
@@ -743,7 +810,7 @@ class SampleState:
 
 def ddpm_sample_init(st: SampleState, seed: int) -> None:
     """x_T ~ N(0,1) (Philox stream 3, key (seed, 0)) into the state, the first model input and timestep tensor, cursor = 0."""
-    _check(lib().ddpm_sample_init(_ptr(st.x), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps), st.B,
+    _check(st._entry("ddpm_sample_init")(_ptr(st.x), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps), st.B,
                                   st.per_row, st.S, int(st.cfg), int(seed) & (2**64 - 1), dtype_code(st.model_in.dtype),
                                   _stream(st.x)),
            "ddpm_sample_init")
@@ -758,7 +825,7 @@ def ddpm_sample_step(st: SampleState, model_out, guidance_scale: float, z_out=No
                          f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
     if z_out is not None and (z_out.dtype != torch.float32 or z_out.shape != st.x.shape or not z_out.is_contiguous()):
         raise ValueError(f"z_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
-    _check(lib().ddpm_sample_step(_ptr(st.x), _ptr(model_out), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor),
+    _check(st._entry("ddpm_sample_step")(_ptr(st.x), _ptr(model_out), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor),
                                   _ptr(st.timesteps), _ptr(st.coef), _ptr(z_out), st.B, st.per_row, st.S, int(st.cfg),
                                   float(guidance_scale), dtype_code(model_out.dtype), _stream(st.x)),
            "ddpm_sample_step")
@@ -772,7 +839,7 @@ def ddpm_sample_init_from(st: SampleState, seed: int, start: int, k: float, n: f
     _require_device(eps_out)
     if eps_out is not None and (eps_out.dtype != torch.float32 or eps_out.shape != st.x.shape or not eps_out.is_contiguous()):
         raise ValueError(f"eps_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
-    _check(lib().ddpm_sample_init_from(_ptr(st.x), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps),
+    _check(st._entry("ddpm_sample_init_from")(_ptr(st.x), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps),
                                        _ptr(st.init), _ptr(eps_out), st.B, st.per_row, st.S, int(start), float(k), float(n),
                                        int(st.cfg), int(seed) & (2**64 - 1), dtype_code(st.model_in.dtype), _stream(st.x)),
            "ddpm_sample_init_from")
@@ -793,7 +860,7 @@ def ddpm_sample_step_keep(st: SampleState, model_out, guidance_scale: float, z_o
                          f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
     if z_out is not None and (z_out.dtype != torch.float32 or z_out.shape != st.x.shape or not z_out.is_contiguous()):
         raise ValueError(f"z_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
-    _check(lib().ddpm_sample_step_keep(_ptr(st.x), _ptr(model_out), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor),
+    _check(st._entry("ddpm_sample_step_keep")(_ptr(st.x), _ptr(model_out), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor),
                                        _ptr(st.timesteps), _ptr(st.coef), _ptr(z_out), _ptr(st.mask), _ptr(st.init),
                                        _ptr(st.keep_coef), st.B, st.per_row, st.hw, st.S, int(st.cfg), float(guidance_scale),
                                        dtype_code(model_out.dtype), _stream(st.x)),
@@ -871,7 +938,7 @@ def ddpm_sample_multistep_keep(st: MultistepState, model_out, guidance_scale: fl
     if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
         raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
                          f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
-    _check(lib().ddpm_sample_multistep_keep(_ptr(st.x), _ptr(st.xs), _ptr(st.hist), _ptr(model_out), _ptr(st.model_in),
+    _check(st._entry("ddpm_sample_multistep_keep")(_ptr(st.x), _ptr(st.xs), _ptr(st.hist), _ptr(model_out), _ptr(st.model_in),
                                             _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps), _ptr(st.coef),
                                             _ptr(st.plan), _ptr(st.mask), _ptr(st.init), _ptr(st.keep_coef), st.B, st.per_row,
                                             st.hw, st.S, int(st.cfg), float(guidance_scale), dtype_code(model_out.dtype),

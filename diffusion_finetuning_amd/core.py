@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
-from .ops import lora_linear
+from .ops import lora_linear, lora_row_scales, set_lora_row_scales  # noqa: F401  (per-sample gates: part of this API surface)
 
 
 class LoraInjectedLinear(nn.Module):
@@ -213,6 +213,22 @@ def monkeypatch_or_replace_lora(
         source = child.linear if isinstance(child, LoraInjectedLinear) else child
         rank = r.pop(0) if isinstance(r, list) else r
         _wrap_linear(holder, name, source, rank, up=loras.pop(0), down=loras.pop(0))
+
+
+def monkeypatch_stack_lora(model, lists, target_replace_module=DEFAULT_TARGET_REPLACE):
+    """Patches `model` with K LoRA checkpoints AT ONCE: per layer the adapters' factors are stacked along the rank
+    (formats.stack_lora_lists) and installed by `monkeypatch_or_replace_lora` with r = Σ ranks.  Returns `slots`:
+    slots[k] is the slice of rank slots adapter k owns, so a `set_lora_row_scales` table that is open on slots[k] only
+    makes a sample see adapter k alone, and an all-ones table the sum of all adapters — what the reference's
+    `visualize_progress` (utils.py:191-211) does with one `patch_pipe` and one sample per checkpoint, as one batch.
+    `lists`: K positional `[up0, down0, up1, …]` lists (what `.pt` files and `parse_safeloras` hold); they are not consumed.
+    A total rank of at most 16 rides on the fused MFMA kernels at the cost of one adapter; a total above 16 is allowed and
+    runs on the shape-agnostic kernels (correct, not fast), as ranks 17–64 do for a single adapter."""
+    from .formats import stack_lora_lists
+
+    stacked, slots = stack_lora_lists(lists)
+    monkeypatch_or_replace_lora(model, stacked, target_replace_module=target_replace_module, r=slots[-1].stop)
+    return slots
 
 
 def monkeypatch_remove_lora(model):

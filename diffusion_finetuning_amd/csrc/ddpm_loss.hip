@@ -633,7 +633,39 @@ struct SampleParams {
     int cfg;
     float guidance;
     uint32_t seed;
+    int64_t shared_row;        // 0: the draws of the batch (counter = element group of the [B, per_row] state); per_row: every
+                               // sample takes the draws of the B = 1 run (the *_shared entries, sample_normals4 below)
 };
+
+// The four normals of element group g (elements 4g .. 4g+3 of the [B, per_row] state) of `stream` under key (seed, step).
+//   shared_row == 0:  counter g — one stream over the whole batch (what every entry without `_shared` draws);
+//   shared_row == per_row ("equal seed" in the reference's loops: torch.manual_seed(seed) before every member of a sweep,
+//       utils.py:191-211): element j of EVERY sample takes lane j mod 4 of counter j div 4 — exactly what the B = 1 run of the
+//       same seed gives its element j.  With per_row % 4 == 0 a group lies inside one sample and maps to one counter; otherwise
+//       a group straddles counters (and samples) and is assembled element by element, at most one Philox call per counter.
+__device__ __forceinline__ void sample_normals4(int64_t g, int64_t shared_row, uint32_t stream, uint32_t seed, uint32_t step,
+                                                float z[4]) {
+    if (shared_row == 0) {
+        philox_normals4((uint64_t)g, stream, seed, step, z);
+        return;
+    }
+    const int64_t j0 = (g * 4) % shared_row;
+    if ((j0 & 3) == 0 && j0 + 4 <= shared_row) {
+        philox_normals4((uint64_t)(j0 >> 2), stream, seed, step, z);
+        return;
+    }
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+    int64_t have = -1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int64_t j = (g * 4 + e) % shared_row;
+        if ((j >> 2) != have) {
+            have = j >> 2;
+            philox_normals4((uint64_t)have, stream, seed, step, t);
+        }
+        z[e] = t[j & 3];
+    }
+}
 
 __device__ __forceinline__ float sample_update(float a, float b, float sigma, float x, float o, float z) {
 #pragma clang fp contract(off)
@@ -694,10 +726,11 @@ __device__ __forceinline__ float keep_blend(float m, float y, float xn) {
 // xn[0..3] of element group g (first element i0) blended in place.  QUAD: hw % 4 == 0 too, so the group lies inside one channel
 // of one row and its four mask values are consecutive; otherwise the mask index is computed per element.
 template <bool QUAD>
-__device__ __forceinline__ void keep_apply(const KeepParams& k, int64_t n_total, uint32_t seed, int step, int64_t g, float* xn) {
+__device__ __forceinline__ void keep_apply(const KeepParams& k, int64_t n_total, int64_t shared_row, uint32_t seed, int step,
+                                           int64_t g, float* xn) {
     const float kk = k.keep_coef[2 * step], kn = k.keep_coef[2 * step + 1];
     Quad<float> eps;
-    philox_normals4((uint64_t)g, kStreamInit, seed, 0u, eps.v);
+    sample_normals4(g, shared_row, kStreamInit, seed, 0u, eps.v);
     const int64_t i0 = g * 4;
     if constexpr (QUAD) {
         const int64_t b = i0 / k.per_row;
@@ -730,7 +763,7 @@ __global__ __launch_bounds__(256) void sample_init_kernel(SampleParams p) {
     const int64_t groups = (p.n_total + 3) >> 2;
     for (int64_t g = tid; g < groups; g += nthreads) {
         Quad<float> z;
-        philox_normals4((uint64_t)g, kStreamInit, p.seed, 0u, z.v);
+        sample_normals4(g, p.shared_row, kStreamInit, p.seed, 0u, z.v);
         const int64_t i0 = g * 4;
         if constexpr (QUAD) {
             *reinterpret_cast<Quad<float>*>(p.x + i0) = z;
@@ -758,7 +791,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(P p) {
     for (int64_t g = tid; g < groups; g += nthreads) {
         Quad<float> z;
         if (sigma != 0.f) {
-            philox_normals4((uint64_t)g, kStreamStepNoise, seed, (uint32_t)step, z.v);
+            sample_normals4(g, p.shared_row, kStreamStepNoise, seed, (uint32_t)step, z.v);
         } else {
             z.v[0] = z.v[1] = z.v[2] = z.v[3] = 0.f;
         }
@@ -775,7 +808,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(P p) {
                 const float o = p.cfg ? guided(uf, to_f32<T>(c.v[e]), p.guidance) : uf;
                 xn.v[e] = sample_update(a, b, sigma, x.v[e], o, z.v[e]);
             }
-            if constexpr (KEEP) keep_apply<true>(p.k, p.n_total, seed, step, g, xn.v);
+            if constexpr (KEEP) keep_apply<true>(p.k, p.n_total, p.shared_row, seed, step, g, xn.v);
             *reinterpret_cast<Quad<float>*>(p.x + i0) = xn;
             if (p.z_out) *reinterpret_cast<Quad<float>*>(p.z_out + i0) = z;
         } else {
@@ -790,7 +823,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(P p) {
                 if (p.z_out) p.z_out[i] = z.v[e];
             }
             if constexpr (KEEP) {
-                keep_apply<false>(p.k, p.n_total, seed, step, g, xn.v);
+                keep_apply<false>(p.k, p.n_total, p.shared_row, seed, step, g, xn.v);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (i0 + e < p.n_total) p.x[i0 + e] = xn.v[e];
@@ -915,7 +948,7 @@ __global__ __launch_bounds__(256) void sample_multistep_kernel(P m) {
                 h.v[e] = multistep_history(kp, kq, x.v[e], o);
                 xn.v[e] = multistep_update(a, c0, c1, c2, c3, base.v[e], h.v[e], h1.v[e], h2.v[e], h3.v[e]);
             }
-            if constexpr (KEEP) keep_apply<true>(m.k, p.n_total, (uint32_t)p.cursor[1], it, g, xn.v);
+            if constexpr (KEEP) keep_apply<true>(m.k, p.n_total, p.shared_row, (uint32_t)p.cursor[1], it, g, xn.v);
             if (save) *reinterpret_cast<Quad<float>*>(m.xs + i0) = x;
             if (push) *reinterpret_cast<Quad<float>*>(hw + i0) = h;
             *reinterpret_cast<Quad<float>*>(p.x + i0) = xn;
@@ -936,7 +969,7 @@ __global__ __launch_bounds__(256) void sample_multistep_kernel(P m) {
                 if constexpr (!KEEP) p.x[i] = xn.v[e];
             }
             if constexpr (KEEP) {
-                keep_apply<false>(m.k, p.n_total, (uint32_t)p.cursor[1], it, g, xn.v);
+                keep_apply<false>(m.k, p.n_total, p.shared_row, (uint32_t)p.cursor[1], it, g, xn.v);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (i0 + e < p.n_total) p.x[i0 + e] = xn.v[e];
@@ -984,19 +1017,32 @@ extern "C" int ddpm_sample_multistep(float* x, float* xs, float* hist, const voi
     return LORA_OK;
 }
 
-extern "C" int ddpm_sample_init(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps, int B,
-                                int64_t per_row, int S, int cfg, uint64_t seed, int dtype, void* stream) {
+namespace {
+int ddpm_sample_init_impl(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps, int B,
+                                int64_t per_row, int S, int cfg, uint64_t seed, int dtype, void* stream, bool shared) {
     if (!x || !model_in || !t_model || !cursor || !timesteps || B < 1 || per_row < 1 || S < 1 || !known_dtype(dtype))
         return LORA_E_BADARG;
     SampleParams p{};
     p.x = x; p.in = model_in; p.t_model = t_model; p.cursor = cursor; p.timesteps = timesteps;
     p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = S; p.cfg = cfg ? 1 : 0; p.seed = (uint32_t)seed;
+    p.shared_row = shared ? per_row : 0;
     return launch_sample_dtype(p, per_row, true, dtype, static_cast<hipStream_t>(stream));
 }
+}  // namespace
 
-extern "C" int ddpm_sample_step(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+extern "C" int ddpm_sample_init(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps, int B,
+                                int64_t per_row, int S, int cfg, uint64_t seed, int dtype, void* stream) {
+    return ddpm_sample_init_impl(x, model_in, t_model, cursor, timesteps, B, per_row, S, cfg, seed, dtype, stream, false);
+}
+extern "C" int ddpm_sample_init_shared(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps, int B,
+                                int64_t per_row, int S, int cfg, uint64_t seed, int dtype, void* stream) {
+    return ddpm_sample_init_impl(x, model_in, t_model, cursor, timesteps, B, per_row, S, cfg, seed, dtype, stream, true);
+}
+
+namespace {
+int ddpm_sample_step_impl(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
                                 const int64_t* timesteps, const float* coef, float* z_out, int B, int64_t per_row, int S,
-                                int cfg, float guidance_scale, int dtype, void* stream) {
+                                int cfg, float guidance_scale, int dtype, void* stream, bool shared) {
     if (!x || !model_out || !model_in || !t_model || !cursor || !timesteps || !coef || B < 1 || per_row < 1 || S < 1 ||
         !known_dtype(dtype))
         return LORA_E_BADARG;
@@ -1005,7 +1051,22 @@ extern "C" int ddpm_sample_step(float* x, const void* model_out, void* model_in,
     p.timesteps = timesteps; p.coef = coef; p.z_out = z_out;
     p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = S; p.cfg = cfg ? 1 : 0;
     p.guidance = guidance_scale;
+    p.shared_row = shared ? per_row : 0;
     return launch_sample_dtype(p, per_row, false, dtype, static_cast<hipStream_t>(stream));
+}
+}  // namespace
+
+extern "C" int ddpm_sample_step(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+                                const int64_t* timesteps, const float* coef, float* z_out, int B, int64_t per_row, int S,
+                                int cfg, float guidance_scale, int dtype, void* stream) {
+    return ddpm_sample_step_impl(x, model_out, model_in, t_model, cursor, timesteps, coef, z_out, B, per_row, S, cfg,
+                                 guidance_scale, dtype, stream, false);
+}
+extern "C" int ddpm_sample_step_shared(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+                                const int64_t* timesteps, const float* coef, float* z_out, int B, int64_t per_row, int S,
+                                int cfg, float guidance_scale, int dtype, void* stream) {
+    return ddpm_sample_step_impl(x, model_out, model_in, t_model, cursor, timesteps, coef, z_out, B, per_row, S, cfg,
+                                 guidance_scale, dtype, stream, true);
 }
 
 extern "C" int ddpm_sample_advance(int* cursor, int S, void* stream) {
@@ -1042,7 +1103,7 @@ __global__ __launch_bounds__(256) void sample_init_from_kernel(SampleParams p, I
     const int64_t groups = (p.n_total + 3) >> 2;
     for (int64_t g = tid; g < groups; g += nthreads) {
         Quad<float> z, x = {};
-        philox_normals4((uint64_t)g, kStreamInit, p.seed, 0u, z.v);
+        sample_normals4(g, p.shared_row, kStreamInit, p.seed, 0u, z.v);
         const int64_t i0 = g * 4;
         if constexpr (QUAD) {
             const Quad<float> init = *reinterpret_cast<const Quad<float>*>(f.init + i0);
@@ -1106,15 +1167,17 @@ bool keep_args_ok(const float* mask, const float* init, const float* keep_coef, 
 
 }  // namespace
 
-extern "C" int ddpm_sample_init_from(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps,
+namespace {
+int ddpm_sample_init_from_impl(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps,
                                      const float* init, float* eps_out, int B, int64_t per_row, int S, int start, float k,
-                                     float n, int cfg, uint64_t seed, int dtype, void* stream) {
+                                     float n, int cfg, uint64_t seed, int dtype, void* stream, bool shared) {
     if (!x || !model_in || !t_model || !cursor || !timesteps || !init || B < 1 || per_row < 1 || S < 1 || start < 0 ||
         start >= S || !known_dtype(dtype))
         return LORA_E_BADARG;
     SampleParams p{};
     p.x = x; p.in = model_in; p.t_model = t_model; p.cursor = cursor; p.timesteps = timesteps;
     p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = S; p.cfg = cfg ? 1 : 0; p.seed = (uint32_t)seed;
+    p.shared_row = shared ? per_row : 0;
     InitFromParams f{};
     f.init = init; f.eps_out = eps_out; f.start = start; f.k = k; f.n = n;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1126,11 +1189,26 @@ extern "C" int ddpm_sample_init_from(float* x, void* model_in, int64_t* t_model,
     LORA_LAUNCH_CHECK();
     return LORA_OK;
 }
+}  // namespace
 
-extern "C" int ddpm_sample_step_keep(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+extern "C" int ddpm_sample_init_from(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps,
+                                     const float* init, float* eps_out, int B, int64_t per_row, int S, int start, float k,
+                                     float n, int cfg, uint64_t seed, int dtype, void* stream) {
+    return ddpm_sample_init_from_impl(x, model_in, t_model, cursor, timesteps, init, eps_out, B, per_row, S, start, k, n,
+                                      cfg, seed, dtype, stream, false);
+}
+extern "C" int ddpm_sample_init_from_shared(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps,
+                                     const float* init, float* eps_out, int B, int64_t per_row, int S, int start, float k,
+                                     float n, int cfg, uint64_t seed, int dtype, void* stream) {
+    return ddpm_sample_init_from_impl(x, model_in, t_model, cursor, timesteps, init, eps_out, B, per_row, S, start, k, n,
+                                      cfg, seed, dtype, stream, true);
+}
+
+namespace {
+int ddpm_sample_step_keep_impl(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
                                      const int64_t* timesteps, const float* coef, float* z_out, const float* mask,
                                      const float* init, const float* keep_coef, int B, int64_t per_row, int64_t hw, int S, int cfg,
-                                     float guidance_scale, int dtype, void* stream) {
+                                     float guidance_scale, int dtype, void* stream, bool shared) {
     if (!x || !model_out || !model_in || !t_model || !cursor || !timesteps || !coef || B < 1 || S < 1 ||
         !keep_args_ok(mask, init, keep_coef, per_row, hw) || !known_dtype(dtype))
         return LORA_E_BADARG;
@@ -1140,6 +1218,7 @@ extern "C" int ddpm_sample_step_keep(float* x, const void* model_out, void* mode
     p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = S; p.cfg = cfg ? 1 : 0;
     p.guidance = guidance_scale;
     p.k = KeepParams{mask, init, keep_coef, per_row, hw};
+    p.shared_row = shared ? per_row : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (dtype) {
         case LORA_F32: launch_step_keep<float>(p, s); break;
@@ -1149,12 +1228,29 @@ extern "C" int ddpm_sample_step_keep(float* x, const void* model_out, void* mode
     LORA_LAUNCH_CHECK();
     return LORA_OK;
 }
+}  // namespace
 
-extern "C" int ddpm_sample_multistep_keep(float* x, float* xs, float* hist, const void* model_out, void* model_in,
+extern "C" int ddpm_sample_step_keep(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+                                     const int64_t* timesteps, const float* coef, float* z_out, const float* mask,
+                                     const float* init, const float* keep_coef, int B, int64_t per_row, int64_t hw, int S, int cfg,
+                                     float guidance_scale, int dtype, void* stream) {
+    return ddpm_sample_step_keep_impl(x, model_out, model_in, t_model, cursor, timesteps, coef, z_out, mask, init, keep_coef,
+                                      B, per_row, hw, S, cfg, guidance_scale, dtype, stream, false);
+}
+extern "C" int ddpm_sample_step_keep_shared(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+                                     const int64_t* timesteps, const float* coef, float* z_out, const float* mask,
+                                     const float* init, const float* keep_coef, int B, int64_t per_row, int64_t hw, int S, int cfg,
+                                     float guidance_scale, int dtype, void* stream) {
+    return ddpm_sample_step_keep_impl(x, model_out, model_in, t_model, cursor, timesteps, coef, z_out, mask, init, keep_coef,
+                                      B, per_row, hw, S, cfg, guidance_scale, dtype, stream, true);
+}
+
+namespace {
+int ddpm_sample_multistep_keep_impl(float* x, float* xs, float* hist, const void* model_out, void* model_in,
                                           int64_t* t_model, const int* cursor, const int64_t* timesteps, const float* coef,
                                           const int* plan, const float* mask, const float* init, const float* keep_coef, int B,
                                           int64_t per_row, int64_t hw, int I, int cfg, float guidance_scale, int dtype,
-                                          void* stream) {
+                                          void* stream, bool shared) {
     if (!x || !xs || !hist || !model_out || !model_in || !t_model || !cursor || !timesteps || !coef || !plan || B < 1 || I < 1 ||
         !keep_args_ok(mask, init, keep_coef, per_row, hw) || !known_dtype(dtype))
         return LORA_E_BADARG;
@@ -1166,6 +1262,7 @@ extern "C" int ddpm_sample_multistep_keep(float* x, float* xs, float* hist, cons
     p.guidance = guidance_scale;
     m.xs = xs; m.hist = hist; m.plan = plan;
     m.k = KeepParams{mask, init, keep_coef, per_row, hw};
+    p.shared_row = shared ? per_row : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (dtype) {
         case LORA_F32: launch_multistep_keep<float>(m, s); break;
@@ -1174,4 +1271,22 @@ extern "C" int ddpm_sample_multistep_keep(float* x, float* xs, float* hist, cons
     }
     LORA_LAUNCH_CHECK();
     return LORA_OK;
+}
+}  // namespace
+
+extern "C" int ddpm_sample_multistep_keep(float* x, float* xs, float* hist, const void* model_out, void* model_in,
+                                          int64_t* t_model, const int* cursor, const int64_t* timesteps, const float* coef,
+                                          const int* plan, const float* mask, const float* init, const float* keep_coef, int B,
+                                          int64_t per_row, int64_t hw, int I, int cfg, float guidance_scale, int dtype,
+                                          void* stream) {
+    return ddpm_sample_multistep_keep_impl(x, xs, hist, model_out, model_in, t_model, cursor, timesteps, coef, plan, mask,
+                                           init, keep_coef, B, per_row, hw, I, cfg, guidance_scale, dtype, stream, false);
+}
+extern "C" int ddpm_sample_multistep_keep_shared(float* x, float* xs, float* hist, const void* model_out, void* model_in,
+                                          int64_t* t_model, const int* cursor, const int64_t* timesteps, const float* coef,
+                                          const int* plan, const float* mask, const float* init, const float* keep_coef, int B,
+                                          int64_t per_row, int64_t hw, int I, int cfg, float guidance_scale, int dtype,
+                                          void* stream) {
+    return ddpm_sample_multistep_keep_impl(x, xs, hist, model_out, model_in, t_model, cursor, timesteps, coef, plan, mask,
+                                           init, keep_coef, B, per_row, hw, I, cfg, guidance_scale, dtype, stream, true);
 }

@@ -34,6 +34,9 @@
 //   - SPLITK instantiations (long contractions on grids too small for the chip): the K-slices of a tile are workgroups of the
 //     SAME launch; each stores its fp32 partials write-through (sc1), draws a ticket, and the last arriver adds the slices in
 //     index order and runs the epilogue above — deterministic, no second launch (plan_splitk()).
+//   - RS instantiations (forward, inference: lora_linear_fwd_rows / lora_linear_geglu_fwd_rows): the factor s of the rank-r term
+//     becomes s·G[sample of the row, rank slot] from an fp32 gate table — formed in fp32 FIRST, then multiplied into P, wherever
+//     an epilogue form builds s·P; instantiations of their own, so that every other kernel is compiled exactly as before.
 // Workgroups are dealt to XCDs so that the column tiles of one row panel (or the row tiles of one column panel, whichever
 // re-fetches the smaller operand) share an L2 — or, for square-ish problems, so that each XCD owns a rectangle of the tile grid.
 // Tile / ring / split choice per shape: launch_pipe(), gate_tile_width(), plan_splitk() — all measured with cold weights.
@@ -90,6 +93,12 @@ struct GemmParams {
     // epilogue writes C2[M, gateF] = h·gelu(g) next to C (C may be null: nothing is saved for a backward pass).
     void* C2;
     int gateF;
+    // Per-row gates of the rank-r term (RS kernels; inference only): row m multiplies rank slot j with scale·row_scale[(m /
+    // rs_rps)·rs_ld + j] instead of scale — the fp32 table holds one row of gates per SAMPLE, a sample is rs_rps consecutive
+    // rows of Am.  P is written out un-gated.  Unused (null) in every other instantiation.
+    const float* row_scale;
+    int64_t rs_rps;
+    int rs_ld;
 };
 
 constexpr int kRowBytes = 128;  // one K-step of one tile row
@@ -162,7 +171,8 @@ template <int BM, int BN, typename T, bool MAIN, int STG, int NW, int WM> conste
 // SPLITK: the launch cuts its contraction into K-slices (in-launch combine, below) — instantiations of their own, so that the
 // unsplit kernels carry none of that code and profilers can tell the two apart by name
 // KP > 1: the contraction consists of KP equal parts with a factor pair each (grouped q/k/v backward-input at 3r > 16)
-template <typename T, int BM, int BN, bool MAIN, int STG, int NW, int WM, int GATE = 0, bool SPLITK = false, int KP = 1>  // GATE: 0 none, 1 GEGLU forward, 2 GEGLU backward
+// RS: per-row gates of the rank-r term from GemmParams::row_scale (forward launches of one layer)
+template <typename T, int BM, int BN, bool MAIN, int STG, int NW, int WM, int GATE = 0, bool SPLITK = false, int KP = 1, bool RS = false>  // GATE: 0 none, 1 GEGLU forward, 2 GEGLU backward
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void lora_gemm_kernel(GemmParams p) {  // 4-wave tiles: two per CU
     constexpr bool PIPE = STG > 0;
     constexpr int kStages = PIPE ? STG : 1;
@@ -688,6 +698,18 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void lora_gemm_kernel(Gem
             __syncthreads();
         }
     }
+    static_assert(!RS || (MAIN && GATE != 2 && KP == 1), "row gates exist on the single-layer forward kernels");
+    // RS: factor of rank slot j in tile row `row` — scale·G[sample][j], formed in fp32 before it meets P (slots >= r hold P = 0 and
+    // have no table column: factor 0; rows past M read the last row's sample and are never stored)
+    auto gate_row = [&](int row) -> const float* {
+        int64_t m = m0 + row;
+        if (m > p.M - 1) m = p.M - 1;
+        return p.row_scale + (m / p.rs_rps) * p.rs_ld;
+    };
+    auto gate_factor = [&](const float* g, int j) -> float {
+        const float f = p.scale * g[j < p.r ? j : p.r - 1];
+        return j < p.r ? f : 0.f;
+    };
     constexpr bool PACKED_P = MAIN && !F32 && PIPE;  // the rank-r term's operand is built ONCE per row, cooperatively
     constexpr int kPkStride = 80;                     // bytes per row of the packed image [hi j0..15 | lo j0..15] (+16 pad)
     char* const sPk = reinterpret_cast<char*>(sP) + QOFF + (MAIN ? BN * kRP * (int)sizeof(T) : 0);
@@ -714,9 +736,17 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void lora_gemm_kernel(Gem
                     if (half * 8 + e < p.r) Pout[(m0 + row) * p.ldp + part * p.r + half * 8 + e] = v[e];
             }
             Chunk<T> hi, lo;
+            float fac[8];
+            if constexpr (RS) {
+                const float* g = gate_row(row);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) fac[e] = gate_factor(g, half * 8 + e);
+            }
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float sv = v[e] * p.scale;
+                float sv;
+                if constexpr (RS) sv = v[e] * fac[e];
+                else sv = v[e] * p.scale;
                 hi.v[e] = from_f32<T>(sv);
                 lo.v[e] = from_f32<T>(sv - to_f32<T>(hi.v[e]));
             }
@@ -819,12 +849,19 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void lora_gemm_kernel(Gem
 #pragma unroll
                 for (int i = 0; i < MG; ++i) {
                     Frag pf;
+                    float fac[8];
+                    if constexpr (RS) {
+                        const float* g = gate_row(wm * WTM + (mg + i) * 16 + l15);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) fac[e] = gate_factor(g, j0 + e);
+                    }
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         float v = 0.f;
 #pragma unroll
                         for (int w = 0; w < WN; ++w) v += pimg[i][w][e >> 2][e & 3];
-                        v *= p.scale;
+                        if constexpr (RS) v *= fac[e];
+                        else v *= p.scale;
                         const T hi = from_f32<T>(v);
                         const T lo = from_f32<T>(v - to_f32<T>(hi));
                         pf[e] = lq < 2 ? hi : lo;
@@ -848,7 +885,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void lora_gemm_kernel(Gem
                     float pv = 0.f;
 #pragma unroll
                     for (int w = 0; w < WN; ++w) pv += sP[(w * BM + row) * kSPS + j];
-                    pv *= p.scale;
+                    if constexpr (RS) pv *= gate_factor(gate_row(row), j);
+                    else pv *= p.scale;
 #pragma unroll
                     for (int ni = 0; ni < NI; ++ni)
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(qv[ni], pv, acc[mi][ni], 0, 0, 0);
@@ -1030,6 +1068,9 @@ struct GenericParams {
     int64_t M;
     int Kc, Nc, r;
     float scale;
+    const float* row_scale;  // RS kernel: per-sample gates (GemmParams::row_scale)
+    int64_t rs_rps;
+    int rs_ld;
 };
 template <typename T>
 __global__ void lora_skinny_generic_kernel(GenericParams p) {
@@ -1042,7 +1083,14 @@ __global__ void lora_skinny_generic_kernel(GenericParams p) {
     for (int k = 0; k < p.Kc; ++k) s += to_f32<T>(a[k]) * to_f32<T>(from_f32<T>(p.F[j * p.f_sr + k * p.f_sk]));
     p.P[idx] = s;
 }
-template <typename T>
+// f − f0 with f = scale·g rounded on its own: contracted into one fma the difference of two EQUAL factors would be the product's
+// rounding error instead of zero
+__device__ __forceinline__ float gate_deviation(float scale, float g, float f0) {
+#pragma clang fp contract(off)
+    const float f = scale * g;
+    return f - f0;
+}
+template <typename T, bool RS = false>
 __global__ void lora_gemm_generic_kernel(GenericParams p) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= p.M * p.Nc) return;
@@ -1053,9 +1101,28 @@ __global__ void lora_gemm_generic_kernel(GenericParams p) {
     float s = 0.f;
     for (int k = 0; k < p.Kc; ++k) s += to_f32<T>(a[k]) * to_f32<T>(b[k]);
     float l = 0.f;
+    if constexpr (RS) {
+        // This kernel's ungated form scales the SUM, s·(Σ_j P_j·Q_j) — there is no per-row s·P to put a factor into, as the MFMA
+        // epilogues have.  With f_j = scale·G[sample][j] (formed first, in fp32) the gated form is that same arithmetic at the
+        // factor of slot 0 plus the other slots' deviations from it,
+        //     Σ_j f_j·P_j·Q_j = f_0·(Σ_j P_j·Q_j) + Σ_j ((f_j − f_0)·P_j)·Q_j ,
+        // so a row whose gates are all equal — a uniform table, a table of ones under any scale, a closed sample — is the
+        // ungated launch at that factor bit for bit (every deviation is an exact zero), as it is on the MFMA forms.
+        const float* g = p.row_scale + (m / p.rs_rps) * p.rs_ld;
+        const float f0 = p.scale * g[0];
+        float dev = 0.f;
+        for (int j = 0; j < p.r; ++j) {
+            const float q = to_f32<T>(from_f32<T>(p.Q[(int64_t)n * p.q_sn + j * p.q_sj]));
+            l += p.P[m * p.r + j] * q;
+            dev += (gate_deviation(p.scale, g[j], f0) * p.P[m * p.r + j]) * q;
+        }
+        s += f0 * l;
+        s += dev;
+    } else {
     for (int j = 0; j < p.r; ++j)
         l += p.P[m * p.r + j] * to_f32<T>(from_f32<T>(p.Q[(int64_t)n * p.q_sn + j * p.q_sj]));
     s += p.scale * l;
+    }
     if (p.bias) s += to_f32<T>(static_cast<const T*>(p.bias)[n]);
     static_cast<T*>(p.C)[idx] = from_f32<T>(s);
 }
@@ -1186,6 +1253,32 @@ int launch_tile(GemmParams p, hipStream_t stream) {
     }
     constexpr int lds = gemm_lds_bytes<BM, BN, T, MAIN, STG, NW, WM>();
     constexpr bool CAN_SPLIT = MAIN && STG > 0 && NW == 4 && BN == 128 && (BM == 64 || BM == 128);  // what plan_splitk hands out
+    if constexpr (MAIN) {
+        if (p.row_scale != nullptr) {  // per-row gates: the RS twin of whatever kernel the shape would run on
+            if (p.tile_part != nullptr || p.n_parts != 0) return LORA_E_UNSUPPORTED;  // (grouped launches carry no gates)
+            if constexpr (CAN_SPLIT) {
+                if (p.splitk > 1) {
+                    auto kern = lora_gemm_kernel<T, BM, BN, MAIN, STG, NW, WM, 0, true, 1, true>;
+                    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+                    if (attr != hipSuccess) return LORA_E_LAUNCH;
+                    p.ws_c = reinterpret_cast<float*>(reinterpret_cast<char*>(p.tickets) + kTicketBytes);
+                    p.ws_p = p.ws_c + (int64_t)p.tiles_m * p.tiles_n * p.splitk * (BM * BN);
+                    LORA_LAUNCH(PK_GEMM_SPLITK, kern, dim3(p.tiles_m * p.tiles_n * p.splitk), dim3(NW * 64), lds, stream, p);
+                    LORA_LAUNCH_CHECK();
+                    return LORA_OK;
+                }
+            }
+            p.splitk = 0;
+            auto kern = lora_gemm_kernel<T, BM, BN, MAIN, STG, NW, WM, 0, false, 1, true>;
+            static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            if (attr != hipSuccess) return LORA_E_LAUNCH;
+            LORA_LAUNCH(BM == 128 ? PK_GEMM_128x128 : PK_GEMM_64x64, kern, dim3(p.tiles_m * p.tiles_n), dim3(NW * 64), lds, stream, p);
+            LORA_LAUNCH_CHECK();
+            return LORA_OK;
+        }
+    }
     if constexpr (CAN_SPLIT) {
         if (p.splitk > 1) {  // workspace = [tickets | fp32 tiles | P tiles] (splitk_ws_bytes)
             auto kern = lora_gemm_kernel<T, BM, BN, MAIN, STG, NW, WM, 0, true>;
@@ -1237,6 +1330,15 @@ int launch_gate_bn(GemmParams p, hipStream_t stream) {
     p.ldp = p.r;
     p.col_major = (int64_t)p.Nc > p.M ? 1 : 0;
     constexpr int lds = gemm_lds_bytes<BM, BN, T, true, 2, 4, 2>();
+    if (p.row_scale != nullptr) {  // per-row gates of the rank-r term: the RS twin
+        auto kern = lora_gemm_kernel<T, BM, BN, true, 2, 4, 2, 1, false, 1, true>;
+        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (attr != hipSuccess) return LORA_E_LAUNCH;
+        LORA_LAUNCH(PK_GEMM_128x128, kern, dim3(p.tiles_m * p.tiles_n), dim3(256), lds, stream, p);
+        LORA_LAUNCH_CHECK();
+        return LORA_OK;
+    }
     auto kern = lora_gemm_kernel<T, BM, BN, true, 2, 4, 2, 1>;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -1404,6 +1506,9 @@ struct CallArgs {  // what an entry point knows
     bool packed_only;          // no fp32 masters behind Fp/Qp: the shape-agnostic kernels cannot run
     void* workspace;           // optional fp32 scratch for split-K (lora_gemm_workspace_bytes)
     int64_t ws_bytes;
+    const float* row_scale;    // per-sample gates of the rank-r term (forward of one layer; null = none)
+    int64_t rs_rps;            // rows per sample
+    int rs_ld;                 // row stride of the table in floats
 };
 
 template <typename T>
@@ -1420,6 +1525,7 @@ int launch_typed(const CallArgs& c, bool main_part, hipStream_t stream) {
         p.Am = c.Am; p.Bm = c.Bm; p.bias = c.bias; p.Fp = c.Fp; p.Qp = c.Qp;
         p.C = c.C; p.P = c.P; p.M = c.M; p.Kc = c.Kc; p.Nc = c.Nc; p.r = c.r; p.scale = c.scale;
         p.lda = lda; p.tile_part = c.tile_part; p.part_table = c.part_table; p.tiles_n = c.n_parts;
+        p.row_scale = c.row_scale; p.rs_rps = c.rs_rps; p.rs_ld = c.rs_ld;
         if (main_part && !grouped && c.workspace != nullptr && aligned16(c.workspace) && (c.Kc % BK) == 0) {
             const SplitPlan sp = plan_splitk(c.M, c.Kc, c.Nc, (int)sizeof(T));
             if (sp.S > 1 && c.ws_bytes >= splitk_ws_bytes(c.M, c.Nc, sp)) {
@@ -1439,6 +1545,7 @@ int launch_typed(const CallArgs& c, bool main_part, hipStream_t stream) {
     g.Am = c.Am; g.Bm = c.Bm; g.bias = c.bias; g.F = c.F; g.f_sr = c.f_sr; g.f_sk = c.f_sk; g.Q = c.Q;
     g.q_sn = c.q_sn; g.q_sj = c.q_sj; g.C = c.C; g.P = c.P; g.M = c.M; g.Kc = c.Kc; g.Nc = c.Nc; g.r = c.r;
     g.scale = c.scale;
+    g.row_scale = c.row_scale; g.rs_rps = c.rs_rps; g.rs_ld = c.rs_ld;
     {
         const int64_t n = g.M * g.r;
         hipLaunchKernelGGL(lora_skinny_generic_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g);
@@ -1446,6 +1553,9 @@ int launch_typed(const CallArgs& c, bool main_part, hipStream_t stream) {
     }
     if (main_part) {
         const int64_t n = g.M * g.Nc;
+        if (g.row_scale != nullptr)
+            hipLaunchKernelGGL((lora_gemm_generic_kernel<T, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g);
+        else
         hipLaunchKernelGGL(lora_gemm_generic_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g);
         LORA_LAUNCH_CHECK();
     }
@@ -1565,9 +1675,39 @@ extern "C" int lora_linear_fwd(const void* X, const void* W, const void* bias, c
     return lora_linear_fwd_ws(X, W, bias, A, B, Apack, Bpack, Y, T_out, M, K, N, r, scale, dtype, nullptr, 0, stream);
 }
 
+namespace {
+int check_rows(int64_t M, int r, const float* row_scale, int n_samples, int ld_scale) {
+    if (row_scale == nullptr || n_samples < 1 || M % n_samples != 0 || ld_scale < r) return LORA_E_BADARG;
+    return LORA_OK;
+}
+int linear_fwd(const void* X, const void* W, const void* bias, const float* A, const float* B, const void* Apack,
+               const void* Bpack, void* Y, float* T_out, int64_t M, int K, int N, int r, float scale, const float* row_scale,
+               int n_samples, int ld_scale, int dtype, void* workspace, int64_t ws_bytes, void* stream);
+}  // namespace
+
 extern "C" int lora_linear_fwd_ws(const void* X, const void* W, const void* bias, const float* A, const float* B,
                                   const void* Apack, const void* Bpack, void* Y, float* T_out, int64_t M, int K, int N,
                                   int r, float scale, int dtype, void* workspace, int64_t ws_bytes, void* stream) {
+    return linear_fwd(X, W, bias, A, B, Apack, Bpack, Y, T_out, M, K, N, r, scale, nullptr, 0, 0, dtype, workspace, ws_bytes,
+                      stream);
+}
+
+extern "C" int lora_linear_fwd_rows(const void* X, const void* W, const void* bias, const float* A, const float* B,
+                                    const void* Apack, const void* Bpack, void* Y, float* T_out, int64_t M, int K, int N,
+                                    int r, float scale, const float* row_scale, int n_samples, int ld_scale, int dtype,
+                                    void* workspace, int64_t ws_bytes, void* stream) {
+    const int st = check_common(M, K, N, r, dtype);
+    if (st != LORA_OK) return st;
+    const int rs = check_rows(M, r, row_scale, n_samples, ld_scale);
+    if (rs != LORA_OK) return rs;
+    return linear_fwd(X, W, bias, A, B, Apack, Bpack, Y, T_out, M, K, N, r, scale, row_scale, n_samples, ld_scale, dtype,
+                      workspace, ws_bytes, stream);
+}
+
+namespace {
+int linear_fwd(const void* X, const void* W, const void* bias, const float* A, const float* B, const void* Apack,
+               const void* Bpack, void* Y, float* T_out, int64_t M, int K, int N, int r, float scale, const float* row_scale,
+               int n_samples, int ld_scale, int dtype, void* workspace, int64_t ws_bytes, void* stream) {
     const int st = check_common(M, K, N, r, dtype);
     if (st != LORA_OK) return st;
     if (M == 0) return LORA_OK;  // empty batch: nothing to do (pointers may be null)
@@ -1582,16 +1722,46 @@ extern "C" int lora_linear_fwd_ws(const void* X, const void* W, const void* bias
     c.C = Y; c.P = T_out;
     c.M = M; c.Kc = K; c.Nc = N; c.r = r; c.scale = scale;
     c.workspace = workspace; c.ws_bytes = ws_bytes;
+    if (row_scale != nullptr) {
+        c.row_scale = row_scale; c.rs_rps = M / n_samples; c.rs_ld = ld_scale;
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const double e = esize(dtype);
     ProfWork work(e * ((double)M * K + (double)N * K + (double)M * N) + e * r * (K + N) + (bias ? e * N : 0.0),
                   2.0 * M * K * N + 2.0 * M * r * (double)(K + N));
     return launch_gemm(c, true, dtype, s);
 }
+}  // namespace
+
+namespace {
+int linear_geglu_fwd(const void* X, const void* W, const void* bias, const void* Apack, const void* Bpack, void* Y, void* Out,
+                     float* T_out, int64_t M, int K, int N, int r, float scale, const float* row_scale, int n_samples,
+                     int ld_scale, int dtype, void* stream);
+}  // namespace
 
 extern "C" int lora_linear_geglu_fwd(const void* X, const void* W, const void* bias, const void* Apack, const void* Bpack,
                                      void* Y, void* Out, float* T_out, int64_t M, int K, int N, int r, float scale,
                                      int dtype, void* stream) {
+    return linear_geglu_fwd(X, W, bias, Apack, Bpack, Y, Out, T_out, M, K, N, r, scale, nullptr, 0, 0, dtype, stream);
+}
+
+extern "C" int lora_linear_geglu_fwd_rows(const void* X, const void* W, const void* bias, const void* Apack,
+                                          const void* Bpack, void* Y, void* Out, float* T_out, int64_t M, int K, int N, int r,
+                                          float scale, const float* row_scale, int n_samples, int ld_scale, int dtype,
+                                          void* stream) {
+    const int st = check_common(M, K, N, r, dtype);
+    if (st != LORA_OK) return st;
+    if ((N & 1) != 0) return LORA_E_BADARG;
+    const int rs = check_rows(M, r, row_scale, n_samples, ld_scale);
+    if (rs != LORA_OK) return rs;
+    return linear_geglu_fwd(X, W, bias, Apack, Bpack, Y, Out, T_out, M, K, N, r, scale, row_scale, n_samples, ld_scale, dtype,
+                            stream);
+}
+
+namespace {
+int linear_geglu_fwd(const void* X, const void* W, const void* bias, const void* Apack, const void* Bpack, void* Y, void* Out,
+                     float* T_out, int64_t M, int K, int N, int r, float scale, const float* row_scale, int n_samples,
+                     int ld_scale, int dtype, void* stream) {
     const int st = check_common(M, K, N, r, dtype);
     if (st != LORA_OK) return st;
     if ((N & 1) != 0) return LORA_E_BADARG;
@@ -1610,6 +1780,9 @@ extern "C" int lora_linear_geglu_fwd(const void* X, const void* W, const void* b
     p.Qp = static_cast<const char*>(Bpack) + (size_t)kRP * N * 2;   // B16 [N,16]
     p.C = Y; p.C2 = Out; p.gateF = F; p.P = T_out;
     p.M = M; p.Kc = K; p.Nc = N; p.r = r; p.scale = scale; p.lda = K;
+    if (row_scale != nullptr) {
+        p.row_scale = row_scale; p.rs_rps = M / n_samples; p.rs_ld = ld_scale;
+    }
     const double e = 2.0;
     ProfWork work(e * ((double)M * K + (double)N * K + (Y ? (double)M * N : 0.0) + (double)M * F) + e * r * (K + N) +
                       (bias ? e * N : 0.0),
@@ -1617,6 +1790,7 @@ extern "C" int lora_linear_geglu_fwd(const void* X, const void* W, const void* b
     hipStream_t s = static_cast<hipStream_t>(stream);
     return dtype == LORA_F16 ? launch_gate<half_t>(p, s) : launch_gate<bf16_t>(p, s);
 }
+}  // namespace
 
 extern "C" int geglu_linear_bwd(const void* dZ, const void* W2t, const void* Y, void* dY, const void* zeros, int64_t M,
                                 int Nz, int F, int dtype, void* stream) {

@@ -30,6 +30,43 @@ except ImportError:  # reference: lora.py:12-29
     safetensors_available = False
 
 
+def stack_lora_lists(lists):
+    """K positional `[up0, down0, up1, …]` lists (one per adapter: what a `.pt` file or `parse_safeloras` holds) → one list of
+    the same form whose layer i carries ALL adapters side by side along the rank,
+        up_i = [up_i⁰ | up_i¹ | …]  [N, Σr],      down_i = [down_i⁰; down_i¹; …]  [Σr, K]
+    so that up_i·diag(g)·down_i = Σ_k g_k·up_iᵏ·down_iᵏ for gates g constant on each adapter's slots.  Returns
+    (stacked, slots): slots[k] is the `slice` of rank slots adapter k owns (they partition [0, Σr)).  The adapters may differ in
+    rank, but each has ONE rank for all its layers; all lists have equal length and, per layer, equal feature sizes — anything
+    else is a ValueError naming the layer index.  Pure tensor code (runs on the CPU); the inputs are left alone."""
+    lists = [list(l) for l in lists]
+    if not lists:
+        raise ValueError("stack_lora_lists: no adapters given")
+    n = len(lists[0])
+    for k, l in enumerate(lists):
+        if len(l) != n or n % 2 != 0 or n == 0:
+            raise ValueError(f"stack_lora_lists: adapter {k} has {len(l)} tensors, adapter 0 has {n} "
+                             "(equal, even, non-zero lengths are required: [up0, down0, up1, ...])")
+    ranks = [int(l[1].shape[0]) for l in lists]
+    stacked = []
+    for i in range(n // 2):
+        ups, downs = [l[2 * i] for l in lists], [l[2 * i + 1] for l in lists]
+        for k, (u, d) in enumerate(zip(ups, downs)):
+            if u.dim() != 2 or d.dim() != 2 or u.shape[1] != ranks[k] or d.shape[0] != ranks[k]:
+                raise ValueError(f"stack_lora_lists: layer {i} of adapter {k} has up {tuple(u.shape)} / down {tuple(d.shape)}; "
+                                 f"the adapter's rank is {ranks[k]} (one rank per adapter)")
+            if u.shape[0] != ups[0].shape[0] or d.shape[1] != downs[0].shape[1]:
+                raise ValueError(f"stack_lora_lists: layer {i} of adapter {k} is {d.shape[1]} -> {u.shape[0]} features, "
+                                 f"adapter 0 has {downs[0].shape[1]} -> {ups[0].shape[0]}")
+        like = ups[0]
+        stacked.append(torch.cat([u.detach().to(like.device, like.dtype) for u in ups], dim=1))
+        stacked.append(torch.cat([d.detach().to(like.device, like.dtype) for d in downs], dim=0))
+    slots, at = [], 0
+    for r in ranks:
+        slots.append(slice(at, at + r))
+        at += r
+    return stacked, slots
+
+
 def save_lora_weight(model, path="./lora.pt", target_replace_module=DEFAULT_TARGET_REPLACE):
     """`.pt`: flat python list [up0, down0, up1, ...] of fp16 CPU tensors (lora.py:201-213)."""
     flat = []

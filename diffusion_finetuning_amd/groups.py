@@ -227,6 +227,8 @@ class QKVGroup:
                     (l.linear.bias is None) == (lin.bias is None) and l.lora_down.weight.shape[0] == r for l in layers))
 
     def usable(self, x: torch.Tensor, cdtype: torch.dtype) -> bool:
+        if "_dfa_row_scales" in self.layers[0].__dict__:
+            return False  # per-sample gates (ops.set_lora_row_scales): grouped launches carry none, the members run on their own
         if self.wide and cdtype == torch.float32:
             return False  # the part-wise kernels are 16-bit (fp32 parity runs keep the members on their own)
         if self.sinks is None and not (x.is_cuda and _dropin_ready(self, cdtype)):
@@ -481,6 +483,8 @@ class CtxKVGroup:
         # (per-module path); the reentrant form's no-grad forward and every ordinary pass use the group.
         if _in_backward() or _saved_tensor_hooks_active():
             return False
+        if "_dfa_row_scales" in self.layers[0].__dict__:
+            return False  # per-sample gates (ops.set_lora_row_scales): grouped launches carry none
         # The members (32 layers in an SD UNet) are checked once per pass — by the cross-attention that opens it, whose
         # projection launch serves all of them: packed operands current and gradients deferrable (drop-in mode), one LoRA
         # scale, frozen weights.  The other 15 consumers of the pass only check what is their own.

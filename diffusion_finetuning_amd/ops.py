@@ -642,6 +642,12 @@ def lora_linear(module, x: torch.Tensor, gate=False) -> torch.Tensor:
     global _warned_trainable_base
     w_param, b_param = frozen_linear(module)
     down, up = factor_weights(module)
+    table = module.__dict__.get(ROW_SCALES)
+    if table is not None and torch.is_grad_enabled():
+        raise RuntimeError(
+            "LoraInjectedLinear.forward: per-sample LoRA gates (set_lora_row_scales) are inference-only — the gated forward "
+            "has no backward; run under torch.no_grad() or clear the table with set_lora_row_scales(model, None)."
+        )
     if not x.is_cuda or not w_param.is_cuda:
         raise RuntimeError(
             "LoraInjectedLinear.forward: the fused LoRA path runs only on a HIP device (MI355X); got input on "
@@ -656,6 +662,8 @@ def lora_linear(module, x: torch.Tensor, gate=False) -> torch.Tensor:
             "reference trainers do."
         )
     cdtype = _compute_dtype(w_param)
+    if table is not None:  # (grouped launches carry no gates: the layer runs on its own, whatever group it belongs to)
+        return _lora_linear_rows(module, x, gate, table, cdtype, w_param, b_param, down, up)
     shared = module.__dict__.get("_dfa_shared")  # (group, member): projections of one input called one by one (CLIP q/k/v)
     if shared is not None and not gate and shared[0].usable(x, cdtype) and x.dim() >= 2:
         from .groups import shared_projection
@@ -666,6 +674,95 @@ def lora_linear(module, x: torch.Tensor, gate=False) -> torch.Tensor:
         return (_LoraGegluFn if gate else _LoraLinearFn).apply(x, *operands)
     # `gate` is the frozen nn.Linear that follows the gate (feed_forward_geglu): the whole block as one node
     return _FeedForwardFn.apply(x, *operands, *_frozen_linear(gate, cdtype))
+
+
+ROW_SCALES = "_dfa_row_scales"  # module.__dict__ key of an installed gate table (set_lora_row_scales)
+
+
+def _lora_linear_rows(module, x, gate, table, cdtype, w_param, b_param, down, up):
+    """`lora_linear` while a gate table is installed: the `_rows` entries (csrc/lora_gemm.hip, RS kernels) — sample b of the
+    batch multiplies rank slot j with module.scale · table[b, j].  No autograd node: the caller has checked that grad mode
+    is off."""
+    r = down.shape[0]
+    if table.shape[1] < r:
+        raise ValueError(f"lora_linear: the installed gate table has {table.shape[1]} columns, the layer has rank {r}")
+    if x.dim() >= 2 and x.shape[0] != table.shape[0]:
+        raise ValueError(f"lora_linear: the installed gate table is for {table.shape[0]} samples, the input has "
+                         f"{x.shape[0]} (shape {tuple(x.shape)})")
+    down, up, w, _, bias, scale, _, packed = _layer_operands(module, cdtype, False, w_param, b_param, down, up)
+    K, N = w.shape[1], w.shape[0]
+    x2 = x.reshape(-1, K)
+    if x2.dtype != w.dtype:
+        x2 = x2.to(w.dtype)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    a = _as_f32(down)
+    b = _as_f32(up)
+    packs = packed if packed is not None else nat.lora_pack_factors(a, b, w.dtype)
+    if gate is False:
+        y2, _ = nat.lora_linear_fwd_rows(x2, w, bias, a, b, scale, table, packs)
+        return y2.view(*x.shape[:-1], N)
+    res = nat.lora_linear_geglu_fwd_rows(x2, w, bias, r, scale, table, packs, False)
+    if res is None:  # no fused kernel for this shape / dtype: the two launches it stands for
+        gated = nat.geglu_gate_fwd(nat.lora_linear_fwd_rows(x2, w, bias, a, b, scale, table, packs)[0])
+    else:
+        gated = res[0]
+    gated = gated.view(*x.shape[:-1], N // 2)
+    if gate is True:
+        return gated
+    w2, _, b2 = _frozen_linear(gate, cdtype)  # `gate` is the frozen nn.Linear behind the gate (feed_forward_geglu)
+    return torch.nn.functional.linear(gated, w2, b2)
+
+
+def _gated_layers(model):
+    return [m for m in model.modules() if type(m).__name__ == "LoraInjectedLinear"]
+
+
+def set_lora_row_scales(model, table) -> None:
+    """Installs (or, with None, clears) per-sample gates of the LoRA term on every module of `model` whose class NAME is
+    LoraInjectedLinear (the match of `tune_lora_scale`, lora.py:597-600).  `table`: float32 [n_samples, R]; while it is
+    installed, sample b of a batch — rows [b·M/n_samples, …) of a layer's flattened input — computes
+        y = W x + b + Σ_j (module.scale · table[b, j]) · up[:, j] · down[j, :] x
+    in the same single launch (a layer of rank r reads columns [0, r); R below any layer's rank is a ValueError and
+    nothing is installed).  A [B, 1]-shaped idea — one `tune_lora_scale` value per sample — is a table with the value
+    repeated over the R columns; a table that is one-hot over `stack_lora_lists`' slots picks one stacked adapter per
+    sample.  Inference only (a forward under grad mode raises), inputs must have n_samples as their leading dimension, and
+    the grouped q/k/v and context-K/V launches stand aside (every layer launches on its own) until the table is cleared.
+    The tensor is installed as it is: rewriting it in place changes the gates of the next forward, a recorded one included."""
+    layers = _gated_layers(model)
+    if table is not None:
+        if not torch.is_tensor(table) or table.dtype != torch.float32 or table.dim() != 2 or table.shape[0] < 1:
+            raise ValueError("set_lora_row_scales: the table must be a float32 [n_samples, R] tensor (or None)")
+        if table.stride(1) != 1:
+            raise ValueError("set_lora_row_scales: the table's rows must be dense")
+        for i, m in enumerate(layers):
+            r = factor_weights(m)[0].shape[0]
+            if table.shape[1] < r:
+                raise ValueError(f"set_lora_row_scales: the table has {table.shape[1]} columns, LoRA layer {i} has rank {r}")
+    for m in layers:
+        if table is None:
+            m.__dict__.pop(ROW_SCALES, None)
+        else:
+            m.__dict__[ROW_SCALES] = table
+
+
+class lora_row_scales:
+    """`with lora_row_scales(model, table): …` — set_lora_row_scales for the block; what was installed before comes back."""
+
+    def __init__(self, model, table):
+        self.model, self.table = model, table
+
+    def __enter__(self):
+        self.before = [(m, m.__dict__.get(ROW_SCALES)) for m in _gated_layers(self.model)]
+        set_lora_row_scales(self.model, self.table)
+        return self.table
+
+    def __exit__(self, *exc):
+        set_lora_row_scales(self.model, None)
+        for m, t in self.before:
+            if t is not None:
+                m.__dict__[ROW_SCALES] = t
+        return False
 
 
 def _layer_operands(module, cdtype, need_wt: bool, w_param, b_param, down, up):

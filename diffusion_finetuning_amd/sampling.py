@@ -39,6 +39,16 @@ produced, x' (variance noise included), becomes x = fp32(m·y) + fp32((1−m)·x
 m == 1 the final latents are `init` bit for bit; where m == 0 every iteration's result is the unmasked entry's.  diffusers'
 img2img / inpaint pipelines are not part of the reference tree: restated from their published behaviour, parity UNPINNED beyond
 this repository's own float64 restatement (tests/partial_reference.py).
+Comparing LoRAs in one batch (`visualize_progress`, utils.py:166-214: patch_pipe + tune_lora_scale + torch.manual_seed(seed) + one
+sample per checkpoint; the img2img recipe's 0.0 / 0.7 / 1.0 sweep): `lora_scales` gives every SAMPLE its own factor in front of
+the LoRA term — fp32 [B] (a `tune_lora_scale` value per sample) or [B, R] (a weight per rank slot: one-hot over the slots of
+`monkeypatch_stack_lora` picks one stacked checkpoint per sample) — through the gated forward of csrc/lora_gemm.hip
+(lora_linear_fwd_rows; ops.set_lora_row_scales): the table lives in a static [rows, R] buffer (repeated for the unconditional
+rows), is rewritten in place per run and installed on the LoRA layers only while the run's forward executes, so a recording depends
+on WHETHER there is a table and on R, never on its values — one recording serves every sweep and every mix — and a trainer that
+shares the UNet never sees it.  The grouped q/k/v and context-K/V launches stand aside while it is installed.  `shared_noise=True`
+gives every sample the draws of the B = 1 run of the same seed (x_T, the variance noise, the start noise the keep blend
+regenerates: the `_shared` entries of csrc/ddpm_loss.hip) — "equal seed" in the reference's loops.
 Out of scope: VAE encode / decode, starting from cached moments, 9-channel inpainting UNets, per-row strengths, prompts,
 clip_sample / thresholding, PRK steps, Euler / Heun, the SDE variants, Karras sigmas.
 """
@@ -52,6 +62,7 @@ import torch
 from . import _native as nat
 from . import step as stp
 from .core import LoraInjectedLinear
+from .ops import ROW_SCALES
 
 METHODS = ("ddpm", "ddim")
 MULTISTEP_METHODS = ("plms", "dpmpp_2m")
@@ -265,7 +276,9 @@ class LatentSampler:
     (fp32 [B, 1, h, w] in [0, 1] — the VALUES are not checked: that would synchronise) holds the masked part at the re-noised
     original.  `run_evaluations` / `run_timesteps` describe the run begun; `step()` and the callback count its iterations
     from 0.  A recording depends on WHETHER there is an init and a mask only: strength, seed and the init / mask values replay
-    the same graph (static buffers rewritten in place, the run's first table row in the device cursor)."""
+    the same graph (static buffers rewritten in place, the run's first table row in the device cursor).
+    `lora_scales` (fp32 [B] or [B, R] on the device, or B numbers): per-sample factors of the LoRA term, multiplied with each
+    layer's own `scale`; `shared_noise`: every sample draws what the B = 1 run of the seed draws (module docstring)."""
 
     def __init__(self, unet, num_inference_steps: int = 50, guidance_scale: float = 5.0, method: str = "ddpm", eta: float = 0.0,
                  v_prediction: bool = False, capture_graph: bool = True):
@@ -285,7 +298,8 @@ class LatentSampler:
         self.num_inference_steps = int(num_inference_steps)
         self.capture_graph = bool(capture_graph)
         self._recorder = _IterationRecorder("LatentSampler")
-        self._key = self._fp = self._state = self._cond = None
+        self._key = self._fp = self._state = self._cond = self._table = None
+        self._gated = ()  # the LoRA layers the table is installed on while the forward runs
         self._run_len, self._run_timesteps = self.num_model_evaluations, self.timesteps
         self._done = self._run_len  # nothing begun: step() has nothing to do
         self._inside = False
@@ -391,7 +405,16 @@ class LatentSampler:
     # -- one run ---------------------------------------------------------------------------------------------------------------
     def _iteration(self):
         st = self._state
-        out = self.unet(st.model_in, st.t_model, self._cond).sample
+        if self._table is None:
+            out = self.unet(st.model_in, st.t_model, self._cond).sample
+        else:  # the gates are on the layers only while the forward runs (a recorded forward keeps the buffer's address)
+            for layer in self._gated:
+                layer.__dict__[ROW_SCALES] = self._table
+            try:
+                out = self.unet(st.model_in, st.t_model, self._cond).sample
+            finally:
+                for layer in self._gated:
+                    layer.__dict__.pop(ROW_SCALES, None)
         if out.dtype != st.model_in.dtype:
             out = out.to(st.model_in.dtype)
         keep = st.mask is not None
@@ -423,8 +446,30 @@ class LatentSampler:
                                  f"{tuple(getattr(mask, 'shape', ()))}")
         return start
 
+    def _check_scales(self, B, device, scales):
+        """`lora_scales` as a [B, R'] tensor (R' = 1 for the per-sample form) — checked before anything is written; None
+        without one."""
+        if scales is None:
+            return None
+        if not torch.is_tensor(scales):
+            try:
+                scales = torch.tensor([float(v) for v in scales], dtype=torch.float32)
+            except (TypeError, ValueError):
+                raise ValueError("lora_scales must be a float32 [B] or [B, R] tensor, or B numbers") from None
+            if scales.shape[0] != B:
+                raise ValueError(f"lora_scales must have one entry per sample (B = {B}); got {scales.shape[0]}")
+            return scales.to(device).view(B, 1)
+        if scales.dtype != torch.float32:
+            raise ValueError(f"lora_scales must be float32; got {scales.dtype}")
+        if scales.dim() not in (1, 2) or scales.shape[0] != B or min(scales.shape) < 1:
+            raise ValueError(f"lora_scales must be [B = {B}] or [B = {B}, R]; got {tuple(scales.shape)}")
+        if not scales.is_cuda:
+            raise ValueError(f"lora_scales must live on the HIP device; got a {scales.device} tensor")
+        return scales.view(B, -1)
+
     def begin(self, encoder_hidden_states, negative_encoder_hidden_states=None, *, seed: int, latent_shape=(4, 64, 64),
-              init_latents=None, strength: Optional[float] = None, keep_mask=None):
+              init_latents=None, strength: Optional[float] = None, keep_mask=None, lora_scales=None,
+              shared_noise: bool = False):
         ehs, neg = encoder_hidden_states, negative_encoder_hidden_states
         if ehs.dim() != 3:
             raise ValueError(f"encoder_hidden_states must be [B, L, D]; got {tuple(ehs.shape)}")
@@ -434,6 +479,8 @@ class LatentSampler:
         B = ehs.shape[0]
         dtype = stp.compute_dtype(self.unet)
         partial = self._check_partial(B, dtype, init_latents, strength, keep_mask)
+        scales = self._check_scales(B, ehs.device, lora_scales)
+        shared_noise = bool(shared_noise)
         has_init, has_mask = partial is not None, keep_mask is not None
         latent_shape = tuple(int(n) for n in (init_latents.shape[1:] if has_init else latent_shape))
         if len(latent_shape) != 3 or min(latent_shape) < 1:
@@ -444,8 +491,16 @@ class LatentSampler:
         cfg = neg is not None and self.guidance_scale > 1.0
         with self._mode():
             layers = [m for m in self.unet.modules() if isinstance(m, LoraInjectedLinear)]
+            R = 0
+            if scales is not None:
+                gated = [m for m in self.unet.modules() if type(m).__name__ == "LoraInjectedLinear"]  # (set_lora_row_scales' match)
+                rank = max([m.lora_down.weight.shape[0] for m in gated], default=1)
+                per_slot = lora_scales is not None and torch.is_tensor(lora_scales) and lora_scales.dim() == 2
+                if per_slot and scales.shape[1] < rank:
+                    raise ValueError(f"lora_scales has {scales.shape[1]} rank slots, a LoRA layer of the model has rank {rank}")
+                R = scales.shape[1] if per_slot else rank
             self._refresh_packed(layers, dtype)
-            key = (B, latent_shape, tuple(ehs.shape[1:]), cfg, dtype, ehs.device, has_init, has_mask)
+            key = (B, latent_shape, tuple(ehs.shape[1:]), cfg, dtype, ehs.device, has_init, has_mask, R, shared_noise)
             fp = self._fingerprint(layers)
             if self._state is None or key != self._key or fp != self._fp:
                 self._recorder.drop()  # before the buffers it reads are replaced
@@ -457,12 +512,19 @@ class LatentSampler:
                 else:
                     self._state = nat.SampleState.alloc((B, *latent_shape), dtype, cfg, self.timesteps, self.coef, ehs.device,
                                                         with_init=has_init, with_mask=has_mask)
+                self._state.shared_noise = shared_noise
                 self._cond = torch.empty(((2 if cfg else 1) * B, *ehs.shape[1:]), dtype=dtype, device=ehs.device)
+                self._table = torch.empty(((2 if cfg else 1) * B, R), dtype=torch.float32, device=ehs.device) if R else None
+                self._gated = tuple(gated) if R else ()
             if cfg:
                 self._cond[:B].copy_(neg)  # unconditional rows first, as the pipeline concatenates them
                 self._cond[B:].copy_(ehs)
             else:
                 self._cond.copy_(ehs)
+            if R:  # rewritten in place: a recording reads the table through its address (unconditional rows: the same gates)
+                self._table[-B:].copy_(scales.expand(B, R))
+                if cfg:
+                    self._table[:B].copy_(scales.expand(B, R))
             st = self._state
             if has_init:
                 # static buffers rewritten in place: a recording reads them through their addresses
@@ -527,12 +589,14 @@ class LatentSampler:
         return self._recorder.graph is not None
 
     def sample(self, encoder_hidden_states, negative_encoder_hidden_states=None, *, seed: int, latent_shape=(4, 64, 64),
-               callback=None, init_latents=None, strength: Optional[float] = None, keep_mask=None) -> torch.Tensor:
+               callback=None, init_latents=None, strength: Optional[float] = None, keep_mask=None, lora_scales=None,
+               shared_noise: bool = False) -> torch.Tensor:
         """All iterations of the run; `callback(i, timestep, latents)` after iteration i, if given (reading the latents
         synchronises).  Returns a copy of the final state."""
         with self._mode():
             self.begin(encoder_hidden_states, negative_encoder_hidden_states, seed=seed, latent_shape=latent_shape,
-                       init_latents=init_latents, strength=strength, keep_mask=keep_mask)
+                       init_latents=init_latents, strength=strength, keep_mask=keep_mask, lora_scales=lora_scales,
+                       shared_noise=shared_noise)
             for i in range(self._run_len):
                 self.step()
                 if callback is not None:

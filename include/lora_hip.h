@@ -108,6 +108,33 @@ int lora_linear_geglu_fwd(const void* X, const void* W, const void* bias /* null
                           int r, float scale, int dtype, void* stream);
 
 /*
+ * The two forwards above with a PER-SAMPLE, PER-RANK-SLOT factor in front of the rank-r term (inference only: there is no
+ * backward form):
+ *     Y[m,:] = X[m,:]·Wᵀ + b + Σ_j (s · G[m / rps, j]) · T[m,j] · B[:,j] ,   T = X·Aᵀ ,   rps = M / n_samples
+ * row_scale = G: fp32 [n_samples, ld_scale] in device memory, columns [0, r) are read; a sample is rps consecutive rows of
+ * X.  The factor is formed in fp32 as (s·G) first and then multiplied into T wherever a kernel builds s·T per row (every MFMA
+ * form); the shape-agnostic kernels, whose ungated form scales the sum, compute the same arithmetic at slot 0's factor plus the
+ * other slots' deviations from it — so on EVERY path a table filled with g at scale 1, or a table of ones at scale g, gives bit
+ * for bit what lora_linear_fwd_ws gives at scale g, and a row of zeros what it gives at scale 0.  T_out receives T un-gated and unscaled, as above.  One launch then serves what the reference
+ * does one sample at a time:
+ *   - G[b, :] = s_b: `tune_lora_scale(unet, s_b)` (lora.py:597-600 setting `scale` of lora.py:49-50) per sample of a batch —
+ *     the 0.0 / 0.7 / 1.0 sweeps at equal seed;
+ *   - K checkpoints of rank r_k stacked along the rank (A = [A_0; A_1; …], B = [B_0 | B_1 | …], Σ r_k slots) with G[b, :]
+ *     open on the slots of checkpoint k_b only: `visualize_progress` (utils.py:191-211: patch_pipe, tune_lora_scale, one
+ *     sample per checkpoint) as one batch.  Σ r_k <= 16 rides on the same single extra MFMA K-step as one checkpoint.
+ * LORA_E_BADARG for n_samples < 1, M % n_samples != 0, ld_scale < r or a null table (nothing is launched or written);
+ * everything else as the entry it mirrors, lora_linear_geglu_fwd_rows including the LORA_E_UNSUPPORTED envelope.
+ */
+int lora_linear_fwd_rows(const void* X, const void* W, const void* bias /* nullable */, const float* A, const float* B,
+                         const void* Apack, const void* Bpack, void* Y, float* T_out, int64_t M, int K, int N, int r,
+                         float scale, const float* row_scale, int n_samples, int ld_scale, int dtype,
+                         void* workspace /* nullable */, int64_t ws_bytes, void* stream);
+int lora_linear_geglu_fwd_rows(const void* X, const void* W, const void* bias /* nullable */, const void* Apack,
+                               const void* Bpack, void* Y /* nullable */, void* Out, float* T_out, int64_t M, int K, int N,
+                               int r, float scale, const float* row_scale, int n_samples, int ld_scale, int dtype,
+                               void* stream);
+
+/*
  * Backward of the same gate, in the epilogue of the GEMM that produces its incoming gradient.  In a transformer block the
  * gated activation feeds a frozen linear layer (diffusers FeedForward: net = [GEGLU, Dropout, Linear]); autograd of
  *     z = (hidden * gelu(gate)) @ W2ᵀ + b2 ,   [hidden | gate] = Y = proj(x)      (proj: the LoraInjectedLinear above)
@@ -494,6 +521,36 @@ int ddpm_sample_multistep_keep(float* x, float* xs, float* hist, const void* mod
                                const int* cursor, const int64_t* timesteps, const float* coef, const int* plan,
                                const float* mask, const float* init, const float* keep_coef, int B, int64_t per_row, int64_t hw,
                                int I, int cfg, float guidance_scale, int dtype, void* stream);
+
+/*
+ * Shared noise ("equal seed"): the five entries above that draw — x_T, the start noise ε (drawn, and regenerated by the keep
+ * blend) and the variance noise z — with the Philox counter taken from the element's index INSIDE ITS SAMPLE instead of inside
+ * the batch: element j of every sample takes lane j mod 4 of counter (j div 4, (j div 4) >> 32, stream, 0) under the same key,
+ * which is what the B = 1 run of the same seed gives its element j.  Every sample of the batch therefore starts from, and is
+ * perturbed by, the same noise — the reference's comparison loops call torch.manual_seed(seed) before every member
+ * (utils.py:191-211: one sample per checkpoint; README.md:287-289: one per tune_lora_scale value).  per_row % 4 != 0 is
+ * allowed: a group of four consecutive state elements then straddles counters (and samples) and is assembled element by
+ * element; the result is the same B = 1 draw.  A run uses either the plain or the `_shared` entries throughout (the keep blend
+ * regenerates the start draw of ddpm_sample_init_from*).  Arguments, statuses and everything else as the entry without the
+ * suffix, whose own draws are unchanged.  ddpm_sample_multistep draws nothing and has no such form.
+ */
+int ddpm_sample_init_shared(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps, int B,
+                            int64_t per_row, int S, int cfg, uint64_t seed, int dtype, void* stream);
+int ddpm_sample_step_shared(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+                            const int64_t* timesteps, const float* coef, float* z_out /* nullable */, int B, int64_t per_row,
+                            int S, int cfg, float guidance_scale, int dtype, void* stream);
+int ddpm_sample_init_from_shared(float* x, void* model_in, int64_t* t_model, int* cursor, const int64_t* timesteps,
+                                 const float* init, float* eps_out /* nullable */, int B, int64_t per_row, int S, int start,
+                                 float k, float n, int cfg, uint64_t seed, int dtype, void* stream);
+int ddpm_sample_step_keep_shared(float* x, const void* model_out, void* model_in, int64_t* t_model, const int* cursor,
+                                 const int64_t* timesteps, const float* coef, float* z_out /* nullable */, const float* mask,
+                                 const float* init, const float* keep_coef, int B, int64_t per_row, int64_t hw, int S, int cfg,
+                                 float guidance_scale, int dtype, void* stream);
+int ddpm_sample_multistep_keep_shared(float* x, float* xs, float* hist, const void* model_out, void* model_in,
+                                      int64_t* t_model, const int* cursor, const int64_t* timesteps, const float* coef,
+                                      const int* plan, const float* mask, const float* init, const float* keep_coef, int B,
+                                      int64_t per_row, int64_t hw, int I, int cfg, float guidance_scale, int dtype,
+                                      void* stream);
 
 /*
  * The two ops sandwiched by the hot path inside a transformer block, as streaming kernels.

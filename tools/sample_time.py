@@ -22,7 +22,18 @@ image at that strength, min(int(steps·S), steps) grid steps — and --keep-mask
 8×8 blocks (ddpm_sample_*_keep).  They alternate with the full run's routes in the same process; every route is reported per
 iteration of ITS run (a partial run has fewer), with the spread (min – max) of its repetitions.
 
+--sweep K compares the two ways to sample K members of a `tune_lora_scale` sweep (scales 0 … 1, equal seed, one prompt) — the
+reference's `visualize_progress` / img2img comparison loops:
+  sequential       one member after the other on ONE LatentSampler: `tune_lora_scale(unet, s_k)`, then a B = 1 sample (2 UNet
+                   rows).  The change of scale drops the recording, so every member pays its warm-up passes and a capture again
+  sequential host  the same with capture_graph=False: no recording to lose, every launch issued from the host
+  batched          ONE sample of K rows per pass (2K with guidance) with `lora_scales=` (the per-row gates of the fused forward)
+                   and `shared_noise=True`, replayed — the recording survives every change of the table
+in one process, alternating, medians and spreads over --reps; the first (untimed) round also prints how far member k of the
+batch is from member k sampled alone.  --batch is not read in this mode.
+
     python tools/sample_time.py [--reps 5] [--steps 50] [--batch 4]
+    python tools/sample_time.py --sweep 4 --method ddpm plms --steps 50 50
     python tools/sample_time.py --batch 1 --method ddpm plms dpmpp_2m --steps 50 50 20
     python tools/sample_time.py --batch 1 --method plms --steps 50 --strength 0.75 --keep-mask
 """
@@ -146,6 +157,68 @@ def routes_for(unet, method, steps, guidance, cond, neg, shape, gen, strength=No
     return replayed, routes, iterations
 
 
+def sweep(a):
+    """--sweep K: K members one after another against one batched run (module docstring)."""
+    K = a.sweep
+    unet, ctx_dim = build_unet()
+    shape, guidance = (4, 64, 64), 5.0
+    g = torch.Generator().manual_seed(2)
+    cond1, neg1 = torch.randn(1, 77, ctx_dim, generator=g).to("cuda"), torch.randn(1, 77, ctx_dim, generator=g).to("cuda")
+    cond, neg = cond1.repeat(K, 1, 1), neg1.repeat(K, 1, 1)
+    scales = [k / max(K - 1, 1) for k in range(K)]
+    table = torch.tensor(scales, device="cuda")
+
+    def members(sampler):
+        out = []
+        for s_k in scales:
+            dfa.tune_lora_scale(unet, s_k)
+            out.append(sampler.sample(cond1, neg1, seed=7, latent_shape=shape))
+        dfa.tune_lora_scale(unet, 1.0)
+        return torch.cat(out)
+
+    configs = {}
+    for method, steps in zip(a.method, a.steps):
+        seq = dfa.LatentSampler(unet, steps, guidance, method=method)
+        seq_host = dfa.LatentSampler(unet, steps, guidance, method=method, capture_graph=False)
+        batched = dfa.LatentSampler(unet, steps, guidance, method=method)
+        routes = {
+            "sequential": lambda seq=seq: members(seq),
+            "sequential host": lambda seq_host=seq_host: members(seq_host),
+            "batched": lambda batched=batched: batched.sample(cond, neg, seed=7, latent_shape=shape, lora_scales=table,
+                                                              shared_noise=True),
+        }
+        configs[f"{method} {steps}"] = (method, steps, batched, routes)
+    first = {}
+    for label, (_, _, batched, routes) in configs.items():  # untimed round: recording, solver searches, allocator
+        first[label] = {name: timed(fn) for name, fn in routes.items()}
+        assert batched.replaying, "the recording failed: the batched route would measure host launches"
+        graph = batched._recorder.graph
+        alone, both = first[label]["sequential host"][1].double(), first[label]["batched"][1].double()
+        rel = [float((both[k] - alone[k]).norm() / alone[k].norm()) for k in range(K)]
+        print(f"[sweep {K}, {label}] first (untimed) round, ms: " + ", ".join(f"{k} {v[0]:.1f}" for k, v in first[label].items()) +
+              "; member k of the batch vs member k alone, rel L2: " + ", ".join(f"{r:.2e}" for r in rel), flush=True)
+        configs[label] = configs[label] + (graph,)
+    times = {label: {name: [] for name in cfg[3]} for label, cfg in configs.items()}
+    for rep in range(a.reps):
+        for label, (_, _, _, routes, _) in configs.items():
+            for name, fn in routes.items():
+                times[label][name].append(timed(fn)[0])
+            print(f"[sweep {K}, {label}] rep {rep}: " + ", ".join(f"{k} {times[label][k][-1]:.1f} ms" for k in routes), flush=True)
+    for label, (method, steps, batched, _, graph) in configs.items():
+        assert batched._recorder.graph is graph, "the batched route recorded again"
+        med = {k: statistics.median(v) for k, v in times[label].items()}
+        print(f"[sweep {K}, {label}] medians: " + ", ".join(f"{k} {v:.1f} ms (spread {min(times[label][k]):.1f} – "
+                                                           f"{max(times[label][k]):.1f})" for k, v in med.items()) +
+              f"; sequential / batched = {med['sequential'] / med['batched']:.2f}, sequential host / batched = "
+              f"{med['sequential host'] / med['batched']:.2f}", flush=True)
+        print(json.dumps({"gpu": torch.cuda.get_device_name(0), "unet": "sd15", "sweep": K, "scales": scales, "method": method,
+                          "steps": steps, "iterations": batched.num_model_evaluations, "dtype": "f16", "guidance": guidance,
+                          "rows_sequential": 2, "rows_batched": 2 * K, "reps": a.reps, "median_ms": med, "all_ms": times[label],
+                          "first_round_ms": {k: v[0] for k, v in first[label].items()},
+                          "sequential_over_batched": med["sequential"] / med["batched"],
+                          "sequential_host_over_batched": med["sequential host"] / med["batched"]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -154,6 +227,8 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--strength", type=float, default=None, help="add a replayed image-to-image route at this strength")
     ap.add_argument("--keep-mask", action="store_true", help="with --strength: add the route with a keep mask too")
+    ap.add_argument("--sweep", type=int, default=None, metavar="K",
+                    help="K members of a tune_lora_scale sweep one after another against one batched run (lora_scales=)")
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps must be at least 5")
@@ -163,6 +238,10 @@ def main():
         ap.error("--steps takes one value, or one per --method")
     if a.keep_mask and a.strength is None:
         ap.error("--keep-mask needs --strength")
+    if a.sweep is not None:
+        if a.sweep < 2 or a.strength is not None:
+            ap.error("--sweep takes K >= 2 and no --strength")
+        return sweep(a)
     unet, ctx_dim = build_unet()
     shape = (4, 64, 64)
     g = torch.Generator().manual_seed(2)
