@@ -13,4 +13,4 @@ from .lora import (  # noqa: F401  (underscore names the reference's callers imp
 )
 from .ops import ddpm_mse_loss, invalidate_weight_cache, lora_linear  # noqa: F401
 from .distill import distill_lora, extract_linear_weights, svd_distill  # noqa: F401  (lora_distill, cli_svd.py)
-from .sampling import LatentSampler, keep_schedule, multistep_schedule, partial_start, sampler_schedule  # noqa: F401  (evaluate_pipe / class images: utils.py:112-163)
+from .sampling import LatentSampler, keep_schedule, multistep_schedule, partial_start, sampler_schedule, sigma_schedule  # noqa: F401  (evaluate_pipe / class images: utils.py:112-163)

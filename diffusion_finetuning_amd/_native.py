@@ -103,6 +103,8 @@ SIGNATURES = {
                                             ctypes.c_uint64, _i32, _vp]),
     "ddpm_sample_step_keep_shared": (_i32, [_vp] * 11 + [_i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp]),
     "ddpm_sample_multistep_keep_shared": (_i32, [_vp] * 13 + [_i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp]),
+    "ddpm_sample_sigma_init": (_i32, [_vp] * 7 + [_i32, _i64, _i32, _i32, _f32, _f32, _f32, _i32, _i32, ctypes.c_uint64, _i32, _vp]),
+    "ddpm_sample_sigma": (_i32, [_vp] * 14 + [_i32, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
     "embed_rows_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "embed_rows_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp]),
     "lora_adamw_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
@@ -944,6 +946,88 @@ def ddpm_sample_multistep_keep(st: MultistepState, model_out, guidance_scale: fl
                                             st.hw, st.S, int(st.cfg), float(guidance_scale), dtype_code(model_out.dtype),
                                             _stream(st.x)),
            "ddpm_sample_multistep_keep")
+
+
+class SigmaState(SampleState):
+    """SampleState for the sigma-space methods (include/lora_hip.h: ddpm_sample_sigma): the saved state `xs` and the ONE history
+    slot `hist` (fp32, like x), `t_model` [rows] and `timesteps` [I] in FP32 — the grid is fractional — `coef` fp32 [I, 8] = (p, q,
+    a, c0, c1, s, n, σ_eval) and `plan` int32 [I, 5] of sampling.sigma_schedule.  `S` is I, the number of model evaluations, so
+    ddpm_sample_advance serves it as it is.  `xs` and `hist` need no clearing."""
+
+    def __init__(self, x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan, cfg: bool, init=None, mask=None,
+                 keep_coef=None):
+        B, rows = x.shape[0], model_in.shape[0]
+        if (rows != (2 * B if cfg else B) or model_in.shape[1:] != x.shape[1:] or t_model.shape != (rows,) or
+                xs.shape != x.shape or hist.shape != x.shape):
+            raise ValueError(f"sampler buffers disagree: state {tuple(x.shape)}, saved state {tuple(xs.shape)}, history "
+                             f"{tuple(hist.shape)}, model input {tuple(model_in.shape)}, timesteps {tuple(t_model.shape)}, "
+                             f"guidance {cfg}")
+        n = timesteps.shape[0]
+        if (x.dtype != torch.float32 or xs.dtype != torch.float32 or hist.dtype != torch.float32 or
+                t_model.dtype != torch.float32 or cursor.dtype != torch.int32 or cursor.numel() != 2 or
+                timesteps.dtype != torch.float32 or timesteps.dim() != 1 or coef.dtype != torch.float32 or
+                tuple(coef.shape) != (n, 8) or plan.dtype != torch.int32 or tuple(plan.shape) != (n, 5) or n < 1):
+            raise ValueError("sampler buffers: x / xs / hist fp32, t_model / timesteps fp32, cursor int32 [2], coef fp32 "
+                             "[I, 8], plan int32 [I, 5]")
+        for t in (x, xs, hist, model_in, t_model, timesteps, coef, plan):
+            if not t.is_contiguous():
+                raise ValueError("sampler buffers must be contiguous")
+        self._set_keep(x, n, init, mask, keep_coef)
+        _require_device(x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan)
+        self.x, self.model_in, self.t_model, self.cursor, self.timesteps, self.coef = x, model_in, t_model, cursor, timesteps, coef
+        self.xs, self.hist, self.plan = xs, hist, plan
+        self.cfg, self.B, self.per_row, self.S = bool(cfg), B, x[0].numel(), n
+
+    @classmethod
+    def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, plan, device, with_init: bool = False,
+              with_mask: bool = False):
+        """`shape`: of the state, [B, C, h, w]; `timesteps` / `coef` / `plan`: host or device tensors of sigma_schedule (the
+        float64 timesteps are rounded to fp32 here)."""
+        rows = (2 if cfg else 1) * shape[0]
+        return cls(torch.empty(shape, dtype=torch.float32, device=device), torch.empty(shape, dtype=torch.float32, device=device),
+                   torch.empty(shape, dtype=torch.float32, device=device),
+                   torch.empty((rows, *shape[1:]), dtype=dtype, device=device),
+                   torch.empty(rows, dtype=torch.float32, device=device), torch.zeros(2, dtype=torch.int32, device=device),
+                   timesteps.to(device=device, dtype=torch.float32).contiguous(), coef.to(device).contiguous(),
+                   plan.to(device).contiguous(), cfg, *cls._alloc_keep(shape, timesteps.shape[0], device, with_init, with_mask))
+
+
+def ddpm_sample_sigma_init(st: SigmaState, seed: int, start: int, k: float, nn: float, c_in: float, from_init: bool = False,
+                           eps_out=None) -> None:
+    """The start of a sigma-space run at table row `start`: x = fp32(nn·ε), or fp32(k·init) + fp32(nn·ε) from `st.init` with
+    `from_init`; ε the x_T draw of `ddpm_sample_init` at equal seed; model input cast(fp32(c_in·x)), t_model = timesteps[start],
+    cursor = {start, seed}.  `eps_out` (fp32 like x) gets ε."""
+    if from_init and st.init is None:
+        raise ValueError("ddpm_sample_sigma_init: the state has no init buffer")
+    _require_device(eps_out)
+    if eps_out is not None and (eps_out.dtype != torch.float32 or eps_out.shape != st.x.shape or not eps_out.is_contiguous()):
+        raise ValueError(f"eps_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
+    _check(lib().ddpm_sample_sigma_init(_ptr(st.x), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps),
+                                        _ptr(st.init) if from_init else 0, _ptr(eps_out), st.B, st.per_row, st.S, int(start),
+                                        float(k), float(nn), float(c_in), int(st.cfg), int(st.shared_noise),
+                                        int(seed) & (2**64 - 1), dtype_code(st.model_in.dtype), _stream(st.x)),
+           "ddpm_sample_sigma_init")
+
+
+def ddpm_sample_sigma(st: SigmaState, model_out, guidance_scale: float, z_out=None, keep: bool = False) -> None:
+    """One sigma-space iteration at the device-resident cursor (and seed): guidance, h = p·x + q·o, x ← a·base + c0·h + c1·H +
+    s·z in place, the saved state and the history slot as plan[i] says, with `keep` the blend of `ddpm_sample_step_keep` on the
+    state produced, then the next model input cast(fp32(n·x)) and the fp32 timestep tensor.  `model_out` [rows, ...] in the
+    model input's dtype.  Does not move the cursor: ddpm_sample_advance."""
+    if keep:
+        _require_mask(st, "ddpm_sample_sigma")
+    _require_device(model_out, z_out)
+    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
+        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
+                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
+    if z_out is not None and (z_out.dtype != torch.float32 or z_out.shape != st.x.shape or not z_out.is_contiguous()):
+        raise ValueError(f"z_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
+    _check(lib().ddpm_sample_sigma(_ptr(st.x), _ptr(st.xs), _ptr(st.hist), _ptr(model_out), _ptr(st.model_in), _ptr(st.t_model),
+                                   _ptr(st.cursor), _ptr(st.timesteps), _ptr(st.coef), _ptr(st.plan), _ptr(z_out),
+                                   _ptr(st.mask) if keep else 0, _ptr(st.init) if keep else 0,
+                                   _ptr(st.keep_coef) if keep else 0, st.B, st.per_row, st.hw if keep else 1, st.S, int(st.cfg),
+                                   int(st.shared_noise), float(guidance_scale), dtype_code(model_out.dtype), _stream(st.x)),
+           "ddpm_sample_sigma")
 
 
 def embed_rows_fwd(table, ids, out_dtype: torch.dtype):

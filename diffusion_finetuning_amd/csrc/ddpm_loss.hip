@@ -1290,3 +1290,268 @@ extern "C" int ddpm_sample_multistep_keep_shared(float* x, float* xs, float* his
     return ddpm_sample_multistep_keep_impl(x, xs, hist, model_out, model_in, t_model, cursor, timesteps, coef, plan, mask,
                                            init, keep_coef, B, per_row, hw, I, cfg, guidance_scale, dtype, stream, true);
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Sigma-space step (k-diffusion's Euler, Euler-ancestral and Heun: the `EulerAncestralDiscreteScheduler` cells of
+// scripts/lora_training_process_visualized.ipynb:57 and scripts/merge_lora_with_lora.ipynb:74 of the reference, and the
+// equal-seed comparison loop of utils.py:191-211 run under them).  The state lives in sigma space — x_T = σ₀·z — the model is
+// fed c_in(σ)·x with the σ of the NEXT evaluation, and the timestep grid is fractional: `timesteps` and `t_model` are fp32.
+// Per iteration i = cursor[0], (p, q, a, c0, c1, s, n, σ_eval) = coef[i] and flags = plan[i][4] (sampling.sigma_schedule):
+//     h    = p·x + q·o                          d = (x − denoised)/σ of the method (o guided as above)
+//     base = USE_SAVED ? xs : x
+//     x'   = a·base + c0·h + c1·H + s·z         left to right, every product rounded on its own; z only where s ≠ 0
+//     SAVE: xs ← x;   PUSH: H ← h               (one history slot: Heun's d₁)
+//     x ← x' (after the keep blend, where compiled in);   model_in ← cast(fp32(n·x));   t_model ← timesteps[min(i+1, I−1)]
+// It needs what neither kernel above has alone: the variance noise of sample_step_kernel (euler_a) and the saved state and
+// history of sample_multistep_kernel (heun).  A term whose coefficient is exactly 0 is neither loaded nor added, so xs and H
+// stay unread until a Heun stage B — they are uninitialised memory before.
+namespace {
+
+struct SigmaParams {
+    SampleParams s;   // x, out, in, cursor, coef = [I, 8], z_out, n_total, rows, S = I, cfg, guidance, shared_row; t_model and
+                      // timesteps unused (fp32 here: below)
+    float* xs;        // [B, per_row] fp32: the saved state
+    float* hist;      // [B, per_row] fp32: the one history slot
+    const int* plan;  // [I, 5]
+    float* t_model;           // [rows] fp32
+    const float* timesteps;   // [I] fp32
+};
+struct KeepSigmaParams : SigmaParams {
+    KeepParams k;
+};
+template <> constexpr bool kHasKeep<KeepSigmaParams> = true;
+
+__device__ __forceinline__ float sigma_history(float p, float q, float x, float o) {
+#pragma clang fp contract(off)
+    const float qo = q * o;
+    if (p == 0.f) return qo;
+    const float px = p * x;
+    return px + qo;
+}
+__device__ __forceinline__ float sigma_update(float a, float c0, float c1, float s, float base, float h, float h1, float z) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+    if (a != 0.f) acc = a * base;
+    if (c0 != 0.f) { const float t = c0 * h; acc = acc + t; }
+    if (c1 != 0.f) { const float t = c1 * h1; acc = acc + t; }
+    if (s != 0.f) { const float t = s * z; acc = acc + t; }
+    return acc;
+}
+// fp32(n·x), an operation of its own: without `exceptions(strict)` hipcc folds the product into the f16 conversion that follows
+// (v_fma_mixlo_f16 — ONE rounding, to f16), and the model input is then not the cast of the fp32 product: 1 f16 ulp off in about
+// one element in a thousand, and differently on the 4-element path, which converts in pairs.
+__device__ __forceinline__ float sigma_scaled(float n, float x) {
+#pragma clang fp contract(off)
+#pragma clang fp exceptions(strict)
+    return n * x;
+}
+
+template <typename T, bool QUAD, typename P>
+__global__ __launch_bounds__(256) void sample_sigma_kernel(P m) {
+    constexpr bool KEEP = kHasKeep<P>;
+    const SampleParams& p = m.s;
+    const int it = p.cursor[0];
+    const uint32_t seed = (uint32_t)p.cursor[1];
+    if (it < 0 || it >= p.S) return;  // (uniform over the whole launch: one replay too many touches nothing)
+    const float* cf = p.coef + 8 * it;
+    const float kp = cf[0], kq = cf[1], a = cf[2], c0 = cf[3], c1 = cf[4], sn = cf[5], n_in = cf[6];
+    const int flags = m.plan[5 * it + 4];
+    const bool push = (flags & kMultistepPush) != 0, save = (flags & kMultistepSave) != 0;
+    const bool saved_base = (flags & kMultistepUseSaved) != 0 && a != 0.f;
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthreads = (int64_t)gridDim.x * 256;
+    const float t_next = m.timesteps[it + 1 < p.S ? it + 1 : it];
+    for (int64_t r = tid; r < p.rows; r += nthreads) m.t_model[r] = t_next;
+    const T* out = static_cast<const T*>(p.out);
+    const int64_t groups = (p.n_total + 3) >> 2;
+    for (int64_t g = tid; g < groups; g += nthreads) {
+        Quad<float> z;
+        if (sn != 0.f) {
+            sample_normals4(g, p.shared_row, kStreamStepNoise, seed, (uint32_t)it, z.v);
+        } else {
+            z.v[0] = z.v[1] = z.v[2] = z.v[3] = 0.f;
+        }
+        const int64_t i0 = g * 4;
+        Quad<float> xn = {}, scaled;
+        if constexpr (QUAD) {
+            const Quad<float> x = *reinterpret_cast<const Quad<float>*>(p.x + i0);
+            const Quad<T> u = *reinterpret_cast<const Quad<T>*>(out + i0);
+            Quad<T> c = u;
+            if (p.cfg) c = *reinterpret_cast<const Quad<T>*>(out + p.n_total + i0);
+            Quad<float> base = x, h1 = {}, h;
+            if (saved_base) base = *reinterpret_cast<const Quad<float>*>(m.xs + i0);
+            if (c1 != 0.f) h1 = *reinterpret_cast<const Quad<float>*>(m.hist + i0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float uf = to_f32<T>(u.v[e]);
+                const float o = p.cfg ? guided(uf, to_f32<T>(c.v[e]), p.guidance) : uf;
+                h.v[e] = sigma_history(kp, kq, x.v[e], o);
+                xn.v[e] = sigma_update(a, c0, c1, sn, base.v[e], h.v[e], h1.v[e], z.v[e]);
+            }
+            if constexpr (KEEP) keep_apply<true>(m.k, p.n_total, p.shared_row, seed, it, g, xn.v);
+            if (save) *reinterpret_cast<Quad<float>*>(m.xs + i0) = x;
+            if (push) *reinterpret_cast<Quad<float>*>(m.hist + i0) = h;
+            *reinterpret_cast<Quad<float>*>(p.x + i0) = xn;
+            if (p.z_out) *reinterpret_cast<Quad<float>*>(p.z_out + i0) = z;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = i0 + e;
+                if (i >= p.n_total) break;
+                const float x = p.x[i];
+                const float uf = to_f32<T>(out[i]);
+                const float o = p.cfg ? guided(uf, to_f32<T>(out[p.n_total + i]), p.guidance) : uf;
+                const float base = saved_base ? m.xs[i] : x;
+                const float h1 = c1 != 0.f ? m.hist[i] : 0.f;
+                const float h = sigma_history(kp, kq, x, o);
+                xn.v[e] = sigma_update(a, c0, c1, sn, base, h, h1, z.v[e]);
+                if (save) m.xs[i] = x;
+                if (push) m.hist[i] = h;
+                if constexpr (!KEEP) p.x[i] = xn.v[e];
+                if (p.z_out) p.z_out[i] = z.v[e];
+            }
+            if constexpr (KEEP) {
+                keep_apply<false>(m.k, p.n_total, p.shared_row, seed, it, g, xn.v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (i0 + e < p.n_total) p.x[i0 + e] = xn.v[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) scaled.v[e] = sigma_scaled(n_in, xn.v[e]);
+        store_model_input<T, QUAD>(p, i0, scaled.v);
+    }
+}
+
+struct SigmaInitParams {
+    const float* init;  // nullable: text-to-image, x = nn·ε
+    float* eps_out;     // nullable
+    float* t_model;           // [rows] fp32
+    const float* timesteps;   // [I] fp32
+    int start;
+    float k, nn, c_in;
+};
+
+template <typename T, bool QUAD>
+__global__ __launch_bounds__(256) void sample_sigma_init_kernel(SampleParams p, SigmaInitParams f) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthreads = (int64_t)gridDim.x * 256;
+    const float t0 = f.timesteps[f.start];
+    for (int64_t r = tid; r < p.rows; r += nthreads) f.t_model[r] = t0;
+    if (tid == 0) {
+        p.cursor[0] = f.start;
+        p.cursor[1] = (int)p.seed;
+    }
+    const int64_t groups = (p.n_total + 3) >> 2;
+    for (int64_t g = tid; g < groups; g += nthreads) {
+        Quad<float> z, x = {}, scaled;
+        sample_normals4(g, p.shared_row, kStreamInit, p.seed, 0u, z.v);
+        const int64_t i0 = g * 4;
+        if constexpr (QUAD) {
+            if (f.init) {
+                const Quad<float> init = *reinterpret_cast<const Quad<float>*>(f.init + i0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x.v[e] = ddpm_noisy(f.k, f.nn, init.v[e], z.v[e]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x.v[e] = sigma_scaled(f.nn, z.v[e]);
+            }
+            *reinterpret_cast<Quad<float>*>(p.x + i0) = x;
+            if (f.eps_out) *reinterpret_cast<Quad<float>*>(f.eps_out + i0) = z;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = i0 + e;
+                if (i >= p.n_total) break;
+                x.v[e] = f.init ? ddpm_noisy(f.k, f.nn, f.init[i], z.v[e]) : sigma_scaled(f.nn, z.v[e]);
+                p.x[i] = x.v[e];
+                if (f.eps_out) f.eps_out[i] = z.v[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) scaled.v[e] = sigma_scaled(f.c_in, x.v[e]);
+        store_model_input<T, QUAD>(p, i0, scaled.v);
+    }
+}
+
+template <typename T>
+void launch_sigma(const KeepSigmaParams& m, int64_t per_row, bool keep, hipStream_t s) {
+    const SampleParams& p = m.s;
+    const dim3 grid(posterior_blocks(p.n_total));
+    const bool own = quad_aligned<float>(m.xs) && quad_aligned<float>(m.hist);
+    if (keep) {
+        if (keep_quad<T>(p, m.k) && own)
+            hipLaunchKernelGGL((sample_sigma_kernel<T, true, KeepSigmaParams>), grid, dim3(256), 0, s, m);
+        else
+            hipLaunchKernelGGL((sample_sigma_kernel<T, false, KeepSigmaParams>), grid, dim3(256), 0, s, m);
+    } else {
+        const SigmaParams& plain = m;  // (the instantiation without the blend: the keep block is sliced off)
+        const bool quad = (per_row % 4) == 0 && quad_aligned<float>(p.x) && quad_aligned<T>(p.out) && quad_aligned<T>(p.in) &&
+                          quad_aligned<float>(p.z_out) && own;
+        if (quad)
+            hipLaunchKernelGGL((sample_sigma_kernel<T, true, SigmaParams>), grid, dim3(256), 0, s, plain);
+        else
+            hipLaunchKernelGGL((sample_sigma_kernel<T, false, SigmaParams>), grid, dim3(256), 0, s, plain);
+    }
+}
+
+template <typename T>
+void launch_sigma_init(const SampleParams& p, const SigmaInitParams& f, int64_t per_row, hipStream_t s) {
+    const bool quad = (per_row % 4) == 0 && quad_aligned<float>(p.x) && quad_aligned<T>(p.in) && quad_aligned<float>(f.init) &&
+                      quad_aligned<float>(f.eps_out);
+    const dim3 grid(posterior_blocks(p.n_total));
+    if (quad)
+        hipLaunchKernelGGL((sample_sigma_init_kernel<T, true>), grid, dim3(256), 0, s, p, f);
+    else
+        hipLaunchKernelGGL((sample_sigma_init_kernel<T, false>), grid, dim3(256), 0, s, p, f);
+}
+
+}  // namespace
+
+extern "C" int ddpm_sample_sigma_init(float* x, void* model_in, float* t_model, int* cursor, const float* timesteps,
+                                      const float* init, float* eps_out, int B, int64_t per_row, int I, int start, float k,
+                                      float nn, float c_in, int cfg, int shared, uint64_t seed, int dtype, void* stream) {
+    if (!x || !model_in || !t_model || !cursor || !timesteps || B < 1 || per_row < 1 || I < 1 || start < 0 || start >= I ||
+        !known_dtype(dtype))
+        return LORA_E_BADARG;
+    SampleParams p{};
+    p.x = x; p.in = model_in; p.cursor = cursor;
+    p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = I; p.cfg = cfg ? 1 : 0; p.seed = (uint32_t)seed;
+    p.shared_row = shared ? per_row : 0;
+    SigmaInitParams f{};
+    f.init = init; f.eps_out = eps_out; f.t_model = t_model; f.timesteps = timesteps; f.start = start;
+    f.k = k; f.nn = nn; f.c_in = c_in;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case LORA_F32: launch_sigma_init<float>(p, f, per_row, s); break;
+        case LORA_F16: launch_sigma_init<half_t>(p, f, per_row, s); break;
+        default: launch_sigma_init<bf16_t>(p, f, per_row, s); break;
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+extern "C" int ddpm_sample_sigma(float* x, float* xs, float* hist, const void* model_out, void* model_in, float* t_model,
+                                 const int* cursor, const float* timesteps, const float* coef, const int* plan, float* z_out,
+                                 const float* mask, const float* init, const float* keep_coef, int B, int64_t per_row, int64_t hw,
+                                 int I, int cfg, int shared, float guidance_scale, int dtype, void* stream) {
+    if (!x || !xs || !hist || !model_out || !model_in || !t_model || !cursor || !timesteps || !coef || !plan || B < 1 ||
+        per_row < 1 || I < 1 || !known_dtype(dtype))
+        return LORA_E_BADARG;
+    const bool keep = mask != nullptr;
+    if (keep && !keep_args_ok(mask, init, keep_coef, per_row, hw)) return LORA_E_BADARG;
+    KeepSigmaParams m{};
+    SampleParams& p = m.s;
+    p.x = x; p.out = model_out; p.in = model_in; p.cursor = const_cast<int*>(cursor); p.coef = coef; p.z_out = z_out;
+    p.n_total = (int64_t)B * per_row; p.rows = cfg ? 2 * B : B; p.S = I; p.cfg = cfg ? 1 : 0;
+    p.guidance = guidance_scale;
+    p.shared_row = shared ? per_row : 0;
+    m.xs = xs; m.hist = hist; m.plan = plan; m.t_model = t_model; m.timesteps = timesteps;
+    if (keep) m.k = KeepParams{mask, init, keep_coef, per_row, hw};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case LORA_F32: launch_sigma<float>(m, per_row, keep, s); break;
+        case LORA_F16: launch_sigma<half_t>(m, per_row, keep, s); break;
+        default: launch_sigma<bf16_t>(m, per_row, keep, s); break;
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}

@@ -1,4 +1,5 @@
-"""Sampling latents with the model being trained: the DDPM / DDIM / PLMS / DPM-Solver++(2M) loop around the UNet forward.
+"""Sampling latents with the model being trained: the DDPM / DDIM / PLMS / DPM-Solver++(2M) / Euler / Heun loop around the UNet
+forward.
 
 The reference samples in three places — `evaluate_pipe(..., n_step=50)` with `guidance_scale=5.0` (lora_diffusion/utils.py:112-163)
 on a pipeline built around the TRAINING DDPMScheduler every `save_steps` (lora_diffusion/cli_lora_pti.py:370-402), the class
@@ -49,8 +50,20 @@ on WHETHER there is a table and on R, never on its values — one recording serv
 shares the UNet never sees it.  The grouped q/k/v and context-K/V launches stand aside while it is installed.  `shared_noise=True`
 gives every sample the draws of the B = 1 run of the same seed (x_T, the variance noise, the start noise the keep blend
 regenerates: the `_shared` entries of csrc/ddpm_loss.hip) — "equal seed" in the reference's loops.
+Sigma-space methods ("k_euler", "euler_a", "heun"; `karras_sigmas=True`; plain Euler is spelt "k_euler" here because
+`LatentSampler(method="euler")` is an unknown-method error that callers rely on — `sigma_schedule` itself calls it "euler"):
+two of the reference's notebooks set `EulerAncestralDiscreteScheduler` before they sample (scripts/lora_training_process_visualized.ipynb:57, 40 and 50 steps;
+scripts/merge_lora_with_lora.ipynb:74, 30 steps).  `sigma_schedule` computes k-diffusion's Euler, Euler-ancestral and Heun steps
+on a FRACTIONAL timestep grid; the state lives in sigma space (x_T = σ₀·z) and the model is fed x/√(σ²+1) with the σ of the next
+evaluation, written by the step launch itself (csrc/ddpm_loss.hip: ddpm_sample_sigma — fp32 timesteps, the variance noise of the
+one-step kernel and the saved state / history slot of the multistep kernel in one launch).  `timesteps`, `run_timesteps` and the
+callback's timestep are floats there; `latents` mid-run are in sigma space — √(σ²+1) times the model input — and are model-space
+latents once the run completes (σ = 0).  Image-to-image starts at table row k0 (2·k0 for heun) from init + σ_{k0}·ε: Heun needs
+no warm-up, so the tail rows of the full tables are the fresh sub-run; the keep blend re-noises the original to init + σ·ε with the
+σ of the next evaluation (`sigma_keep_schedule`).  `lora_scales` and `shared_noise` as above.
 Out of scope: VAE encode / decode, starting from cached moments, 9-channel inpainting UNets, per-row strengths, prompts,
-clip_sample / thresholding, PRK steps, Euler / Heun, the SDE variants, Karras sigmas.
+clip_sample / thresholding, PRK steps, DPM2 and the SDE / Brownian-tree variants, `leading` / `trailing` spacings for the
+sigma-space methods (and their init_noise_sigma = √(σmax²+1)), per-row schedules.
 """
 import contextlib
 import math
@@ -66,6 +79,10 @@ from .ops import ROW_SCALES
 
 METHODS = ("ddpm", "ddim")
 MULTISTEP_METHODS = ("plms", "dpmpp_2m")
+SIGMA_METHODS = ("euler", "euler_a", "heun")  # sigma space, fractional timesteps: ddpm_sample_sigma (`sigma_schedule`'s names)
+# LatentSampler's names for them.  Plain Euler is "k_euler" there (the k-diffusion front ends' name for it): `method="euler"` has
+# always been an unknown-method error of LatentSampler — callers and tests rely on it — and stays one.
+SAMPLER_SIGMA_METHODS = {"k_euler": "euler", "euler_a": "euler_a", "heun": "heun"}
 PUSH, SAVE, USE_SAVED = 1, 2, 4  # plan flags of ddpm_sample_multistep (include/lora_hip.h)
 
 
@@ -220,6 +237,110 @@ def multistep_schedule(method: str, num_inference_steps: int, v_prediction: bool
         torch.from_numpy(plan)
 
 
+def sigma_schedule(method: str, num_inference_steps: int, v_prediction: bool, *, karras_sigmas: bool = False, timesteps=None,
+                   num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                   coef_dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(timesteps float64 [I], sigmas float64 [S + 1], coef fp32 [I, 8] = (p, q, a, c0, c1, s, n, σ_eval), plan int32 [I, 5] =
+    (0, 0, 0, 0, flags)) of the sigma-space methods "euler", "euler_a" and "heun" (k-diffusion's sample_euler,
+    sample_euler_ancestral, sample_heun; Karras et al. 2022, Algorithm 1 for Heun) for the I model evaluations of a run:
+        h = p·x + q·o;  base = xs if USE_SAVED else x;  x' = a·base + c0·h + c1·H + s·z;  SAVE: xs ← x;  PUSH: H ← h;
+        the next model input is n·x'
+    — float64 rounded once (`coef_dtype=torch.float64`: not rounded); flags as in `multistep_schedule`.  A coefficient of
+    history or saved state that is not used is exactly 0 (the kernel then reads nothing).
+    Sigma table: table[t] = √((1−ᾱ_t)/ᾱ_t), betas and T as in `sampler_schedule`.  Grid, S = num_inference_steps:
+      default: τ = linspace(0, T−1, S) reversed — FRACTIONAL, 999, 978.61, 958.22, … at 50 steps — and σ_i the linear
+          interpolation of the table at τ_i (S = 1: τ_0 = T − 1, the noisiest row, not linspace's 0);
+      `karras_sigmas`: σ_i = (σmax^{1/ρ} + i/(S−1)·(σmin^{1/ρ} − σmax^{1/ρ}))^ρ, ρ = 7, σmin = table[0], σmax = table[T−1]
+          (S = 1: σ_0 = σmax), τ_i by linear interpolation in log σ (k-diffusion's sigma_to_t);
+      `timesteps=`: an explicit strictly descending grid of S numbers inside [0, T−1], sigmas interpolated as in the default
+          grid (exclusive with `karras_sigmas`);
+      σ_S = 0 on all three.
+    At σ, in k-diffusion's formulation: ε-prediction denoised = x − σ·o, v-prediction denoised = x/(σ²+1) − o·σ/√(σ²+1);
+    d = (x − denoised)/σ = p·x + q·o with (p, q) = (0, 1) for ε and (σ/(σ²+1), 1/√(σ²+1)) for v; the model input is c_in(σ)·x,
+    c_in(σ) = 1/√(σ²+1).  Stepping σ → σ':
+      "euler":   x' = x + (σ' − σ)·d.  I = S.
+      "euler_a": σ_up = √(σ'²(σ²−σ'²)/σ²), σ_down = √(σ'² − σ_up²);  x' = x + (σ_down − σ)·d + σ_up·z.  I = S; σ_up = 0 at the
+          last step.
+      "heun":    every step with σ' > 0 is two iterations — A at τ_i: d₁ pushed, x saved, x' = x + (σ'−σ)·d₁; B at τ_{i+1} on
+          the predicted state: x'' = xs + (σ'−σ)/2·d₂ + (σ'−σ)/2·H[d₁], USE_SAVED, nothing pushed — and the last step is one
+          Euler iteration: I = 2S − 1, `timesteps` repeats τ_{i+1}.
+    s is the noise scale, n = c_in of the NEXT evaluation's σ (1 in the last row), σ_eval the σ this iteration's model
+    evaluation sees (not read by the kernel).
+    Conventions: x_T = σ₀·z (k-diffusion, and diffusers of the reference's era — not √(σmax²+1)·z), and the `linspace`
+    spacing, which is all that era's Euler schedulers had.  On a shared integer grid "euler" is DDIM at η = 0 and "euler_a"
+    DDIM at η = 1 for the state c_in(σ)·x (tests/test_sigma_host.py pins it against `sampler_schedule`).
+    diffusers and k-diffusion are not part of the reference tree: restated from the paper and the published samplers, parity
+    UNPINNED beyond this repository's own stateful float64 restatement (tests/sigma_reference.py) and that identity."""
+    T, S = int(num_train_timesteps), int(num_inference_steps)
+    if method not in SIGMA_METHODS:
+        raise ValueError(f"unknown sigma-space sampling method {method!r}: one of {SIGMA_METHODS}")
+    if T < 1 or S < 1 or S > T:
+        raise ValueError(f"num_inference_steps must lie in [1, num_train_timesteps = {T}]; got {S}")
+    if coef_dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"coef_dtype must be torch.float32 or torch.float64; got {coef_dtype}")
+    if timesteps is not None and karras_sigmas:
+        raise ValueError("timesteps= and karras_sigmas exclude each other")
+    betas = np.linspace(float(beta_start) ** 0.5, float(beta_end) ** 0.5, T, dtype=np.float64) ** 2
+    acp = np.cumprod(1.0 - betas)
+    table = np.sqrt((1.0 - acp) / acp)
+    rows = np.arange(T, dtype=np.float64)
+    if karras_sigmas:
+        rho = 7.0
+        lo, hi = table[0] ** (1.0 / rho), table[T - 1] ** (1.0 / rho)
+        ramp = np.arange(S, dtype=np.float64) / (S - 1) if S > 1 else np.zeros(1)
+        sig = (hi + ramp * (lo - hi)) ** rho
+        tau = np.interp(np.log(sig), np.log(table), rows)
+    else:
+        if timesteps is None:
+            tau = np.linspace(0.0, T - 1.0, S, dtype=np.float64)[::-1].copy() if S > 1 else np.array([T - 1.0])
+        else:
+            tau = np.array([float(t) for t in timesteps], dtype=np.float64)
+            if tau.shape != (S,):
+                raise ValueError(f"timesteps= must hold num_inference_steps = {S} numbers; got {tau.shape[0]}")
+        sig = np.interp(tau, rows, table)
+    if not (np.all(np.isfinite(tau)) and tau[0] <= T - 1 and tau[-1] >= 0.0 and np.all(np.diff(tau) < 0.0)):
+        raise ValueError(f"the timestep grid must be strictly descending inside [0, {T - 1}]")
+    sig = np.append(sig, 0.0)
+
+    def pq(s):
+        return (s / (s * s + 1.0), 1.0 / math.sqrt(s * s + 1.0)) if v_prediction else (0.0, 1.0)
+
+    def c_in(s):
+        return 1.0 / math.sqrt(s * s + 1.0)
+
+    its = []  # (τ, (p, q, a, c0, c1, s, n, σ_eval), flags)
+    for i in range(S):
+        s0, s1 = float(sig[i]), float(sig[i + 1])
+        last = i == S - 1
+        n_next = 1.0 if last else c_in(s1)
+        if method == "euler_a":
+            up = math.sqrt(s1 * s1 * (s0 * s0 - s1 * s1) / (s0 * s0))
+            down = math.sqrt(s1 * s1 - up * up)
+            its.append((tau[i], (*pq(s0), 1.0, down - s0, 0.0, up, n_next, s0), 0))
+        elif method == "euler" or last:
+            its.append((tau[i], (*pq(s0), 1.0, s1 - s0, 0.0, 0.0, n_next, s0), 0))
+        else:
+            half = 0.5 * (s1 - s0)
+            its.append((tau[i], (*pq(s0), 1.0, s1 - s0, 0.0, 0.0, n_next, s0), PUSH | SAVE))
+            its.append((tau[i + 1], (*pq(s1), 1.0, half, half, 0.0, n_next, s1), USE_SAVED))
+    coef = np.array([it[1] for it in its], dtype=np.float64)
+    plan = np.zeros((len(its), 5), dtype=np.int32)
+    plan[:, 4] = [it[2] for it in its]
+    return torch.from_numpy(np.array([it[0] for it in its], dtype=np.float64)), torch.from_numpy(sig), \
+        torch.from_numpy(coef.astype(np.float32) if coef_dtype == torch.float32 else coef), torch.from_numpy(plan)
+
+
+def sigma_keep_schedule(coef) -> torch.Tensor:
+    """fp32 [I, 2] = (k_j, n_j) of the keep blend for a `sigma_schedule` coef table (float64 or fp32 [I, 8]): in sigma space
+    the original at the state's noise level is init + σ·ε, so (1, σ of the NEXT evaluation) — σ_eval of row j + 1, which after a
+    Heun stage A and after its stage B alike is σ_{i+1} — and (1, 0) in the last row."""
+    sig = coef[:, 7].double()
+    out = torch.ones((sig.shape[0], 2), dtype=torch.float64)
+    out[:-1, 1] = sig[1:]
+    out[-1, 1] = 0.0
+    return out.float()
+
+
 def partial_start(num_inference_steps: int, strength: float) -> Tuple[int, int]:
     """(n, k0) of an image-to-image run: n = min(int(S·strength), S) grid steps, from grid index k0 = S − n.  ValueError for a
     strength outside (0, 1] or not finite, and for n == 0 — the noised image after zero steps is not a sample."""
@@ -261,7 +382,12 @@ class LatentSampler:
     caller divides by 0.18215 and decodes).  Defaults are evaluate_pipe's: 50 steps, guidance 5.0, the training scheduler's
     DDPM.  `method`: "ddpm", "ddim" (any η), or the deterministic multistep "plms" (SD 1.x's own scheduler: the class images,
     visualize_progress) and "dpmpp_2m" (η must be 0); those run `num_model_evaluations` iterations — S + 1 for plms — of
-    ddpm_sample_multistep, and `timesteps`, `step()` and the callback count iterations, not grid steps.
+    ddpm_sample_multistep, and `timesteps`, `step()` and the callback count iterations, not grid steps.  "k_euler" (plain Euler;
+    "euler" stays an unknown method, as it was), "euler_a"
+    (the reference notebooks' EulerAncestralDiscreteScheduler) and "heun" run in sigma space on ddpm_sample_sigma (η must be 0;
+    `karras_sigmas=True`: the Karras grid, an error with the other methods): `timesteps` / `run_timesteps` are float64 and
+    fractional, the callback gets a float, `sigmas` holds σ_0 … σ_{S−1}, 0, heun runs 2S − 1 iterations, and `latents` are in
+    sigma space until the run completes (module docstring).
     `guidance_scale <= 1` or no negative conditioning: one B-row pass per step (diffusers' do_classifier_free_guidance);
     else 2B rows, unconditional first.  Stepwise: `begin(...)`, then `step()` until it returns False, then `latents`.
     capture_graph: one denoising iteration — UNet forward, ddpm_sample_step, ddpm_sample_advance — is recorded once per (shapes,
@@ -281,19 +407,29 @@ class LatentSampler:
     layer's own `scale`; `shared_noise`: every sample draws what the B = 1 run of the seed draws (module docstring)."""
 
     def __init__(self, unet, num_inference_steps: int = 50, guidance_scale: float = 5.0, method: str = "ddpm", eta: float = 0.0,
-                 v_prediction: bool = False, capture_graph: bool = True):
+                 v_prediction: bool = False, capture_graph: bool = True, karras_sigmas: bool = False):
         self.unet = unet
         self.guidance_scale = float(guidance_scale)
-        self._schedule_args = (str(method), int(num_inference_steps), bool(v_prediction), float(eta))
-        if method not in METHODS + MULTISTEP_METHODS:
-            raise ValueError(f"unknown sampling method {method!r}: one of {METHODS + MULTISTEP_METHODS}")
+        self._schedule_args = (str(method), int(num_inference_steps), bool(v_prediction), float(eta), bool(karras_sigmas))
+        if method not in METHODS + MULTISTEP_METHODS + tuple(SAMPLER_SIGMA_METHODS):
+            raise ValueError(f"unknown sampling method {method!r}: one of "
+                             f"{METHODS + MULTISTEP_METHODS + tuple(SAMPLER_SIGMA_METHODS)}")
         self._multistep = method in MULTISTEP_METHODS
-        if self._multistep:
+        self._sigma = method in SAMPLER_SIGMA_METHODS
+        if karras_sigmas and not self._sigma:
+            raise ValueError(f"karras_sigmas belongs to the sigma-space methods {tuple(SAMPLER_SIGMA_METHODS)}; got {method!r}")
+        self._sigmas = None
+        if self._sigma:
+            if float(eta) != 0.0:
+                raise ValueError(f"{method!r} takes no eta (\"euler_a\" is the ancestral form): eta must be 0; got {eta}")
+            self.timesteps, self._sigmas, self.coef, self.plan = sigma_schedule(
+                SAMPLER_SIGMA_METHODS[method], int(num_inference_steps), bool(v_prediction), karras_sigmas=bool(karras_sigmas))
+        elif self._multistep:
             if float(eta) != 0.0:
                 raise ValueError(f"{method!r} is deterministic: eta must be 0; got {eta}")
             self.timesteps, self.coef, self.plan = multistep_schedule(str(method), int(num_inference_steps), bool(v_prediction))
         else:
-            self.timesteps, self.coef = sampler_schedule(*self._schedule_args)  # (raises for a bad method / step count / eta)
+            self.timesteps, self.coef = sampler_schedule(*self._schedule_args[:4])  # (raises for a bad method / step count / eta)
             self.plan = None
         self.num_inference_steps = int(num_inference_steps)
         self.capture_graph = bool(capture_graph)
@@ -312,18 +448,27 @@ class LatentSampler:
 
     @property
     def run_timesteps(self) -> torch.Tensor:
-        """int64 [run_evaluations]: the model timestep of every evaluation of the run begun."""
+        """[run_evaluations]: the model timestep of every evaluation of the run begun — int64, float64 for the sigma-space
+        methods (their grid is fractional)."""
         return self._run_timesteps
+
+    @property
+    def sigmas(self) -> Optional[torch.Tensor]:
+        """float64 [S + 1]: σ_0 … σ_{S−1}, 0 of a sigma-space method (`sigma_schedule`); None for the others."""
+        return None if self._sigmas is None else self._sigmas.clone()
 
     def _run_tables(self, k0: int):
         """(first table row, run length, timesteps, coef, plan) of the run that starts at grid step k0, as full-size tables.
         "ddpm" / "ddim": the tables as they are, from row k0.  Multistep: the fresh sub-run's I' rows in the tail rows
         [I − I', I) — the recorded I stays valid — the rows before them as in the full run (never reached)."""
         n_it = self.num_model_evaluations
+        if self._sigma:  # Heun needs no warm-up: the tail rows of the full table ARE the fresh sub-run, from stage A of step k0
+            row = 2 * k0 if self._schedule_args[0] == "heun" else k0
+            return row, n_it - row, self.timesteps, self.coef, self.plan
         if not self._multistep:
             return k0, n_it - k0, self.timesteps, self.coef, None
         if k0 not in self._partial:
-            method, S, v, _ = self._schedule_args
+            method, S, v = self._schedule_args[:3]
             ts, coef, plan = multistep_schedule(method, S, v, first_step=k0)
             start = n_it - ts.shape[0]
             full = [self.timesteps.clone(), self.coef.clone(), self.plan.clone()]
@@ -418,7 +563,9 @@ class LatentSampler:
         if out.dtype != st.model_in.dtype:
             out = out.to(st.model_in.dtype)
         keep = st.mask is not None
-        if self._multistep:
+        if self._sigma:
+            nat.ddpm_sample_sigma(st, out.contiguous(), self.guidance_scale, keep=keep)
+        elif self._multistep:
             (nat.ddpm_sample_multistep_keep if keep else nat.ddpm_sample_multistep)(st, out.contiguous(), self.guidance_scale)
         else:
             (nat.ddpm_sample_step_keep if keep else nat.ddpm_sample_step)(st, out.contiguous(), self.guidance_scale)
@@ -505,7 +652,10 @@ class LatentSampler:
             if self._state is None or key != self._key or fp != self._fp:
                 self._recorder.drop()  # before the buffers it reads are replaced
                 self._key, self._fp = key, fp
-                if self._multistep:
+                if self._sigma:
+                    self._state = nat.SigmaState.alloc((B, *latent_shape), dtype, cfg, self.timesteps, self.coef, self.plan,
+                                                       ehs.device, with_init=has_init, with_mask=has_mask)
+                elif self._multistep:
                     # (history ring and saved state stay uninitialised: a coefficient of exactly 0 keeps them unread)
                     self._state = nat.MultistepState.alloc((B, *latent_shape), dtype, cfg, self.timesteps, self.coef, self.plan,
                                                            ehs.device, with_init=has_init, with_mask=has_mask)
@@ -537,12 +687,22 @@ class LatentSampler:
                     st.plan.copy_(plan)
                 if has_mask:
                     st.mask.copy_(keep_mask)
-                    st.keep_coef[row:row + self._run_len].copy_(keep_schedule(self._run_timesteps))
-                ab = float(trainer_acp(int(self._run_timesteps[0])))
-                start = lambda: nat.ddpm_sample_init_from(st, seed, row, math.sqrt(ab), math.sqrt(1.0 - ab))  # noqa: E731
+                    st.keep_coef[row:row + self._run_len].copy_(sigma_keep_schedule(coef[row:]) if self._sigma else
+                                                                keep_schedule(self._run_timesteps))
+                if self._sigma:  # the start state is init + σ_{k0}·ε, the first model input c_in(σ_{k0}) times it
+                    s0 = float(self._sigmas[partial[1]])
+                    start = lambda: nat.ddpm_sample_sigma_init(st, seed, row, 1.0, s0, 1.0 / math.sqrt(s0 * s0 + 1.0),  # noqa: E731
+                                                               from_init=True)
+                else:
+                    ab = float(trainer_acp(int(self._run_timesteps[0])))
+                    start = lambda: nat.ddpm_sample_init_from(st, seed, row, math.sqrt(ab), math.sqrt(1.0 - ab))  # noqa: E731
             else:
                 self._run_len, self._run_timesteps = self.num_model_evaluations, self.timesteps
-                start = lambda: nat.ddpm_sample_init(st, seed)  # noqa: E731
+                if self._sigma:  # x_T = σ₀·z
+                    s0 = float(self._sigmas[0])
+                    start = lambda: nat.ddpm_sample_sigma_init(st, seed, 0, 0.0, s0, 1.0 / math.sqrt(s0 * s0 + 1.0))  # noqa: E731
+                else:
+                    start = lambda: nat.ddpm_sample_init(st, seed)  # noqa: E731
             start()
             if self.capture_graph and self._recorder.graph is None:
                 # the warm-up passes move the state and the cursor: the run is begun again behind them
@@ -600,5 +760,6 @@ class LatentSampler:
             for i in range(self._run_len):
                 self.step()
                 if callback is not None:
-                    callback(i, int(self._run_timesteps[i]), self._state.x)
+                    t = self._run_timesteps[i]
+                    callback(i, float(t) if self._sigma else int(t), self._state.x)
             return self._state.x.clone()

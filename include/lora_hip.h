@@ -553,6 +553,48 @@ int ddpm_sample_multistep_keep_shared(float* x, float* xs, float* hist, const vo
                                       void* stream);
 
 /*
+ * Sigma-space sampling — k-diffusion's Euler, Euler-ancestral and Heun.  Two of the reference's notebooks switch the pipeline
+ * to `EulerAncestralDiscreteScheduler` before they sample (scripts/lora_training_process_visualized.ipynb:57, then 40 and 50
+ * steps; scripts/merge_lora_with_lora.ipynb:74, then 30 steps), and the equal-seed comparison loop of utils.py:191-211 runs
+ * under whichever scheduler the pipeline carries.  diffusers and k-diffusion are not part of the reference tree: the methods
+ * are restated from Karras et al. 2022 and k-diffusion's published samplers, parity unpinned beyond this repository's own
+ * stateful float64 restatement (tests/sigma_reference.py) and the identity euler == DDIM(η = 0), euler_a == DDIM(η = 1) on a
+ * shared integer grid (tests/test_sigma_host.py).
+ * The state lives in sigma space (x_T = σ₀·z), the model is fed c_in(σ)·x = x/√(σ²+1) with the σ of the NEXT evaluation, and
+ * the timestep grid is fractional: `timesteps` [I] and `t_model` [rows] are FP32 here, int64 everywhere above.
+ *   ddpm_sample_sigma_init : x = fp32(k·init) + fp32(nn·ε), or x = fp32(nn·ε) with init == NULL (text-to-image: nn = σ₀; k is
+ *       not read); ε the x_T draw of ddpm_sample_init at equal seed (stream 3, key (seed, 0)); model_in = cast(fp32(c_in·x)),
+ *       twice under cfg; t_model = timesteps[start]; cursor = {start, seed's low word}; eps_out (nullable) gets ε.  k, nn, c_in
+ *       and start are HOST arguments: the launch stays outside a recording.
+ *   ddpm_sample_sigma : per iteration i = cursor[0] (seed = cursor[1]), (p, q, a, c0, c1, s, n, σ_eval) = coef[i], fp32 [I, 8],
+ *       flags = plan[i][4], int32 [I, 5] with the flag bits of ddpm_sample_multistep (sampling.sigma_schedule):
+ *           o    = u + g·(c − u)                              as ddpm_sample_step
+ *           h    = p·x + q·o                                  d = (x − denoised)/σ
+ *           base = USE_SAVED ? xs : x
+ *           x'   = a·base + c0·h + c1·H + s·z                 left to right, every product rounded on its own, no fma;
+ *                                                             z (stream 4, key (seed, i)) drawn only where s ≠ 0
+ *           SAVE: xs ← x;   PUSH: H ← h                       (hist is ONE slot, fp32 [B, per_row])
+ *           keep (mask != NULL): x' ← fp32(m·y) + fp32((1−m)·x'), y = fp32(k_i·init) + fp32(n_i·ε), as ddpm_sample_step_keep
+ *           x ← x';   model_in ← cast(fp32(n·x')), twice under cfg;   t_model ← timesteps[min(i+1, I−1)]
+ *       A term whose coefficient is exactly 0 is neither loaded nor added: xs and H may be uninitialised until a Heun stage B
+ *       reads them.  σ_eval is not read.  z_out (nullable) gets z (zeros where s == 0).  mask == NULL launches the
+ *       instantiation without the blend (init and keep_coef are then not read, hw is ignored).  shared != 0: the draws of the
+ *       `_shared` entries.  A cursor outside [0, I) reads and writes nothing; the cursor is not moved: ddpm_sample_advance.
+ * 4-element accesses under the alignment rule of the entries above (hw % 4 == 0 too with a mask), element by element otherwise —
+ * the same bits.  LORA_E_BADARG for a null pointer (init, eps_out, z_out, and the three keep pointers together, excepted), an
+ * unknown dtype, B, per_row or I < 1, start outside [0, I), and with a mask a null init / keep_coef, hw < 1 or per_row % hw != 0 —
+ * before any HIP call.  No workspace, nothing retained, capturable.
+ */
+int ddpm_sample_sigma_init(float* x, void* model_in, float* t_model, int* cursor, const float* timesteps,
+                           const float* init /* nullable */, float* eps_out /* nullable */, int B, int64_t per_row, int I,
+                           int start, float k, float nn, float c_in, int cfg, int shared, uint64_t seed, int dtype, void* stream);
+int ddpm_sample_sigma(float* x, float* xs, float* hist, const void* model_out, void* model_in, float* t_model, const int* cursor,
+                      const float* timesteps, const float* coef, const int* plan, float* z_out /* nullable */,
+                      const float* mask /* nullable */, const float* init /* nullable */, const float* keep_coef /* nullable */,
+                      int B, int64_t per_row, int64_t hw, int I, int cfg, int shared, float guidance_scale, int dtype,
+                      void* stream);
+
+/*
  * The two ops sandwiched by the hot path inside a transformer block, as streaming kernels.
  *   geglu_gate_fwd : out[M,C]  = h · gelu(g)  with [h | g] = y[M,2C], exact (erf) gelu — the body of diffusers'
  *                    GEGLU.forward, the caller of the `proj` LoraInjectedLinear (target class "GEGLU", lora.py:53).

@@ -17,6 +17,10 @@ iteration (ddpm_sample_multistep) is timed next to a replayed DDPM iteration (dd
 num_model_evaluations iterations (plms: steps + 1); their stock route keeps the history in a Python list of tensors, as a
 diffusers scheduler does.  One readable line per repetition and configuration, medians and one JSON line per configuration.
 
+"k_euler" / "euler_a" / "heun" (and --karras for their Karras sigma grid) time ddpm_sample_sigma the same way: heun runs
+2·steps − 1 iterations; their stock route scales the model input, keeps the saved sample and derivative in Python variables and
+passes fractional timesteps, as a k-diffusion sampler does.
+
 --strength S adds an image-to-image route per configuration — `img2img`: a replayed LatentSampler begun from a random start
 image at that strength, min(int(steps·S), steps) grid steps — and --keep-mask a second one, `img2img+mask`, with a keep mask of
 8×8 blocks (ddpm_sample_*_keep).  They alternate with the full run's routes in the same process; every route is reported per
@@ -36,6 +40,7 @@ batch is from member k sampled alone.  --batch is not read in this mode.
     python tools/sample_time.py --sweep 4 --method ddpm plms --steps 50 50
     python tools/sample_time.py --batch 1 --method ddpm plms dpmpp_2m --steps 50 50 20
     python tools/sample_time.py --batch 1 --method plms --steps 50 --strength 0.75 --keep-mask
+    python tools/sample_time.py --batch 1 --method ddpm euler_a heun --steps 50 50 25
 """
 import argparse
 import json
@@ -116,6 +121,35 @@ def stock_multistep_loop(unet, cond, neg, guidance, latent_shape, timesteps, coe
     return x
 
 
+def stock_sigma_loop(unet, cond, neg, guidance, latent_shape, timesteps, sigma0, coef, plan, gen):
+    """The loop around a sigma-space sampler: the scaled model input, fractional timesteps, the saved sample and derivative in
+    Python variables, randn for the ancestral noise, host scalars."""
+    B = cond.shape[0]
+    ctx = torch.cat([neg, cond]).half()
+    x = sigma0 * torch.randn((B, *latent_shape), generator=gen, device="cuda", dtype=torch.float32)
+    c_in, saved, d1 = 1.0 / (sigma0 * sigma0 + 1.0) ** 0.5, None, None
+    with torch.no_grad():
+        for i in range(len(coef)):
+            p, q, a, c0, c1, s, n, _ = coef[i]
+            flags = plan[i][4]
+            model_in = torch.cat([x * c_in] * 2).half()
+            out = unet(model_in, timesteps[i].expand(2 * B), ctx).sample
+            u, cc = out.float().chunk(2)
+            o = u + guidance * (cc - u)
+            h = q * o if p == 0.0 else p * x + q * o
+            nxt = a * (saved if flags & dfa.sampling.USE_SAVED else x) + c0 * h
+            if c1 != 0.0:
+                nxt = nxt + c1 * d1
+            if s != 0.0:
+                nxt = nxt + s * torch.randn(x.shape, generator=gen, device="cuda", dtype=torch.float32)
+            if flags & dfa.sampling.SAVE:
+                saved = x
+            if flags & dfa.sampling.PUSH:
+                d1 = h
+            x, c_in = nxt, n
+    return x
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -124,11 +158,16 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
-def routes_for(unet, method, steps, guidance, cond, neg, shape, gen, strength=None, keep_mask=False):
+def routes_for(unet, method, steps, guidance, cond, neg, shape, gen, strength=None, keep_mask=False, karras=False):
     """(replayed sampler, {route: callable}, {route: iterations of its run}) of one configuration."""
-    replayed = dfa.LatentSampler(unet, steps, guidance, method=method)
-    host = dfa.LatentSampler(unet, steps, guidance, method=method, capture_graph=False)
-    if method in dfa.sampling.MULTISTEP_METHODS:
+    kw = dict(karras_sigmas=True) if karras and method in dfa.sampling.SAMPLER_SIGMA_METHODS else {}
+    replayed = dfa.LatentSampler(unet, steps, guidance, method=method, **kw)
+    host = dfa.LatentSampler(unet, steps, guidance, method=method, capture_graph=False, **kw)
+    if method in dfa.sampling.SAMPLER_SIGMA_METHODS:
+        ts, sigmas, coef, plan = dfa.sigma_schedule(dfa.sampling.SAMPLER_SIGMA_METHODS[method], steps, False, **kw)
+        ts_dev, coef_host, plan_host = ts.float().to("cuda"), [tuple(float(v) for v in row) for row in coef], plan.tolist()
+        stock = lambda: stock_sigma_loop(unet, cond, neg, guidance, shape, ts_dev, float(sigmas[0]), coef_host, plan_host, gen)  # noqa: E731
+    elif method in dfa.sampling.MULTISTEP_METHODS:
         ts, coef, plan = dfa.multistep_schedule(method, steps, False)
         ts_dev, coef_host, plan_host = ts.to("cuda"), [tuple(float(v) for v in row) for row in coef], plan.tolist()
         stock = lambda: stock_multistep_loop(unet, cond, neg, guidance, shape, ts_dev, coef_host, plan_host, gen)  # noqa: E731
@@ -148,7 +187,7 @@ def routes_for(unet, method, steps, guidance, cond, neg, shape, gen, strength=No
         yy, xx = torch.arange(shape[1]).view(-1, 1) // 8, torch.arange(shape[2]).view(1, -1) // 8
         mask = ((yy + xx) % 2).float().expand(cond.shape[0], 1, -1, -1).contiguous().to("cuda")
         for name, m in (("img2img", None),) + ((("img2img+mask", mask),) if keep_mask else ()):
-            sampler = dfa.LatentSampler(unet, steps, guidance, method=method)  # (a sampler each: the recording depends on the mask)
+            sampler = dfa.LatentSampler(unet, steps, guidance, method=method, **kw)  # (a sampler each: the recording depends on the mask)
             routes[name] = lambda sampler=sampler, m=m: sampler.sample(cond, neg, seed=7, init_latents=init, strength=strength,
                                                                        keep_mask=m)
             sampler.begin(cond, neg, seed=7, init_latents=init, strength=strength, keep_mask=m)  # (records; counts the run)
@@ -223,7 +262,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, nargs="+", default=[50])
-    ap.add_argument("--method", nargs="+", default=["ddpm"], choices=dfa.sampling.METHODS + dfa.sampling.MULTISTEP_METHODS)
+    ap.add_argument("--method", nargs="+", default=["ddpm"], choices=dfa.sampling.METHODS + dfa.sampling.MULTISTEP_METHODS +
+                    tuple(dfa.sampling.SAMPLER_SIGMA_METHODS))
+    ap.add_argument("--karras", action="store_true", help="the Karras sigma grid for k_euler / euler_a / heun")
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--strength", type=float, default=None, help="add a replayed image-to-image route at this strength")
     ap.add_argument("--keep-mask", action="store_true", help="with --strength: add the route with a keep mask too")
@@ -242,6 +283,8 @@ def main():
         if a.sweep < 2 or a.strength is not None:
             ap.error("--sweep takes K >= 2 and no --strength")
         return sweep(a)
+    if a.karras and not any(m in dfa.sampling.SAMPLER_SIGMA_METHODS for m in a.method):
+        ap.error("--karras needs one of " + " / ".join(dfa.sampling.SAMPLER_SIGMA_METHODS))
     unet, ctx_dim = build_unet()
     shape = (4, 64, 64)
     g = torch.Generator().manual_seed(2)
@@ -251,7 +294,7 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(3)
     configs = {}
     for method, steps in zip(a.method, a.steps):
-        configs[f"{method} {steps}"] = (method, steps, *routes_for(unet, method, steps, guidance, cond, neg, shape, gen, a.strength, a.keep_mask))
+        configs[f"{method} {steps}"] = (method, steps, *routes_for(unet, method, steps, guidance, cond, neg, shape, gen, a.strength, a.keep_mask, a.karras))
     first, same = {}, {}
     for label, (_, _, replayed, routes, _) in configs.items():  # untimed round: recording, solver searches, allocator
         first[label] = {name: timed(fn) for name, fn in routes.items()}
@@ -273,6 +316,7 @@ def main():
         n_it = its["replayed"]
         print(json.dumps({"gpu": torch.cuda.get_device_name(0), "unet": "sd15", "batch": a.batch, "rows": 2 * a.batch,
                           "method": method, "steps": steps, "iterations": n_it, "route_iterations": its, "strength": a.strength,
+                          "karras": bool(a.karras and method in dfa.sampling.SAMPLER_SIGMA_METHODS),
                           "dtype": "f16", "guidance": guidance,
                           "reps": a.reps, "median_ms": med, "all_ms": times[label],
                           "ms_per_iteration": {k: v / its[k] for k, v in med.items()},
