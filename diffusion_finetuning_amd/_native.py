@@ -118,6 +118,7 @@ SIGNATURES = {
     "attn_merge_heads": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "attn_merge_heads_strided": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
     "group_norm_act_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "group_norm_act_plan": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "group_norm_act_fwd": (_i32, [_vp] * 8 + [_i32, _i32, _i32, _i32, _f32, _i32, _i32, _i32, _vp]),
     "group_norm_act_bwd": (_i32, [_vp] * 10 + [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "group_norm_act_bwd_res": (_i32, [_vp] * 11 + [_i32, _i32, _i32, _i32, _i32, _i32, _vp]),

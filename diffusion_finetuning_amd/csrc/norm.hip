@@ -2,11 +2,13 @@
 // a an optional per-(n,c) addend (the time embedding and the preceding convolution's bias), act = SiLU or identity.
 // Stock PyTorch runs moments → normalise → SiLU as three kernels forward and three more backward, about 13 passes over the
 // activation; here it is a statistics pass and an apply pass each way (5 passes through HBM), and the backward recomputes
-// the normalised value and SiLU' from x, so only x is kept alive.
+// the normalised value and SiLU' from x, so only x is kept alive.  Where an NCHW (n,group) slab is small enough (the planner
+// nchw_one_limit, from measurement) the two passes are one launch: a workgroup keeps its slab in registers, reduces and writes.
 //
 // Two layouts, both with 16-byte accesses:
-//   * NCHW: one wave per (n,c) row of H·W elements in the statistics kernels, so the partials are per channel; the apply
-//     kernels work on a slice of one (n,group) slab per workgroup and fold that group's ≤ cpg channel partials first.
+//   * NCHW, two launches: one wave per (n,c) row of H·W elements in the statistics kernels, so the partials are per channel;
+//     the apply kernels work on a slice of one (n,group) slab per workgroup and fold that group's ≤ cpg channel partials first.
+//   * NCHW, one launch: one workgroup of 1024 threads per (n,group) slab, 2, 5 or 8 chunks per thread; the workspace is unused.
 //   * channels-last (NHWC): a thread owns 8 fixed consecutive channels (which may straddle groups: the group width need not be
 //     a multiple of 8) over a block of rows; a workgroup reduces its rows × all channels through LDS to one partial per group,
 //     S partials per (n,group) in all, and the apply kernels fold them.
@@ -18,6 +20,8 @@
 //   * NCHW: the shift of a row is its first element and the row leaves (mean, M2 = Σd² − (Σd)²/HW); the group's cpg rows are
 //     merged about the group mean.  An element far from the rest of its row costs up to about H·W·2⁻²⁴ of the group's
 //     variance when it is the row's first one (2.4e-5 of rstd measured at H·W = 4096).
+//   * NCHW, one launch: a true two-pass from the registers: the mean, then the sums of e = x + a − mean and e² (the first
+//     corrects the mean by what its own rounding left).  No shift, so no element is special.
 //   * NHWC: a thread's shift per channel is its OWN first row, over the n_t rows it reads of one row block (4 … 32 for the
 //     planner's splits unless H·W exceeds 64·RP·32), and it leaves (n_t, mean_t, M2_t).  The workgroup's fold through LDS and
 //     the fold of the S row blocks merge such triples in two passes: the weighted mean μ of the means, then
@@ -220,6 +224,227 @@ __global__ __launch_bounds__(256) void nchw_apply_bwd_kernel(const T* dy, const 
 #pragma unroll
         for (int e = 0; e < VEC; ++e) o.v[e] = from_f32<T>(r[e]);
         *reinterpret_cast<Chunk<T>*>(dx + off) = o;
+    }
+}
+
+// ------------------------------------------------------------------------------------------- NCHW, one launch per direction
+// One workgroup of kOneThreads per (n,group) slab whose cpg·H·W/8 16-byte chunks fit in K per thread, held in registers: chunk
+// i = thread + j·kOneThreads, j < K, lies in channel i / (H·W/8).  All loads are issued before the first use (an index past the
+// slab is clamped to its last chunk and the value masked), the reductions run wave → LDS → every thread in wave order, and the
+// slab is read from memory once.
+constexpr int kOneThreads = 1024, kOneWaves = kOneThreads / 64;
+constexpr int kOneMaxK = 8, kOneMaxKBwd = 5;  // chunks of x per thread, and of x and of dy in the backward: 128 VGPRs per lane
+
+// two 16-bit values in one register: a thread keeps γ, β and the addend of each of its chunks' channels this way
+template <typename T> __device__ __forceinline__ uint32_t pack2(T lo, T hi) {
+    return (uint32_t)__builtin_bit_cast(uint16_t, lo) | ((uint32_t)__builtin_bit_cast(uint16_t, hi) << 16);
+}
+template <typename T> __device__ __forceinline__ float pack_lo(uint32_t p) { return to_f32<T>(__builtin_bit_cast(T, (uint16_t)(p & 0xffffu))); }
+template <typename T> __device__ __forceinline__ float pack_hi(uint32_t p) { return to_f32<T>(__builtin_bit_cast(T, (uint16_t)(p >> 16))); }
+
+// Between two passes over the registers: the 16-bit values stay as loaded.  Without it the compiler converts the slab to fp32
+// once and keeps that, twice the registers, and spills.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+template <typename T, int K> __device__ __forceinline__ void one_keep_packed(Chunk<T> (&v)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        u32x4 u = __builtin_bit_cast(u32x4, v[j]);
+        asm volatile("" : "+v"(u));
+        v[j] = __builtin_bit_cast(Chunk<T>, u);
+    }
+}
+template <int K> __device__ __forceinline__ void one_keep_packed(uint32_t (&p)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) asm volatile("" : "+v"(p[j]));
+}
+
+// Σ over the workgroup of NV values per thread; every thread gets the totals, summed in wave order
+template <int NV> __device__ __forceinline__ void one_block_sum(float (&v)[NV], float (*red)[kOneWaves]) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        v[k] = wave_sum(v[k]);
+        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        float t = 0.f;
+#pragma unroll
+        for (int w = 0; w < kOneWaves; ++w) t += red[k][w];
+        v[k] = t;
+    }
+}
+
+template <typename T, bool SILU, int K>
+__global__ __launch_bounds__(kOneThreads) void nchw_one_fwd_kernel(const T* x, const T* a, const T* gamma, const T* beta, T* y,
+                                                                   float* mean_out, float* rstd_out, int C, int HW, int G,
+                                                                   float eps) {
+    constexpr int VEC = ElemTraits<T>::kVec;
+    __shared__ float red1[1][kOneWaves], red2[2][kOneWaves];
+    const int ng = blockIdx.x, n = ng / G, g = ng - n * G, cpg = C / G;
+    const int64_t row0 = (int64_t)n * C + (int64_t)g * cpg;
+    const int cpr = HW / VEC, chunks = cpg * cpr;
+    const T* xs = x + row0 * HW;
+    Chunk<T> v[K];
+    uint32_t gb[K], ad[K];  // (γ, β) and (addend, unused) of the chunk's channel
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const int i = min((int)threadIdx.x + j * kOneThreads, chunks - 1), cl = i / cpr;
+        v[j] = load_chunk(xs + i * VEC);
+        gb[j] = pack2<T>(gamma[g * cpg + cl], beta[g * cpg + cl]);
+        ad[j] = a ? pack2<T>(a[row0 + cl], a[row0 + cl]) : 0u;
+    }
+    const float cnt = (float)cpg * (float)HW;
+    // the mean of x + a, then the sums of e = x + a − mean and of e² from the registers: the first corrects the mean by what
+    // its own rounding left, the second is centred
+    float s0[1] = {0.f};
+    one_keep_packed(v), one_keep_packed(ad);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if ((int)threadIdx.x + j * kOneThreads < chunks) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) s0[0] += to_f32<T>(v[j].v[e]) + pack_lo<T>(ad[j]);
+        }
+    }
+    one_block_sum(s0, red1);
+    one_keep_packed(v), one_keep_packed(ad);
+    const float mean0 = s0[0] / cnt;
+    float s[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if ((int)threadIdx.x + j * kOneThreads < chunks) {
+            const float d0 = pack_lo<T>(ad[j]) - mean0;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const float u = to_f32<T>(v[j].v[e]) + d0;
+                s[0] += u;
+                s[1] = fmaf(u, u, s[1]);
+            }
+        }
+    }
+    one_block_sum(s, red2);
+    one_keep_packed(v), one_keep_packed(ad), one_keep_packed(gb);
+    const float cm = s[0] / cnt, mean = mean0 + cm, rstd = rsqrtf(fmaxf(s[1] - s[0] * cm, 0.f) / cnt + eps);
+    if (threadIdx.x == 0) {
+        mean_out[ng] = mean;
+        rstd_out[ng] = rstd;
+    }
+    T* ys = y + row0 * HW;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const int i = threadIdx.x + j * kOneThreads;
+        if (i < chunks) {
+            const float sc = rstd * pack_lo<T>(gb[j]), d = pack_lo<T>(ad[j]) - mean;
+            Chunk<T> o;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) o.v[e] = from_f32<T>(act_f<SILU>(fmaf(to_f32<T>(v[j].v[e]) + d, sc, pack_hi<T>(gb[j]))));
+            *reinterpret_cast<Chunk<T>*>(ys + i * VEC) = o;
+        }
+    }
+}
+
+// The backward with x and dy of the slab in registers.  The group constants are Σ γ·dz and Σ γ·dz·x̂ over the slab; every chunk
+// lies in one channel, so a thread folds γ into its own chunks' sums.  With DA each chunk's (γ·Σdz, Σx̂) also goes to LDS and the
+// waves sum them per channel from there in a fixed order.  dh is fetched with x and dy where the registers allow (K = 2).
+template <typename T, bool SILU, bool DA, int K>
+__global__ __launch_bounds__(kOneThreads) void nchw_one_bwd_kernel(const T* dy, const T* x, const T* a, const T* gamma,
+                                                                   const T* beta, const float* mean_in, const float* rstd_in,
+                                                                   T* dx, T* da, int C, int HW, int G, const T* dh) {
+    constexpr int VEC = ElemTraits<T>::kVec;
+    __shared__ float red[2][kOneWaves];
+    __shared__ float2 chan[DA ? K * kOneThreads : 1];
+    const int ng = blockIdx.x, n = ng / G, g = ng - n * G, cpg = C / G;
+    const int64_t row0 = (int64_t)n * C + (int64_t)g * cpg;
+    const int cpr = HW / VEC, chunks = cpg * cpr;
+    const T* xs = x + row0 * HW;
+    const T* ds = dy + row0 * HW;
+    Chunk<T> v[K], w[K];
+    uint32_t gb[K], ad[K];  // (γ, β) and (addend, unused) of the chunk's channel
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const int i = min((int)threadIdx.x + j * kOneThreads, chunks - 1), cl = i / cpr;
+        v[j] = load_chunk(xs + i * VEC);
+        w[j] = load_chunk(ds + i * VEC);
+        gb[j] = pack2<T>(gamma[g * cpg + cl], beta[g * cpg + cl]);
+        ad[j] = a ? pack2<T>(a[row0 + cl], a[row0 + cl]) : 0u;
+    }
+    constexpr int KH = K <= 2 ? K : 1;  // dh chunks fetched up front
+    const T* hs = dh ? dh + row0 * HW : nullptr;
+    Chunk<T> h[KH];
+    if (K <= 2 && hs) {
+#pragma unroll
+        for (int j = 0; j < KH; ++j) h[j] = load_chunk(hs + min((int)threadIdx.x + j * kOneThreads, chunks - 1) * VEC);
+    }
+    const float mean = mean_in[ng], rs = rstd_in[ng];
+    float c[2] = {0.f, 0.f};  // Σ γ·dz·x̂, Σ γ·dz
+    one_keep_packed(v), one_keep_packed(w), one_keep_packed(ad), one_keep_packed(gb);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const int i = threadIdx.x + j * kOneThreads;
+        if (i < chunks) {
+            const float d = pack_lo<T>(ad[j]) - mean;
+            float p = 0.f, q = 0.f, sx = 0.f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const float xh = (to_f32<T>(v[j].v[e]) + d) * rs;
+                const float dz = to_f32<T>(w[j].v[e]) * act_grad_f<SILU>(fmaf(xh, pack_lo<T>(gb[j]), pack_hi<T>(gb[j])));
+                p += dz;
+                q = fmaf(dz, xh, q);
+                sx += xh;
+            }
+            c[0] = fmaf(pack_lo<T>(gb[j]), q, c[0]);
+            c[1] = fmaf(pack_lo<T>(gb[j]), p, c[1]);
+            if (DA) chan[i] = make_float2(pack_lo<T>(gb[j]) * p, sx);
+        }
+    }
+    one_block_sum(c, red);  // its barrier also publishes chan
+    one_keep_packed(v), one_keep_packed(w), one_keep_packed(ad), one_keep_packed(gb);
+    const float inv = 1.f / ((float)cpg * (float)HW), k1 = c[0] * inv, k2 = c[1] * inv;
+    if (DA) {  // Σ_hw dx of each channel; one channel per group: Σ_hw dx = 0 exactly, written as such
+        // lanes per channel: a power of two, no more than a row has chunks and few enough that the workgroup takes all channels
+        // at once where it can (every halving step of the fold costs an LDS round trip)
+        int L = 1;
+        while (L < cpr && L < 64 && 2 * L * cpg <= kOneThreads) L <<= 1;
+        const int lane = threadIdx.x & 63, per = 64 / L, sub = lane / L, sl = lane & (L - 1);
+        for (int c0 = (threadIdx.x >> 6) * per; c0 < cpg; c0 += kOneWaves * per) {
+            const int cl = c0 + sub;
+            float gp = 0.f, sxc = 0.f;
+            if (cl < cpg)
+                for (int t = sl; t < cpr; t += L) {
+                    const float2 u = chan[cl * cpr + t];
+                    gp += u.x;
+                    sxc += u.y;
+                }
+            for (int off = L >> 1; off > 0; off >>= 1) {
+                gp += __shfl_xor(gp, off, 64);
+                sxc += __shfl_xor(sxc, off, 64);
+            }
+            if (cl < cpg && sl == 0) da[row0 + cl] = from_f32<T>(cpg == 1 ? 0.f : rs * (gp - (float)HW * k2 - k1 * sxc));
+        }
+    }
+    T* os = dx + row0 * HW;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const int i = threadIdx.x + j * kOneThreads;
+        if (i < chunks) {
+            const float d = pack_lo<T>(ad[j]) - mean;
+            float r[VEC];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const float xh = (to_f32<T>(v[j].v[e]) + d) * rs;
+                const float dz = to_f32<T>(w[j].v[e]) * act_grad_f<SILU>(fmaf(xh, pack_lo<T>(gb[j]), pack_hi<T>(gb[j])));
+                r[e] = rs * (fmaf(dz, pack_lo<T>(gb[j]), -k2) - xh * k1);
+            }
+            if (hs) {  // the gradient that reaches x along the residual path joins before the one rounding (a uniform branch)
+                const Chunk<T> u = K <= 2 ? h[j < KH ? j : 0] : load_chunk(hs + i * VEC);
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) r[e] += to_f32<T>(u.v[e]);
+            }
+            Chunk<T> o;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) o.v[e] = from_f32<T>(r[e]);
+            *reinterpret_cast<Chunk<T>*>(os + i * VEC) = o;
+        }
     }
 }
 
@@ -536,6 +761,48 @@ int check_shape(int N, int C, int HW, int G, int channels_last) {
     return LORA_OK;
 }
 
+// Chunks per thread of the one-launch NCHW form for this call, or 0 for the two-launch form: a function of the shape and the
+// direction alone.  One workgroup per slab leaves CUs idle when there are fewer slabs than CUs, and the 16-bit ↔ fp32 and SiLU
+// arithmetic of a large slab then takes longer on one CU than the second launch costs, so the largest slab (in 16-byte chunks)
+// that goes to one launch grows with the number of slabs.  The limits are the largest size classes at which one launch was
+// faster inside a replayed graph for the identity, SiLU and SiLU + addend variants at N·G = 32, 128 and 256 slabs
+// (profiles/r13_norm_one_launch_sweep.log; profiles/README.md says which comparison each limit rests on); slab counts in
+// between take the limit of the count below them.
+constexpr int kOneCapFwd = kOneMaxK * kOneThreads, kOneCapBwd = kOneMaxKBwd * kOneThreads;
+int nchw_one_limit(int slabs, bool backward) {
+#ifdef NORM_ONE_FORCE  // dev builds of tools/norm_one_launch_sweep.py: 0 = two launches everywhere, 1 = one wherever the registers allow
+    return NORM_ONE_FORCE ? (backward ? kOneCapBwd : kOneCapFwd) : 0;
+#else
+    if (slabs >= 256) return backward ? kOneCapBwd : kOneCapFwd;  // 80 KB / 128 KB of 16-bit elements
+    if (slabs >= 128) return backward ? 2880 : 2560;              // 45 KB / 40 KB
+    return backward ? 1280 : 1920;                                // 20 KB / 30 KB
+#endif
+}
+
+int nchw_one_k(int N, int C, int HW, int G, bool backward) {
+    const int64_t chunks = (int64_t)(C / G) * (HW / 8);
+    if (chunks > nchw_one_limit(N * G, backward)) return 0;
+    return chunks <= 2 * kOneThreads ? 2 : chunks <= 5 * kOneThreads ? 5 : kOneMaxK;
+}
+
+template <typename T, bool SILU, int K>
+void launch_one_fwd(const T* x, const T* a, const T* gamma, const T* beta, T* y, float* mean, float* rstd, int N, int C, int HW,
+                    int G, float eps, hipStream_t s) {
+    hipLaunchKernelGGL((nchw_one_fwd_kernel<T, SILU, K>), dim3(N * G), dim3(kOneThreads), 0, s, x, a, gamma, beta, y, mean, rstd, C,
+                       HW, G, eps);
+}
+
+template <typename T, bool SILU, int K>
+void launch_one_bwd(const T* dy, const T* x, const T* a, const T* gamma, const T* beta, const float* mean, const float* rstd, T* dx,
+                    T* da, int N, int C, int HW, int G, const T* dh, hipStream_t s) {
+    if (da)
+        hipLaunchKernelGGL((nchw_one_bwd_kernel<T, SILU, true, K>), dim3(N * G), dim3(kOneThreads), 0, s, dy, x, a, gamma, beta,
+                           mean, rstd, dx, da, C, HW, G, dh);
+    else
+        hipLaunchKernelGGL((nchw_one_bwd_kernel<T, SILU, false, K>), dim3(N * G), dim3(kOneThreads), 0, s, dy, x, a, gamma, beta,
+                           mean, rstd, dx, da, C, HW, G, dh);
+}
+
 template <typename T, bool SILU>
 int run_fwd(const void* x_, const void* a_, const void* gamma_, const void* beta_, void* y_, float* mean, float* rstd, void* ws,
             int N, int C, int HW, int G, float eps, int channels_last, hipStream_t s) {
@@ -548,6 +815,10 @@ int run_fwd(const void* x_, const void* a_, const void* gamma_, const void* beta
         hipLaunchKernelGGL(nhwc_stats_fwd_kernel<T>, dim3(p.S, N), dim3(kNhwcThreads), 0, s, x, a, part, C, HW, G, p.rpb_stats);
         hipLaunchKernelGGL((nhwc_apply_fwd_kernel<T, SILU>), dim3(p.SA, N), dim3(kNhwcThreads), 0, s, x, a, gamma, beta, y, mean,
                            rstd, part, C, HW, G, p.S, p.rpb_stats, p.rpb_apply, eps);
+    } else if (const int k = nchw_one_k(N, C, HW, G, false)) {
+        if (k == 2) launch_one_fwd<T, SILU, 2>(x, a, gamma, beta, y, mean, rstd, N, C, HW, G, eps, s);
+        else if (k == 5) launch_one_fwd<T, SILU, 5>(x, a, gamma, beta, y, mean, rstd, N, C, HW, G, eps, s);
+        else launch_one_fwd<T, SILU, kOneMaxK>(x, a, gamma, beta, y, mean, rstd, N, C, HW, G, eps, s);
     } else {
         const int rows = N * C;
         hipLaunchKernelGGL(nchw_stats_fwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, s, x, a, part, rows, HW);
@@ -577,6 +848,9 @@ int run_bwd(const void* dy_, const void* x_, const void* a_, const void* gamma_,
                                mean, rstd, part, cpart, C, HW, G, p.rpb_stats);
         hipLaunchKernelGGL((nhwc_apply_bwd_kernel<T, SILU>), dim3(p.SA, N), dim3(kNhwcThreads), 0, s, dy, x, a, gamma, beta, mean,
                            rstd, dx, da, part, cpart, C, HW, G, p.S, p.rpb_apply);
+    } else if (const int k = nchw_one_k(N, C, HW, G, true)) {
+        if (k == 2) launch_one_bwd<T, SILU, 2>(dy, x, a, gamma, beta, mean, rstd, dx, da, N, C, HW, G, dh, s);
+        else launch_one_bwd<T, SILU, kOneMaxKBwd>(dy, x, a, gamma, beta, mean, rstd, dx, da, N, C, HW, G, dh, s);
     } else {
         const int rows = N * C;
         hipLaunchKernelGGL((nchw_stats_bwd_kernel<T, SILU>), dim3((rows + 3) / 4), dim3(256), 0, s, dy, x, a, gamma, beta, mean,
@@ -595,6 +869,11 @@ extern "C" int64_t group_norm_act_workspace_bytes(int N, int C, int HW, int grou
     if (!channels_last) return align16((int64_t)N * C * 3 * 4);
     const NhwcPlan p = nhwc_plan(N, C, HW);
     return align16((int64_t)N * groups * p.S * 2 * 4) + (want_da ? align16((int64_t)N * p.S * 3 * C * 4) : 0);
+}
+
+extern "C" int group_norm_act_plan(int N, int C, int HW, int groups, int channels_last, int backward) {
+    if (check_shape(N, C, HW, groups, channels_last) != LORA_OK) return 0;
+    return !channels_last && nchw_one_k(N, C, HW, groups, backward != 0) ? 1 : 2;
 }
 
 extern "C" int group_norm_act_fwd(const void* x, const void* addend, const void* gamma, const void* beta, void* y, float* mean,

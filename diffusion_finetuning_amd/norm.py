@@ -61,7 +61,8 @@ def _hip_layout(x, groups, weight, bias, addend):
 
 def group_norm_act(x: torch.Tensor, groups: int, weight, bias, eps: float, act: bool, addend=None) -> torch.Tensor:
     """act(GroupNorm(x + addend[:, :, None, None])) for x [N,C,H,W]; `act` True = SiLU, False = identity; `addend` [N,C] or
-    None.  The result has x's memory layout.  One statistics and one apply kernel each way on the HIP path."""
+    None.  The result has x's memory layout.  On the HIP path one statistics and one apply kernel each way, or a single kernel
+    where an NCHW (n, group) slab fits one workgroup's registers (`_native.lib().group_norm_act_plan` tells which)."""
     layout = _hip_layout(x, groups, weight, bias, addend)
     if layout is None:
         h = x if addend is None else x + addend[:, :, None, None]

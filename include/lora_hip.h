@@ -621,13 +621,18 @@ int attn_merge_heads_strided(const void* src, void* dst, int B, int N, int H, in
  * (needs C % 8 == 0, C <= 4096).  The group width C/groups may be anything.  groups <= 256.  dtype f16 / bf16 only
  * (LORA_E_UNSUPPORTED for f32 and for the shapes above: the caller keeps the stock composite).
  * Statistics, the normalised value and the activation are fp32 up to the one rounding of y / dx / da.  Two launches each way
- * (statistics, apply), partial sums folded in a fixed order, no atomics: results are bit-reproducible.
+ * (statistics, apply), or one where group_norm_act_plan says so; sums folded in a fixed order, no atomics: results are
+ * bit-reproducible.
  *   group_norm_act_fwd : writes y and the per-(n,group) mean / rstd [N,groups] fp32 of x + a that the backward takes.
  *   group_norm_act_bwd : recomputes the normalised value and act' from x; writes dx and, when da is not null, da [N,C] (the
  *                        gradient of the addend, a by-product of the per-channel sums).  No gamma / beta gradients.
  * workspace: group_norm_act_workspace_bytes(...) bytes (0: unsupported shape), 16-byte aligned, caller-owned, per call.
  */
 int64_t group_norm_act_workspace_bytes(int N, int C, int HW, int groups, int channels_last, int want_da);
+/* How many kernels the forward (backward = 0) or the backward (1) launches for this shape: 1 where an NCHW (n,group) slab is
+ * small enough for one workgroup to keep it in registers, else 2; 0 for shapes the kernels do not cover.  Host code only, and
+ * a function of these arguments alone.  The workspace size does not depend on it (the one-launch form leaves it unused). */
+int group_norm_act_plan(int N, int C, int HW, int groups, int channels_last, int backward);
 int group_norm_act_fwd(const void* x, const void* addend /* nullable */, const void* gamma, const void* beta, void* y,
                        float* mean, float* rstd, void* workspace, int N, int C, int HW, int groups, float eps, int act,
                        int channels_last, int dtype, void* stream);
