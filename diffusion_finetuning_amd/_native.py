@@ -127,6 +127,12 @@ SIGNATURES = {
     "tokens_nchw_supported": (_i32, [_i32, _i32, _i32, _i32]),
     "tokens_to_nchw_add": (_i32, [_vp] * 3 + [_i32, _i32, _i32, _i32, _vp]),
     "nchw_to_tokens": (_i32, [_vp] * 2 + [_i32, _i32, _i32, _i32, _vp]),
+    "conv3x3_small_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "conv3x3_small_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "conv3x3_small_plan": (_i32, [_i64, _i32, _i32, _i32]),
+    "conv3x3_small_plan_channels": (_i32, [_i32, _i32, _i32]),
+    "conv3x3_small_pack": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "conv3x3_small": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "add_layer_norm_max_channels": (_i32, []),
     "add_layer_norm_fwd": (_i32, [_vp] * 8 + [_i64, _i32, _f32, _i32, _vp]),
     "add_layer_norm_bwd": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _vp]),
@@ -1328,6 +1334,44 @@ def residual_bias_add(h, res, b1, b2):
     _check(lib().residual_bias_add(_ptr(h), _ptr(res), _ptr(b1), _ptr(b2), _ptr(out), N, C, H * W, dtype_code(h.dtype),
                                    _stream(h)), "residual_bias_add")
     return out
+
+
+def conv3x3_small_supported(N: int, Cin: int, Cout: int, H: int, W: int, dtype) -> bool:
+    """Whether csrc/conv_small.hip covers a 3×3 / stride 1 / padding 1 convolution of this shape and dtype (no launch)."""
+    return dtype in (torch.float16, torch.bfloat16) and bool(lib().conv3x3_small_supported(N, Cin, Cout, H, W, dtype_code(dtype)))
+
+
+def conv3x3_small_plan(pixels: int, Cin: int, Cout: int, dtype) -> bool:
+    """Whether the library's planner routes a frozen convolution of this class to csrc/conv_small.hip (no launch)."""
+    return dtype in (torch.float16, torch.bfloat16) and bool(lib().conv3x3_small_plan(int(pixels), Cin, Cout, dtype_code(dtype)))
+
+
+def conv3x3_small_plan_channels(Cin: int, Cout: int, dtype) -> bool:
+    """Whether the planner routes these channels at some pixel count: the filters worth packing up front (no launch)."""
+    return dtype in (torch.float16, torch.bfloat16) and bool(lib().conv3x3_small_plan_channels(Cin, Cout, dtype_code(dtype)))
+
+
+def conv3x3_small_pack(weight, backward: bool):
+    """The pack of weight [C_out, C_in, 3, 3] (dense) for the forward, or of its flipped and swapped form for backward-data."""
+    _require_device(weight)
+    Cout, Cin = weight.shape[:2]
+    packed = torch.empty(weight.numel(), dtype=weight.dtype, device=weight.device)
+    _check(lib().conv3x3_small_pack(_ptr(weight), _ptr(packed), Cin, Cout, int(backward), dtype_code(weight.dtype),
+                                    _stream(weight)), "conv3x3_small_pack")
+    return packed
+
+
+def conv3x3_small(x, pack, bias, Cout: int):
+    """y [N, Cout, H, W] of the 3×3 convolution of the NCHW-contiguous x with a pack of conv3x3_small_pack."""
+    _require_device(x, pack, bias)
+    N, Cin, H, W = x.shape
+    code = dtype_code(x.dtype)
+    nbytes = int(lib().conv3x3_small_workspace_bytes(N, Cin, Cout, H, W, code))
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=x.device)
+    y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
+    _check(lib().conv3x3_small(_ptr(x), _ptr(pack), _ptr(bias), _ptr(y), _ptr(ws), nbytes, N, Cin, Cout, H, W, code, _stream(x)),
+           "conv3x3_small")
+    return y
 
 
 def tokens_nchw_supported(N: int, C: int, HW: int, dtype) -> bool:

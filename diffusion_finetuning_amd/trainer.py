@@ -776,6 +776,11 @@ class LoraTrainer:
         self.opt = FusedClipAdamW(self.slab, groups, betas, eps, max_grad_norm)
         self.device = self.slab.params.device
         self.dtype = stp.compute_dtype(unet)
+        if self.device.type == "cuda" and getattr(unet, "conv3x3_front", False):
+            # a model whose forward runs its 3×3 convolutions through conv.conv3x3 says so with `conv3x3_front = True`; its frozen
+            # wide filters are packed once, now: nothing is packed while a step is being recorded (conv.py).  Other models pay nothing
+            from .conv import prepack_conv3x3
+            prepack_conv3x3(unet)
         self.tail_events = None  # a list switches on the timing of the host-launched tail of every replayed step
         self.token_table = None
         if train_emb:

@@ -12,7 +12,9 @@ GroupNorms run through the fused norm + addend + SiLU passes of diffusion_finetu
 passes at the blocks' edges that only move or add activations through its block-edge fronts: a ResNet block's tail (the biases
 of conv2 and conv_shortcut and the residual sum) is one pass, a transformer's NCHW ↔ token re-layouts run through an LDS tile
 with the exit residual added on the way, and the gradient of a block input that two branches read is joined inside the
-GroupNorm backward.  All of it sits behind `_fused_norms`.
+GroupNorm backward.  The frozen 3×3 stride-1 convolutions of the ResNets and the upsamplers go through
+diffusion_finetuning_amd.conv.conv3x3 (`_conv3x3` below), which runs the few-pixel, wide-filter classes (the 8×8 and 16×16 levels
+at batch 4) on packed weights in HIP and hands everything else to F.conv2d.  All of it sits behind `_fused_norms`.
 Weights are random-init: there are no SD checkpoints offline.
 """
 import math
@@ -119,6 +121,17 @@ def _tokens_to_nchw_add(tok, res):
     return tokens_to_nchw_add(tok, res)
 
 
+CONV3X3_ROUTE = "auto"  # route of the trunk's frozen 3×3 convolutions (diffusion_finetuning_amd.conv.conv3x3); tests force it
+
+
+def _conv3x3(x, weight, bias=None):
+    """The 3×3 / stride 1 / padding 1 convolution of a ResNet block or an upsampler: F.conv2d, or the packed-weight HIP kernel
+    where the weight is frozen and the planner routes the class (few pixels, wide filters)."""
+    from diffusion_finetuning_amd.conv import conv3x3
+
+    return conv3x3(x, weight, bias, CONV3X3_ROUTE)
+
+
 def _residual_bias_add(h, res, b1, b2=None):
     from diffusion_finetuning_amd.norm import residual_bias_add
 
@@ -156,9 +169,9 @@ class ResnetBlock2D(nn.Module):
                 # the shortcut reads the x that norm1 hands through, so its gradient joins norm1's dx; conv2 and conv_shortcut
                 # run without their biases, which go into the one pass that sums the two branches
                 xp, n = _norm_act_res(self.norm1, x, True)
-                h = F.conv2d(n, self.conv1.weight, None, padding=1)
+                h = _conv3x3(n, self.conv1.weight)
                 n = _norm_act(self.norm2, h, True, self.time_emb_proj(F.silu(temb)) + self.conv1.bias)
-                h = F.conv2d(n, self.conv2.weight, None, padding=1)
+                h = _conv3x3(n, self.conv2.weight)
                 if self.conv_shortcut is None:
                     return _residual_bias_add(h, xp, self.conv2.bias)
                 return _residual_bias_add(h, F.conv2d(xp, self.conv_shortcut.weight, None), self.conv2.bias,
@@ -332,7 +345,10 @@ class Upsample2D(nn.Module):
         self.conv = nn.Conv2d(c, c, 3, padding=1)
 
     def forward(self, x):
-        return self.conv(F.interpolate(x, scale_factor=2.0, mode="nearest"))
+        x = F.interpolate(x, scale_factor=2.0, mode="nearest")
+        if _fused_norms(x) and type(self.conv) is nn.Conv2d:
+            return _conv3x3(x, self.conv.weight, self.conv.bias)
+        return self.conv(x)
 
 
 class DownBlock(nn.Module):
@@ -396,6 +412,8 @@ class UpBlock(nn.Module):
 class UNet2DConditionModel(nn.Module):
     """`unet(noisy_latents, timesteps, encoder_hidden_states).sample` like the diffusers model the reference
     trainers call (training_scripts/train_lora_dreambooth.py:843)."""
+
+    conv3x3_front = True  # the ResNets and upsamplers call diffusion_finetuning_amd.conv.conv3x3: LoraTrainer prepacks their filters
 
     def __init__(self, cfg: Optional[UNetConfig] = None):
         super().__init__()

@@ -668,6 +668,36 @@ int tokens_to_nchw_add(const void* tok, const void* res /* nullable */, void* ou
 int nchw_to_tokens(const void* x, void* tok, int N, int C, int HW, int dtype, void* stream);
 
 /*
+ * 3x3, stride 1, padding 1 convolution with FROZEN weights where the pixels are few and the filters wide (csrc/conv_small.hip):
+ *     y[n,k,h,w] = sum_{c,r,s} x[n,c,h+r-1,w+s-1] * w[k,c,r,s] (+ bias[k]),   x [N,C_in,H,W], y [N,C_out,H,W] NCHW-contiguous,
+ * f16 / bf16, fp32 accumulation, one rounding at the store.  C_in and C_out multiples of 32; any N, H, W >= 1 whose tiles fit
+ * (conv3x3_small_supported: 64 pixels with their halo in 768 padded positions, i.e. W up to about 350; fewer than 2^31 elements
+ * per tensor).  An implicit GEMM over K-slices whose fp32 partials a second launch folds in slice order: two launches, no
+ * atomics, bit-reproducible.
+ *   conv3x3_small_pack : re-lays w [C_out,C_in,3,3] (C_in, C_out as given here, whatever `backward`) into the order the main loop
+ *                        fetches (documented in conv_small.hip); packed has C_in*C_out*9 elements, 16-byte aligned.  backward = 1
+ *                        packs w'[c,k,r,s] = w[k,c,2-r,2-s], with which dx = conv3x3_small(dy, pack', C_in := C_out, C_out := C_in).
+ *                        Run once per weight and direction; the pack is stale once w changes.
+ *   conv3x3_small      : bias [C_out] of the same dtype, nullable.  workspace: conv3x3_small_workspace_bytes(...) bytes (0:
+ *                        unsupported), 16-byte aligned, caller-owned, per call; y must not overlap x.
+ *   conv3x3_small_plan : 1 where this library is the faster way to run a frozen convolution of `pixels` = N*H*W output pixels
+ *                        in BOTH directions, 0 where the stock convolution is, or where nothing was measured: host code, a
+ *                        function of its arguments alone, and exactly the classes of the committed sweep log
+ *                        (tools/conv_small_sweep.py): 256 pixels, 1280 <-> {1280, 2560}; 1024 pixels, 1280 <-> {640, 1280, 1920, 2560}.
+ *   conv3x3_small_plan_channels : 1 where conv3x3_small_plan routes these channels at some pixel count (which filters are
+ *                        worth packing before the activation's size is known).
+ * Statuses, decided before any launch: LORA_E_BADARG (null pointer, non-positive size, unknown dtype, workspace too small),
+ * LORA_E_UNSUPPORTED (f32, a shape outside the above), LORA_E_ALIGN (x, pack, y or workspace off a 16-byte boundary).
+ */
+int conv3x3_small_supported(int N, int C_in, int C_out, int H, int W, int dtype);
+int64_t conv3x3_small_workspace_bytes(int N, int C_in, int C_out, int H, int W, int dtype);
+int conv3x3_small_plan(int64_t pixels, int C_in, int C_out, int dtype);
+int conv3x3_small_plan_channels(int C_in, int C_out, int dtype);
+int conv3x3_small_pack(const void* w, void* packed, int C_in, int C_out, int backward, int dtype, void* stream);
+int conv3x3_small(const void* x, const void* wpack, const void* bias /* nullable */, void* y, void* workspace,
+                  int64_t workspace_bytes, int N, int C_in, int C_out, int H, int W, int dtype, void* stream);
+
+/*
  * LayerNorm of the transformer blocks with the residual add in front of it folded in (csrc/layer_norm.hip), over rows [M, C]
  * with the last dimension contiguous; the caller's `attn(norm(x)) + x` chain, one launch each way:
  *     forward : h = x + delta, rounded to the storage type (bit-equal to the stock sum);  y = (h − mean)·rstd·gamma + beta,

@@ -1,0 +1,128 @@
+"""Per-class timing of the UNet's frozen 3×3 stride-1 convolutions: stock F.conv2d against csrc/conv_small.hip.
+
+    python tools/conv_small_sweep.py [--configs 4x64,8x64,1x96] [--max-pixels 4096] [--calls 32] [--replays 20] [--out FILE]
+
+For every eligible (pixels, C_in, C_out) of benchmark configs 2, 4 and 5 — batch 4 and batch 8 at 64² latents, batch 1 at 96² —
+it prints µs per call of both sides, forward and backward-data, f16, each measured inside a replayed graph of `--calls` calls
+(the median of `--replays` replays), which is how the trainer runs them.  The calls of a graph go round a set of distinct
+weight tensors of the class, about `--weight-mb` MB of them, so that a filter comes from HBM as it does in the model, where
+gigabytes pass between two uses of it, and not from the 256 MB Infinity Cache.  The stock side runs as the model pays for it:
+`torch.backends.cudnn.benchmark` on and MIOPEN_USER_DB_PATH on a copy of the shipped find-db, as bench.conv_autotune sets
+them, so its figure covers all of its launches (re-layouts, zero fill, GEMM).  A class belongs in `conv3x3_small_plan` only if
+the HIP kernel wins in BOTH directions; the last column says what the planner does now."""
+import argparse
+import faulthandler
+import glob
+import os
+import shutil
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def unet_classes():
+    """(level, C_in, C_out) of the 3×3 stride-1 convolutions of the SD1.5 / SD2.1 UNet (ResNet conv1 / conv2 and the
+    upsamplers, which run at the size they produce); level l runs at (latent / 2^l)² pixels per image."""
+    return [
+        (0, 320, 320), (0, 960, 320), (0, 640, 320), (0, 640, 640),
+        (1, 320, 640), (1, 640, 640), (1, 1920, 640), (1, 1280, 640), (1, 960, 640), (1, 1280, 1280),
+        (2, 640, 1280), (2, 1280, 1280), (2, 2560, 1280), (2, 1920, 1280),
+        (3, 1280, 1280), (3, 2560, 1280),
+    ]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="4x64,8x64,1x96", help="batch x latent size of the workloads to cover")
+    ap.add_argument("--max-pixels", type=int, default=4096)
+    ap.add_argument("--calls", type=int, default=32)
+    ap.add_argument("--replays", type=int, default=20)
+    ap.add_argument("--weight-mb", type=int, default=600, help="distinct filter bytes a graph cycles through (0: one filter)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    faulthandler.enable()
+
+    db = tempfile.mkdtemp(prefix="dfa_miopen_db_")
+    for f in glob.glob(os.path.join(ROOT, "harness", "miopen_db", "*.txt")):
+        shutil.copy(f, db)
+    os.environ.setdefault("MIOPEN_USER_DB_PATH", db)
+
+    import torch
+    import torch.nn.functional as F
+
+    from diffusion_finetuning_amd import _native as nat
+
+    torch.backends.cudnn.benchmark = True
+    dev = torch.device("cuda")
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    def timed(fn):
+        """µs per call of fn inside a replayed graph of args.calls calls."""
+        for i in range(2):
+            fn(i)
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(graph, stream=side):
+                for i in range(args.calls):
+                    fn(i)
+        torch.cuda.current_stream().wait_stream(side)
+        graph.replay()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(args.replays):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            graph.replay()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3 / args.calls)
+        ts.sort()
+        return ts[len(ts) // 2]
+
+    cases = set()
+    for batch, latent in (tuple(int(v) for v in c.split("x")) for c in args.configs.split(",")):
+        for level, cin, cout in unet_classes():
+            side = latent >> level
+            if batch * side * side <= args.max_pixels:
+                cases.add((batch, side, cin, cout))
+    say(f"# conv_small sweep: f16, graph of {args.calls} calls over ~{args.weight_mb} MB of distinct filters, median of "
+        f"{args.replays} replays, µs per call")
+    say(f"# {'N':>2} {'HxW':>7} {'pixels':>6} {'C_in':>5} {'C_out':>5} | {'fwd stock':>9} {'fwd hip':>8} | {'bwd stock':>9} {'bwd hip':>8} | wins plan")
+    for batch, side, cin, cout in sorted(cases, key=lambda c: (c[0] * c[1] * c[1], c[2], c[3], c[0])):
+        if not nat.conv3x3_small_supported(batch, cin, cout, side, side, torch.float16):
+            continue
+        x = torch.randn(batch, cin, side, side, device=dev, dtype=torch.float16)
+        dy = torch.randn(batch, cout, side, side, device=dev, dtype=torch.float16)
+        nw = max(1, min(args.calls, (args.weight_mb << 20) // (cin * cout * 18)))
+        ws = [torch.randn(cout, cin, 3, 3, device=dev, dtype=torch.float16) * 0.01 for _ in range(nw)]
+        fwd = [nat.conv3x3_small_pack(w, False) for w in ws]
+        bwd = [nat.conv3x3_small_pack(w, True) for w in ws]
+        # the stock backward-data call is the operator autograd runs for a frozen weight, called directly: a backward through
+        # a forward recorded outside the capture would run on that forward's stream, which is not the capturing one
+        t_fs = timed(lambda i: F.conv2d(x, ws[i % nw], None, padding=1))
+        t_bs = timed(lambda i: torch.ops.aten.convolution_backward(dy, x, ws[i % nw], None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
+                                                                   [True, False, False]))
+        t_fh = timed(lambda i: nat.conv3x3_small(x, fwd[i % nw], None, cout))
+        t_bh = timed(lambda i: nat.conv3x3_small(dy, bwd[i % nw], None, cin))
+        wins = t_fh < t_fs and t_bh < t_bs
+        plan = nat.conv3x3_small_plan(batch * side * side, cin, cout, torch.float16)
+        say(f"  {batch:>2} {side:>3}x{side:<3} {batch * side * side:>6} {cin:>5} {cout:>5} | {t_fs:>9.1f} {t_fh:>8.1f} | {t_bs:>9.1f} {t_bh:>8.1f} | "
+            f"{'yes' if wins else 'no':>4} {'hip' if plan else 'stock'}")
+        del x, dy, ws, fwd, bwd
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    shutil.rmtree(db, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
