@@ -74,6 +74,8 @@ SIGNATURES = {
                                         _i64, _vp]),
     "lora_pack_items": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _vp]),
     "ddpm_mse_fwd_bwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _i64, _i64, _f32, _f32, _vp, _vp, _vp, _i32, _vp]),
+    "ddpm_mse_weighted_fwd_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _f32, _f32, _vp, _vp, _vp, _i32,
+                                         _vp]),
     "lora_mse_workspace_bytes": (_i64, []),
     "lora_mask_prepare": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lora_merge_weight": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp]),
@@ -89,6 +91,10 @@ SIGNATURES = {
     "ddpm_posterior_prologue": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32,
                                        ctypes.c_uint64, ctypes.c_uint64, _i32, _i32, _vp]),
     "ddpm_posterior_sample": (_i32, [_vp, _i32, _vp, _vp, _i32, _i64, _f32, _vp]),
+    "ddpm_noise_prologue_offset": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, ctypes.c_uint64, ctypes.c_uint64,
+                                          _i32, _i32, _i64, _f32, _vp, _vp]),
+    "ddpm_posterior_prologue_offset": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32,
+                                              ctypes.c_uint64, ctypes.c_uint64, _i32, _i32, _i64, _f32, _vp, _vp]),
     "ddpm_sample_init": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, ctypes.c_uint64, _i32, _vp]),
     "ddpm_sample_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _vp]),
     "ddpm_sample_advance": (_i32, [_vp, _i32, _vp]),
@@ -607,6 +613,31 @@ def ddpm_mse_fwd_bwd(pred, target, mask, n_inst: int, n_prior: int, prior_weight
     return loss, dpred
 
 
+def ddpm_mse_weighted_fwd_bwd(pred, target, mask, t, weights, n_inst: int, n_prior: int, prior_weight: float,
+                              grad_scale: float, want_grad: bool = True):
+    """`ddpm_mse_fwd_bwd` with row b weighted by weights[t[b]]: t int64 [rows], weights fp32 [T], both on the device
+    (include/lora_hip.h: ddpm_mse_weighted_fwd_bwd).  Returns (loss fp32 scalar tensor, dpred|None)."""
+    _require_device(pred, target, mask, t, weights)
+    rows = pred.shape[0]
+    assert rows == n_inst + n_prior
+    if t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous():
+        raise ValueError(f"timesteps must be a contiguous int64 [{rows}] tensor; got {t.dtype} {tuple(t.shape)}")
+    if weights.dtype != torch.float32 or weights.dim() != 1 or not weights.numel() or not weights.is_contiguous():
+        raise ValueError(f"the weight table must be a contiguous fp32 [T] tensor; got {weights.dtype} {tuple(weights.shape)}")
+    per_row = pred[0].numel()
+    hw = pred.shape[-1] * pred.shape[-2]
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty_like(pred) if want_grad else None
+    ws = _workspace(pred.device, int(lib().lora_mse_workspace_bytes()), "mse")
+    _check(
+        lib().ddpm_mse_weighted_fwd_bwd(_ptr(pred), _ptr(target), _ptr(mask), _ptr(t), _ptr(weights), weights.numel(), n_inst,
+                                        n_prior, per_row, hw, float(prior_weight), float(grad_scale), _ptr(loss), _ptr(dpred),
+                                        _ptr(ws), dtype_code(pred.dtype), _stream(pred)),
+        "ddpm_mse_weighted_fwd_bwd",
+    )
+    return loss, dpred
+
+
 def lora_mask_prepare(mask_in, h: int, w: int):
     _require_device(mask_in)
     B, _, hin, win = mask_in.shape
@@ -729,6 +760,57 @@ def ddpm_posterior_prologue(moments, sqrt_acp, sqrt_1macp, out_dtype: torch.dtyp
                                          dtype_code(out_dtype), _stream(moments)),
            "ddpm_posterior_prologue")
     return (noisy, target, t, x0, z, eps) if want_draw else (noisy, target, t)
+
+
+def _channel_plane(shape) -> int:
+    """h·w of a [B, C, h, w] latent shape: what one offset-noise normal covers."""
+    if len(shape) != 4:
+        raise ValueError(f"offset noise needs [B, C, h, w] latents; got {tuple(shape)}")
+    return int(shape[2]) * int(shape[3])
+
+
+def ddpm_noise_prologue_offset(x0, sqrt_acp, sqrt_1macp, out_dtype: torch.dtype, seed: int, step: int, v_prediction: bool,
+                               n_timesteps: int = 1000, noise_offset: float = 0.0, want_draw: bool = False):
+    """`ddpm_noise_prologue` with eps' = eps + noise_offset·ξ[b, c], ξ one normal per (row, channel) from Philox stream 3 of
+    the same key; returns (noisy, target, t[, eps', ξ [B, C]]) — include/lora_hip.h: ddpm_noise_prologue_offset."""
+    _require_device(x0, sqrt_acp, sqrt_1macp)
+    B = x0.shape[0]
+    per_row = x0[0].numel()
+    hw = _channel_plane(x0.shape)
+    noisy = torch.empty(x0.shape, dtype=out_dtype, device=x0.device)
+    target = torch.empty(x0.shape, dtype=out_dtype, device=x0.device)
+    t = torch.empty(B, dtype=torch.int64, device=x0.device)
+    eps = torch.empty(x0.shape, dtype=torch.float32, device=x0.device) if want_draw else None
+    xi = torch.empty(x0.shape[:2], dtype=torch.float32, device=x0.device) if want_draw else None
+    _check(lib().ddpm_noise_prologue_offset(_ptr(x0), _ptr(sqrt_acp), _ptr(sqrt_1macp), _ptr(noisy), _ptr(target), _ptr(eps),
+                                            _ptr(t), B, per_row, int(n_timesteps), int(seed) & (2**64 - 1),
+                                            int(step) & (2**64 - 1), int(v_prediction), dtype_code(out_dtype), hw,
+                                            float(noise_offset), _ptr(xi), _stream(x0)),
+           "ddpm_noise_prologue_offset")
+    return (noisy, target, t, eps, xi) if want_draw else (noisy, target, t)
+
+
+def ddpm_posterior_prologue_offset(moments, sqrt_acp, sqrt_1macp, out_dtype: torch.dtype, seed: int, step: int,
+                                   v_prediction: bool, n_timesteps: int = 1000, scale: float = 0.18215,
+                                   noise_offset: float = 0.0, want_draw: bool = False, want_target: bool = True):
+    """`ddpm_posterior_prologue` with the offset noise of `ddpm_noise_prologue_offset`; returns (noisy, target, t[, x0, z,
+    eps', ξ [B, C]]) — include/lora_hip.h: ddpm_posterior_prologue_offset."""
+    _require_device(moments, sqrt_acp, sqrt_1macp)
+    B, per_row, shape = _moments_rows(moments)
+    hw = _channel_plane(shape)
+    dev = moments.device
+    noisy = torch.empty(shape, dtype=out_dtype, device=dev)
+    target = torch.empty(shape, dtype=out_dtype, device=dev) if want_target else None
+    t = torch.empty(B, dtype=torch.int64, device=dev)
+    x0, z, eps = (torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3)) if want_draw else (None, None, None)
+    xi = torch.empty(shape[:2], dtype=torch.float32, device=dev) if want_draw else None
+    _check(lib().ddpm_posterior_prologue_offset(_ptr(moments), dtype_code(moments.dtype), _ptr(sqrt_acp), _ptr(sqrt_1macp),
+                                                _ptr(noisy), _ptr(target), _ptr(x0), _ptr(z), _ptr(eps), _ptr(t), B, per_row,
+                                                int(n_timesteps), float(scale), int(seed) & (2**64 - 1),
+                                                int(step) & (2**64 - 1), int(v_prediction), dtype_code(out_dtype), hw,
+                                                float(noise_offset), _ptr(xi), _stream(moments)),
+           "ddpm_posterior_prologue_offset")
+    return (noisy, target, t, x0, z, eps, xi) if want_draw else (noisy, target, t)
 
 
 def ddpm_posterior_sample(moments, z, scale: float = 0.18215):

@@ -177,19 +177,100 @@ int launch_mse(MseParams p, hipStream_t s) {
     return LORA_OK;
 }
 
-}  // namespace
+// The same loss with one weight per row, looked up on the device by the row's timestep: w_b = weights[t[b]] — Min-SNR-γ
+// (Hang et al. 2023, "Efficient Diffusion Training via Min-SNR Weighting Strategy": min(SNR(t), γ)/SNR(t), divided by SNR + 1
+// instead of SNR for v-prediction) or any table of the caller's.  The reference has no counterpart (its objective is the plain
+// mean); the timesteps of a replayed step exist on the device only, so the lookup cannot be the host's.  The weight is folded
+// into the row's coefficient, coef_row = coef·w_b, read once per 16-byte chunk (a chunk lies inside one row), and everything
+// else is ddpm_mse_kernel's arithmetic word for word: a table of ones leaves its bits.  A timestep outside [0, n_weights) is
+// never used as an index: the row's weight is NaN, so the loss is NaN and the step is skipped like any overflow (the
+// convention for token ids outside the embedding table).  Kernels of their own: ddpm_mse_kernel is not touched.
+struct MseWeightedParams {
+    MseParams m;
+    const int64_t* t;      // [rows]
+    const float* weights;  // [n_weights]
+    int n_weights;
+};
 
-extern "C" int64_t lora_mse_workspace_bytes(void) { return kWsBytes; }
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void ddpm_mse_weighted_kernel(MseWeightedParams q) {
+    __shared__ float s_wave[4];
+    __shared__ bool s_last;
+    const MseParams& p = q.m;
+    const T* pred = static_cast<const T*>(p.pred);
+    const T* target = static_cast<const T*>(p.target);
+    T* dpred = static_cast<T*>(p.dpred);
+    float local = 0.f;
+    const int64_t nvec = p.n_total / VEC;
+    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * 256) {
+        const int64_t i0 = v * VEC;
+        T pv[VEC], tv[VEC], gv[VEC];
+        if constexpr (VEC > 1) {
+            *reinterpret_cast<Chunk<T>*>(pv) = *reinterpret_cast<const Chunk<T>*>(pred + i0);
+            *reinterpret_cast<Chunk<T>*>(tv) = *reinterpret_cast<const Chunk<T>*>(target + i0);
+        } else {
+            pv[0] = pred[i0];
+            tv[0] = target[i0];
+        }
+        // a vector never straddles a row: per_row % VEC == 0 on this path
+        const int64_t row = i0 / p.per_row;
+        const int64_t in_row = i0 - row * p.per_row;
+        const int64_t ti = q.t[row];
+        const float w = (ti >= 0 && ti < (int64_t)q.n_weights) ? q.weights[ti] : __builtin_nanf("");
+        const float coef = (i0 < p.inst_elems ? p.coef_inst : p.coef_prior) * w;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            float mk = 1.f;
+            if (p.mask) mk = p.mask[row * p.hw + (in_row + e) % p.hw];
+            const float a = to_f32<T>(pv[e]) * mk;
+            const float b = to_f32<T>(tv[e]) * mk;
+            const float d = a - b;
+            local = fmaf(coef * d, d, local);
+            gv[e] = from_f32<T>(p.grad_scale * 2.f * coef * d * mk);
+        }
+        if (dpred) {
+            if constexpr (VEC > 1) {
+                *reinterpret_cast<Chunk<T>*>(dpred + i0) = *reinterpret_cast<const Chunk<T>*>(gv);
+            } else {
+                dpred[i0] = gv[0];
+            }
+        }
+    }
+    const float bsum = block_sum_256(local, s_wave);
+    if (publish_partial_and_check_last(bsum, p.partials, p.ticket, &s_last)) {
+        float t = 0.f;
+        for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) t += p.partials[i];
+        t = block_sum_256(t, s_wave);
+        if (threadIdx.x == 0) p.loss_out[0] = t;
+    }
+}
 
-extern "C" int ddpm_mse_fwd_bwd(const void* pred, const void* target, const float* mask, int n_inst,
-                                int n_prior, int64_t per_row, int64_t hw, float prior_weight, float grad_scale,
-                                float* loss_out, void* dpred, void* workspace, int dtype, void* stream) {
+template <typename T>
+int launch_mse_weighted(MseWeightedParams q, hipStream_t s) {
+    constexpr int V = ElemTraits<T>::kVec;
+    const MseParams& p = q.m;
+    const bool vec = (p.per_row % V) == 0 && aligned16(p.pred) && aligned16(p.target) &&
+                     (!p.dpred || aligned16(p.dpred));
+    const int64_t work = vec ? p.n_total / V : p.n_total;
+    int64_t blocks = (work + 255) / 256;
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+    if (blocks < 1) blocks = 1;
+    if (vec)
+        LORA_LAUNCH(PK_MSE, (ddpm_mse_weighted_kernel<T, V>), dim3((unsigned)blocks), dim3(256), 0, s, q);
+    else
+        LORA_LAUNCH(PK_MSE, (ddpm_mse_weighted_kernel<T, 1>), dim3((unsigned)blocks), dim3(256), 0, s, q);
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+// What both loss entries check and fill in before their launch; LORA_OK with the ticket zeroed on `s`.
+int mse_params(MseParams& p, const void* pred, const void* target, const float* mask, int n_inst, int n_prior,
+               int64_t per_row, int64_t hw, float prior_weight, float grad_scale, float* loss_out, void* dpred,
+               void* workspace, hipStream_t s) {
     if (!pred || !target || !loss_out || !workspace) return LORA_E_BADARG;
     if (n_inst < 1 || n_prior < 0 || per_row < 1 || hw < 1 || (per_row % hw) != 0) return LORA_E_BADARG;
     if (!aligned16(workspace)) return LORA_E_ALIGN;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (!lora_zero_ticket(workspace, s)) return LORA_E_LAUNCH;
-    MseParams p{};
     p.pred = pred; p.target = target; p.mask = mask; p.dpred = dpred; p.loss_out = loss_out;
     p.ticket = static_cast<unsigned*>(workspace);
     p.partials = reinterpret_cast<float*>(static_cast<char*>(workspace) + 16);
@@ -199,13 +280,49 @@ extern "C" int ddpm_mse_fwd_bwd(const void* pred, const void* target, const floa
     p.coef_inst = 1.0f / ((float)n_inst * (float)per_row);
     p.coef_prior = n_prior > 0 ? prior_weight / ((float)n_prior * (float)per_row) : 0.f;
     p.grad_scale = grad_scale;
+    return LORA_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t lora_mse_workspace_bytes(void) { return kWsBytes; }
+
+extern "C" int ddpm_mse_fwd_bwd(const void* pred, const void* target, const float* mask, int n_inst,
+                                int n_prior, int64_t per_row, int64_t hw, float prior_weight, float grad_scale,
+                                float* loss_out, void* dpred, void* workspace, int dtype, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MseParams p{};
+    int rc = mse_params(p, pred, target, mask, n_inst, n_prior, per_row, hw, prior_weight, grad_scale, loss_out, dpred,
+                        workspace, s);
+    if (rc != LORA_OK) return rc;
     const double e = dtype == LORA_F32 ? 4.0 : 2.0;
     ProfWork work(e * (double)p.n_total * (dpred ? 3.0 : 2.0), 4.0 * (double)p.n_total);
-    int rc;
     switch (dtype) {
         case LORA_F32: rc = launch_mse<float>(p, s); break;
         case LORA_F16: rc = launch_mse<half_t>(p, s); break;
         case LORA_BF16: rc = launch_mse<bf16_t>(p, s); break;
+        default: rc = LORA_E_BADARG;
+    }
+    return rc;
+}
+
+extern "C" int ddpm_mse_weighted_fwd_bwd(const void* pred, const void* target, const float* mask, const int64_t* t,
+                                         const float* weights, int n_weights, int n_inst, int n_prior, int64_t per_row,
+                                         int64_t hw, float prior_weight, float grad_scale, float* loss_out, void* dpred,
+                                         void* workspace, int dtype, void* stream) {
+    if (!t || !weights || n_weights < 1) return LORA_E_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MseWeightedParams q{};
+    int rc = mse_params(q.m, pred, target, mask, n_inst, n_prior, per_row, hw, prior_weight, grad_scale, loss_out, dpred,
+                        workspace, s);
+    if (rc != LORA_OK) return rc;
+    q.t = t; q.weights = weights; q.n_weights = n_weights;
+    const double e = dtype == LORA_F32 ? 4.0 : 2.0;
+    ProfWork work(e * (double)q.m.n_total * (dpred ? 3.0 : 2.0), 5.0 * (double)q.m.n_total);
+    switch (dtype) {
+        case LORA_F32: rc = launch_mse_weighted<float>(q, s); break;
+        case LORA_F16: rc = launch_mse_weighted<half_t>(q, s); break;
+        case LORA_BF16: rc = launch_mse_weighted<bf16_t>(q, s); break;
         default: rc = LORA_E_BADARG;
     }
     return rc;
@@ -592,6 +709,209 @@ extern "C" int ddpm_posterior_sample(const void* moments, int moments_dtype, con
         case LORA_F32: launch_posterior_sample<float>(moments, z, x0, per_row, n, scale, s); break;
         case LORA_F16: launch_posterior_sample<half_t>(moments, z, x0, per_row, n, scale, s); break;
         default: launch_posterior_sample<bf16_t>(moments, z, x0, per_row, n, scale, s); break;
+    }
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Offset noise inside the two device-drawn prologues (N. Guttenberg, "Diffusion with Offset Noise", 2023 — `--noise_offset` of
+// the diffusers and kohya trainers; the reference has no counterpart): one more normal ξ per (row, channel), added to every
+// element of that channel's noise,
+//     eps' = fmaf(noise_offset, ξ[b, c], eps)
+// and eps' is the noise everywhere downstream (noisy, target, eps_out).  ξ is a FOURTH stream of the step's key (seed, step):
+// with j = b·C + c and C = per_row / hw, counter (j, j>>32, 3, 0), first normal of the Box–Muller mapping above — next to eps
+// (stream 0), t (1) and the posterior z (2), whose counters and arithmetic are unchanged: t and, before the offset is added,
+// eps and z are the bits of the plain prologues.  (The sampler's streams 3 and 4 below belong to another key: (seed, denoising
+// step) of a sampling run, never a training step's.)  noise_offset == 0 selects eps itself, not eps + 0·ξ: every output is
+// then the plain entry's bit for bit, −0 included.
+// One kernel serves both entries: MOMENTS draws the latents as posterior_prologue_kernel does, otherwise x0 is read.  One
+// thread per Philox group; QUAD as above.  A group inside one row can still straddle CHANNELS (hw % 4 != 0 with
+// per_row % 4 == 0), so the channel is tracked per element on both paths: one division per group, then a running channel end.
+namespace {
+
+constexpr uint32_t kStreamOffset = 3u;
+
+struct OffsetParams {
+    PosteriorParams p;  // MOMENTS: as for posterior_prologue_kernel; otherwise moments, x0_out, z_out and scale are unused
+    const float* x0;    // !MOMENTS: the latents, fp32 [B, per_row]
+    float* xi_out;      // nullable, [B, C]
+    int64_t hw, C;
+    float noise_offset;
+};
+
+__device__ __forceinline__ float offset_normal(int64_t j, uint32_t seed, uint32_t step) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)j, (uint32_t)((uint64_t)j >> 32), kStreamOffset, 0u, seed, step, r);
+    float s0, c0;
+    sincosf(6.283185307179586f * u01(r[1]), &s0, &c0);
+    return sqrtf(-2.f * logf(u01(r[0]))) * c0;
+}
+
+template <typename TM, typename TO, bool QUAD, bool MOMENTS>
+__global__ __launch_bounds__(256) void offset_prologue_kernel(OffsetParams q) {
+    const PosteriorParams& p = q.p;
+    const TM* moments = static_cast<const TM*>(p.moments);
+    TO* noisy = static_cast<TO*>(p.noisy);
+    TO* target = static_cast<TO*>(p.target);
+    const bool shifted = q.noise_offset != 0.f;
+    const int64_t groups = (p.n_total + 3) >> 2;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+        Quad<float> eps_q, z_q = {};
+        philox_normals4((uint64_t)g, 0u, p.seed, p.step, eps_q.v);
+        if constexpr (MOMENTS) philox_normals4((uint64_t)g, 2u, p.seed, p.step, z_q.v);
+        float* eps = eps_q.v;
+        const float* z = z_q.v;
+        const int64_t i0 = g * 4;
+        int64_t b = i0 / p.per_row;  // row of the group's first element (B is an int: b fits 32 bits)
+        const uint32_t b_wave = __builtin_amdgcn_readfirstlane((uint32_t)b);  // (see posterior_prologue_kernel)
+        int64_t ti = philox_timestep(b_wave, p.seed, p.step, p.n_timesteps);
+        if ((uint32_t)b != b_wave) ti = philox_timestep((uint32_t)b, p.seed, p.step, p.n_timesteps);
+        // channel of the group's first element, and the element index at which that channel ends
+        int64_t ch = (i0 - b * p.per_row) / q.hw;
+        int64_t ch_end = b * p.per_row + (ch + 1) * q.hw;
+        float xi = offset_normal(b * q.C + ch, p.seed, p.step);
+        if constexpr (QUAD) {
+            const int64_t col = i0 - b * p.per_row;
+            Quad<TM> mean, logvar;
+            Quad<float> x;
+            if constexpr (MOMENTS) {
+                const TM* row = moments + b * 2 * p.per_row + col;
+                mean = *reinterpret_cast<const Quad<TM>*>(row);
+                logvar = *reinterpret_cast<const Quad<TM>*>(row + p.per_row);
+            } else {
+                x = *reinterpret_cast<const Quad<float>*>(q.x0 + i0);
+            }
+            if (col == 0 && p.t_out) p.t_out[b] = ti;
+            const float a = p.sa[ti], s = p.sb[ti];
+            Quad<TO> nv, tv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = i0 + e;
+                if (i >= ch_end) {  // the group runs on into the next channel of its row (a channel has at least one element)
+                    ++ch;
+                    ch_end += q.hw;
+                    xi = offset_normal(b * q.C + ch, p.seed, p.step);
+                }
+                if (q.xi_out && i == ch_end - q.hw) q.xi_out[b * q.C + ch] = xi;
+                if (shifted) eps[e] = fmaf(q.noise_offset, xi, eps[e]);
+                if constexpr (MOMENTS) x.v[e] = posterior_x0(to_f32<TM>(mean.v[e]), to_f32<TM>(logvar.v[e]), z[e], p.scale);
+                nv.v[e] = from_f32<TO>(ddpm_noisy(a, s, x.v[e], eps[e]));
+                tv.v[e] = from_f32<TO>(ddpm_target(a, s, x.v[e], eps[e], p.v_pred));
+            }
+            *reinterpret_cast<Quad<TO>*>(noisy + i0) = nv;
+            if (target) *reinterpret_cast<Quad<TO>*>(target + i0) = tv;
+            if constexpr (MOMENTS) {
+                if (p.x0_out) *reinterpret_cast<Quad<float>*>(p.x0_out + i0) = x;
+                if (p.z_out) *reinterpret_cast<Quad<float>*>(p.z_out + i0) = z_q;
+            }
+            if (p.eps_out) *reinterpret_cast<Quad<float>*>(p.eps_out + i0) = eps_q;
+        } else {
+            int64_t row_end = (b + 1) * p.per_row;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = i0 + e;
+                if (i >= p.n_total) break;
+                if (i >= row_end) {  // the group runs on into the next row(s): per_row may be below 4
+                    b = i / p.per_row;
+                    row_end = (b + 1) * p.per_row;
+                    ti = philox_timestep((uint32_t)b, p.seed, p.step, p.n_timesteps);
+                    ch = 0;  // (i advances by one: the first element of a row the group enters is its column 0)
+                    ch_end = b * p.per_row + q.hw;
+                    xi = offset_normal(b * q.C, p.seed, p.step);
+                } else if (i >= ch_end) {
+                    ++ch;
+                    ch_end += q.hw;
+                    xi = offset_normal(b * q.C + ch, p.seed, p.step);
+                }
+                const int64_t col = i - b * p.per_row;
+                if (col == 0 && p.t_out) p.t_out[b] = ti;
+                if (q.xi_out && i == ch_end - q.hw) q.xi_out[b * q.C + ch] = xi;
+                const float en = shifted ? fmaf(q.noise_offset, xi, eps[e]) : eps[e];
+                const float a = p.sa[ti], s = p.sb[ti];
+                float x;
+                if constexpr (MOMENTS) {
+                    const TM* row = moments + b * 2 * p.per_row + col;
+                    x = posterior_x0(to_f32<TM>(row[0]), to_f32<TM>(row[p.per_row]), z[e], p.scale);
+                } else {
+                    x = q.x0[i];
+                }
+                noisy[i] = from_f32<TO>(ddpm_noisy(a, s, x, en));
+                if (target) target[i] = from_f32<TO>(ddpm_target(a, s, x, en, p.v_pred));
+                if constexpr (MOMENTS) {
+                    if (p.x0_out) p.x0_out[i] = x;
+                    if (p.z_out) p.z_out[i] = z[e];
+                }
+                if (p.eps_out) p.eps_out[i] = en;
+            }
+        }
+    }
+}
+
+template <typename TM, typename TO, bool MOMENTS>
+void launch_offset_prologue(const OffsetParams& q, hipStream_t s) {
+    const PosteriorParams& p = q.p;
+    const bool quad = (p.per_row % 4) == 0 && quad_aligned<TM>(p.moments) && quad_aligned<float>(q.x0) &&
+                      quad_aligned<TO>(p.noisy) && quad_aligned<TO>(p.target) && quad_aligned<float>(p.x0_out) &&
+                      quad_aligned<float>(p.z_out) && quad_aligned<float>(p.eps_out);
+    const dim3 grid(posterior_blocks(p.n_total));
+    if (quad)
+        hipLaunchKernelGGL((offset_prologue_kernel<TM, TO, true, MOMENTS>), grid, dim3(256), 0, s, q);
+    else
+        hipLaunchKernelGGL((offset_prologue_kernel<TM, TO, false, MOMENTS>), grid, dim3(256), 0, s, q);
+}
+
+template <typename TM, bool MOMENTS>
+void launch_offset_prologue_out(const OffsetParams& q, int dtype, hipStream_t s) {
+    switch (dtype) {
+        case LORA_F32: launch_offset_prologue<TM, float, MOMENTS>(q, s); break;
+        case LORA_F16: launch_offset_prologue<TM, half_t, MOMENTS>(q, s); break;
+        default: launch_offset_prologue<TM, bf16_t, MOMENTS>(q, s); break;
+    }
+}
+
+bool offset_args_ok(int64_t per_row, int64_t hw, float noise_offset) {
+    return hw >= 1 && (per_row % hw) == 0 && noise_offset == noise_offset && noise_offset - noise_offset == 0.f;  // (finite)
+}
+
+}  // namespace
+
+extern "C" int ddpm_noise_prologue_offset(const float* x0, const float* sqrt_acp, const float* sqrt_1macp, void* noisy,
+                                          void* target, float* eps_out, int64_t* t_out, int B, int64_t per_row, int n_timesteps,
+                                          uint64_t seed, uint64_t step, int v_prediction, int dtype, int64_t hw,
+                                          float noise_offset, float* xi_out, void* stream) {
+    if (!x0 || !sqrt_acp || !sqrt_1macp || !noisy || B < 1 || per_row < 1 || n_timesteps < 1) return LORA_E_BADARG;
+    if (!known_dtype(dtype) || !offset_args_ok(per_row, hw, noise_offset)) return LORA_E_BADARG;
+    OffsetParams q{};
+    PosteriorParams& p = q.p;
+    p.sa = sqrt_acp; p.sb = sqrt_1macp; p.noisy = noisy; p.target = target; p.eps_out = eps_out; p.t_out = t_out;
+    p.per_row = per_row; p.n_total = (int64_t)B * per_row; p.n_timesteps = n_timesteps;
+    p.seed = (uint32_t)seed; p.step = (uint32_t)step; p.v_pred = v_prediction;
+    q.x0 = x0; q.xi_out = xi_out; q.hw = hw; q.C = per_row / hw; q.noise_offset = noise_offset;
+    launch_offset_prologue_out<float, false>(q, dtype, static_cast<hipStream_t>(stream));
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+extern "C" int ddpm_posterior_prologue_offset(const void* moments, int moments_dtype, const float* sqrt_acp,
+                                              const float* sqrt_1macp, void* noisy, void* target, float* x0_out, float* z_out,
+                                              float* eps_out, int64_t* t_out, int B, int64_t per_row, int n_timesteps,
+                                              float scale, uint64_t seed, uint64_t step, int v_prediction, int dtype, int64_t hw,
+                                              float noise_offset, float* xi_out, void* stream) {
+    if (!moments || !sqrt_acp || !sqrt_1macp || !noisy || B < 1 || per_row < 1 || n_timesteps < 1) return LORA_E_BADARG;
+    if (!known_dtype(moments_dtype) || !known_dtype(dtype) || !offset_args_ok(per_row, hw, noise_offset)) return LORA_E_BADARG;
+    OffsetParams q{};
+    PosteriorParams& p = q.p;
+    p.moments = moments; p.sa = sqrt_acp; p.sb = sqrt_1macp; p.noisy = noisy; p.target = target;
+    p.x0_out = x0_out; p.z_out = z_out; p.eps_out = eps_out; p.t_out = t_out;
+    p.per_row = per_row; p.n_total = (int64_t)B * per_row; p.n_timesteps = n_timesteps;
+    p.seed = (uint32_t)seed; p.step = (uint32_t)step; p.scale = scale; p.v_pred = v_prediction;
+    q.xi_out = xi_out; q.hw = hw; q.C = per_row / hw; q.noise_offset = noise_offset;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (moments_dtype) {
+        case LORA_F32: launch_offset_prologue_out<float, true>(q, dtype, s); break;
+        case LORA_F16: launch_offset_prologue_out<half_t, true>(q, dtype, s); break;
+        default: launch_offset_prologue_out<bf16_t, true>(q, dtype, s); break;
     }
     LORA_LAUNCH_CHECK();
     return LORA_OK;

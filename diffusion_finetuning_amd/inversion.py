@@ -27,7 +27,7 @@ import torch.nn as nn
 from . import _native as nat
 from . import step as stp
 from .formats import load_checkpoint_file, save_checkpoint_file
-from .trainer import ddpm_tables, lr_lambda
+from .trainer import NUM_TRAIN_TIMESTEPS, ddpm_alphas_cumprod, ddpm_tables, lr_lambda
 
 TARGET_NORM = 0.4  # clip_ti_decay's target row norm (cli_lora_pti.py:333)
 
@@ -69,14 +69,19 @@ class InversionTrainer:
     def __init__(self, unet: nn.Module, text_encoder: nn.Module, placeholder_token_ids: Sequence[int], lr: float = 5e-4,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, lr_scheduler: str = "linear",
                  lr_warmup_steps: int = 0, max_train_steps: Optional[int] = 1000, accum_iter: int = 4,
-                 clip_ti_decay: bool = True, v_prediction: bool = False, capture_graph: bool = False, process_group=None):
+                 clip_ti_decay: bool = True, v_prediction: bool = False, capture_graph: bool = False, process_group=None,
+                 snr_gamma: Optional[float] = None, timestep_weights: Optional[torch.Tensor] = None,
+                 noise_offset: float = 0.0):
         """Arguments are train()'s for this phase: `lr` = ti_lr, `weight_decay` = weight_decay_ti, `lr_scheduler` /
         `lr_warmup_steps` / `max_train_steps` = lr_scheduler, lr_warmup_steps, max_train_steps_ti (:659-664), `accum_iter` =
         gradient_accumulation_steps (:518,670).  The optimizer is AdamW(betas, eps) over the token table (:651-657).
         Compute dtype: the UNet's conv weights.  fp32 is the reference's (mixed_precision=False, :685) and the parity route;
         bf16 is an opt-in deviation from it; f16 is refused — the reference's phase has no loss scaler.
         capture_graph: record noise → text encoder → UNet → loss → backward → ti_rows_grad once and replay it; the optimizer
-        launch and the zeroing of the gradient buffer stay outside the recording."""
+        launch and the zeroing of the gradient buffer stay outside the recording.
+        `snr_gamma`, `timestep_weights`, `noise_offset`: LoraTrainer's — Min-SNR-γ or the caller's per-timestep loss weights,
+        looked up inside the loss kernel, and offset noise in the device draw; extensions beyond the reference."""
+        stp.check_objective(snr_gamma, timestep_weights, noise_offset, NUM_TRAIN_TIMESTEPS)
         if process_group is not None:
             raise ValueError("InversionTrainer is single-process, as train_inversion is (cli_lora_pti.py:539)")
         trainable = [n for n, p in unet.named_parameters() if p.requires_grad]
@@ -124,6 +129,10 @@ class InversionTrainer:
         self.exp_avg = torch.zeros_like(self.grad)
         self.exp_avg_sq = torch.zeros_like(self.grad)
         self.sqrt_acp, self.sqrt_1macp = ddpm_tables(device=self.device)
+        self.snr_gamma = None if snr_gamma is None else float(snr_gamma)
+        self.noise_offset = float(noise_offset)
+        self.loss_weights = stp.objective_table(snr_gamma, timestep_weights, ddpm_alphas_cumprod(), self.v_prediction, self.device)
+        self._timestep_weights_digest = stp.table_digest(timestep_weights)
         self.global_step = 0      # micro-steps taken (train_inversion's global_step)
         self.optimizer_steps = 0  # AdamW steps taken (its bias-correction count)
         self.scheduler_epoch = 0  # LambdaLR.last_epoch
@@ -158,7 +167,8 @@ class InversionTrainer:
         return {"lr": self.lr, "weight_decay": self.weight_decay, "betas": [float(b) for b in self.betas], "eps": self.eps,
                 "accum_iter": self.accum_iter, "lr_scheduler": name, "lr_warmup_steps": warmup, "max_train_steps": max_steps,
                 "clip_ti_decay": self.clip_ti_decay, "v_prediction": self.v_prediction,
-                "compute_dtype": str(self.dtype).replace("torch.", "")}
+                "compute_dtype": str(self.dtype).replace("torch.", ""),
+                **stp.objective_config(self.snr_gamma, self._timestep_weights_digest, self.noise_offset)}
 
     def state_dict(self) -> dict:
         """{"meta", "tensors"} like LoraTrainer's: the P placeholder rows of the table, the [P, D] gradient buffer — so a save
@@ -221,12 +231,14 @@ class InversionTrainer:
         if self.module is None:
             raise RuntimeError("InversionTrainer.step after close()")
         stp.check_noise_inputs(latents, moments, noise, timesteps, posterior_noise, seed)
+        stp.check_noise_offset(self.noise_offset, noise)
         if input_ids.device.type == "cpu" and input_ids.numel():
             if int(input_ids.min()) < 0 or int(input_ids.max()) >= self.V:
                 raise IndexError(f"token id out of range for the {self.V}-row embedding table")
         ids = input_ids.to(self.device, torch.int64)
         nz = stp.Noising(self.sqrt_acp, self.sqrt_1macp, self.dtype, self.v_prediction,
-                         max(1, int(self.sqrt_acp.numel() * float(t_multiplier))), float(latent_scale))
+                         max(1, int(self.sqrt_acp.numel() * float(t_multiplier))), float(latent_scale), self.noise_offset,
+                         self.loss_weights)
         self._drawn_from = (moments, posterior_noise)
         g = self.global_step
         self.scheduler_epoch += 1  # lr_scheduler.step() comes first (:293)
@@ -249,7 +261,8 @@ class InversionTrainer:
         Returns the unscaled loss."""
         ehs = self.text_encoder(ids)[0].to(self.dtype)
         pred = self.unet(noisy, timesteps, ehs).sample
-        return stp.loss_backward(pred, target, raw_mask, pred.shape[0], 0, 1.0, 1.0 / self.accum_iter)
+        return stp.loss_backward(pred, target, raw_mask, pred.shape[0], 0, 1.0, 1.0 / self.accum_iter, timesteps,
+                                 self.loss_weights)
 
     def _step_eager(self, latents, noise, timesteps, ids, mask, seed, g, nz):
         moments, posterior_noise = self._drawn_from
@@ -266,7 +279,8 @@ class InversionTrainer:
     def _fingerprint(self):
         """What a recording bakes in besides the shapes: scalars passed as kernel arguments and the address of the table the
         gather reads."""
-        return (self.v_prediction, self.accum_iter, self.module.weight.data_ptr())
+        return (self.v_prediction, self.accum_iter, self.module.weight.data_ptr(), self.noise_offset,
+                stp.table_identity(self.loss_weights))
 
     def _step_graph(self, latents, noise, timesteps, ids, mask, seed, g, nz):
         moments, posterior_noise = self._drawn_from

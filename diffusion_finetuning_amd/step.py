@@ -1,7 +1,9 @@
 """What `trainer.LoraTrainer` and `inversion.InversionTrainer` share of a training step: the DDPM noise prologue, the masked
 loss with its backward pass, and the recording of a step into a hipGraph.  Nothing here knows which trainer is calling."""
+import hashlib
+import math
 import warnings
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -21,23 +23,104 @@ class Noising(NamedTuple):
     v_prediction: bool
     n_timesteps: int  # a device draw takes its timesteps from [0, n_timesteps)
     scale: float = 0.18215  # of latents drawn from VAE moments (train_lora_dreambooth.py:821)
+    noise_offset: float = 0.0  # of a device draw: eps + noise_offset·ξ[b, c] (ddpm_*_prologue_offset)
+    loss_weights: Optional[torch.Tensor] = None  # device fp32 [T]: row b's loss is weighted by loss_weights[t_b]
 
 
 def noise_prologue(nz: Noising, latents, noise, timesteps, seed, step_key, moments=None, posterior_noise=None):
     """(noisy, target, timesteps): from the caller's `noise` and `timesteps`, or — `noise` None — drawn on the device in the
-    same launch, Philox keyed by (seed, step_key), timesteps uniform.  `moments` [B,2C,h,w] instead of `latents`: the latents
-    are drawn from them, `latent_dist.sample() * scale` — in that same launch, or from the caller's `posterior_noise` in a
-    launch of its own in front of add_noise."""
+    same launch, Philox keyed by (seed, step_key), timesteps uniform; with `nz.noise_offset` non-zero that draw is the
+    `_offset` entry's.  `moments` [B,2C,h,w] instead of `latents`: the latents are drawn from them, `latent_dist.sample() *
+    scale` — in that same launch, or from the caller's `posterior_noise` in a launch of its own in front of add_noise."""
     if moments is not None:
         if noise is None:
+            if nz.noise_offset != 0.0:
+                return nat.ddpm_posterior_prologue_offset(moments, nz.sqrt_acp, nz.sqrt_1macp, nz.dtype, seed, step_key,
+                                                          nz.v_prediction, nz.n_timesteps, nz.scale, nz.noise_offset)
             return nat.ddpm_posterior_prologue(moments, nz.sqrt_acp, nz.sqrt_1macp, nz.dtype, seed, step_key, nz.v_prediction,
                                                nz.n_timesteps, nz.scale)
         latents = nat.ddpm_posterior_sample(moments, posterior_noise, nz.scale)
     if noise is None:
+        if nz.noise_offset != 0.0:
+            return nat.ddpm_noise_prologue_offset(latents, nz.sqrt_acp, nz.sqrt_1macp, nz.dtype, seed, step_key,
+                                                  nz.v_prediction, nz.n_timesteps, nz.noise_offset)
         return nat.ddpm_noise_prologue(latents, nz.sqrt_acp, nz.sqrt_1macp, nz.dtype, seed, step_key, nz.v_prediction,
                                        nz.n_timesteps)
     noisy, target = nat.ddpm_add_noise(latents, noise, timesteps, nz.sqrt_acp, nz.sqrt_1macp, nz.dtype, nz.v_prediction)
     return noisy, target, timesteps
+
+
+def min_snr_weights(alphas_cumprod, gamma: float, v_prediction: bool = False) -> torch.Tensor:
+    """The Min-SNR-γ loss weights per timestep (Hang et al. 2023), fp32 [T] on the CPU, computed in float64 from ᾱ_t:
+    SNR = ᾱ/(1 − ᾱ); ε-prediction min(SNR, γ)/SNR — where SNR == 0 (a zero-terminal-SNR schedule) the weight is 1, the limit;
+    v-prediction min(SNR, γ)/(SNR + 1)."""
+    gamma = float(gamma)
+    if not (math.isfinite(gamma) and gamma > 0.0):
+        raise ValueError(f"snr_gamma must be a finite positive number; got {gamma!r}")
+    acp = torch.as_tensor(alphas_cumprod).detach().to("cpu", torch.float64).reshape(-1)
+    if not acp.numel() or bool(((acp < 0.0) | (acp > 1.0) | acp.isnan()).any()):
+        raise ValueError("alphas_cumprod must be a non-empty table of values in [0, 1]")
+    with_signal = acp > 0.0
+    snr = acp / (1.0 - acp)  # (ᾱ == 1: SNR = inf, and γ/inf = 0 in both forms)
+    capped = snr.clamp(max=gamma)
+    if v_prediction:
+        w = capped / (snr + 1.0)
+    else:
+        w = torch.where(with_signal, capped / torch.where(with_signal, snr, torch.ones_like(snr)), torch.ones_like(snr))
+    return w.to(torch.float32)
+
+
+def check_objective(snr_gamma, timestep_weights, noise_offset, n_timesteps: int):
+    """The trainers' rules for their three objective arguments, on the host, before anything is built."""
+    if snr_gamma is not None and timestep_weights is not None:
+        raise ValueError("snr_gamma and timestep_weights are mutually exclusive: the first builds the table the second hands in")
+    if snr_gamma is not None and not (math.isfinite(float(snr_gamma)) and float(snr_gamma) > 0.0):
+        raise ValueError(f"snr_gamma must be a finite positive number; got {snr_gamma!r}")
+    if timestep_weights is not None:
+        w = timestep_weights
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 1:
+            raise ValueError("timestep_weights must be an fp32 [T] tensor")
+        if w.numel() != n_timesteps:
+            raise ValueError(f"timestep_weights has {w.numel()} entries, the schedule has {n_timesteps} timesteps")
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError("timestep_weights must be finite and non-negative")
+    if not math.isfinite(float(noise_offset)):
+        raise ValueError(f"noise_offset must be finite; got {noise_offset!r}")
+
+
+def objective_table(snr_gamma, timestep_weights, alphas_cumprod, v_prediction: bool, device):
+    """The device table of a trainer's loss weights — built once; a recorded step reads it through its address — or None."""
+    if snr_gamma is not None:
+        return min_snr_weights(alphas_cumprod, snr_gamma, v_prediction).to(device)
+    if timestep_weights is not None:
+        return timestep_weights.detach().to(device, copy=True).contiguous()
+    return None
+
+
+def table_digest(timestep_weights):
+    """What a checkpoint's config records of the caller's table: a short digest of its fp32 bytes, None without one."""
+    if timestep_weights is None:
+        return None
+    raw = timestep_weights.detach().to("cpu", torch.float32).contiguous().numpy().tobytes()
+    return hashlib.sha256(raw).hexdigest()[:16]
+
+
+def objective_config(snr_gamma, timestep_weights_digest, noise_offset) -> dict:
+    """The three objective arguments as a trainer's `_config()` records them."""
+    return {"snr_gamma": None if snr_gamma is None else float(snr_gamma), "timestep_weights": timestep_weights_digest,
+            "noise_offset": float(noise_offset)}
+
+
+def table_identity(table):
+    """What a recording bakes in of the loss-weight table: its address and version."""
+    return None if table is None else (table.data_ptr(), table._version)
+
+
+def check_noise_offset(noise_offset: float, noise):
+    """The offset belongs to the device draw: the caller's noise cannot take it."""
+    if noise_offset != 0.0 and noise is not None:
+        raise ValueError("noise_offset applies to noise drawn on the device (pass a seed); with your own `noise`, add the "
+                         "offset to it yourself: noise + noise_offset * randn(B, C, 1, 1)")
 
 
 def latents_like(latents, moments):
@@ -67,12 +150,17 @@ def raw_mask(mask, like):
     return mask.to(like.device).reshape(like.shape[0], 1, like.shape[2] * 8, like.shape[3] * 8).float().contiguous()
 
 
-def loss_backward(pred, target, raw, n_inst, n_prior, prior_weight, grad_scale):
-    """Fused (masked) MSE of the prediction and the backward pass from it, the gradient scaled by `grad_scale`.  Returns the
-    unscaled loss."""
+def loss_backward(pred, target, raw, n_inst, n_prior, prior_weight, grad_scale, timesteps=None, loss_weights=None):
+    """Fused (masked) MSE of the prediction and the backward pass from it, the gradient scaled by `grad_scale`.  With a
+    `loss_weights` table (device fp32 [T]) row b is weighted by loss_weights[timesteps[b]], looked up inside the loss kernel.
+    Returns the unscaled loss."""
     m = nat.lora_mask_prepare(raw, pred.shape[2], pred.shape[3]) if raw is not None else None
     pred_c = pred if pred.is_contiguous() else pred.contiguous()
-    loss, dpred = nat.ddpm_mse_fwd_bwd(pred_c, target, m, n_inst, n_prior, prior_weight, grad_scale)
+    if loss_weights is not None:
+        loss, dpred = nat.ddpm_mse_weighted_fwd_bwd(pred_c, target, m, timesteps, loss_weights, n_inst, n_prior, prior_weight,
+                                                    grad_scale)
+    else:
+        loss, dpred = nat.ddpm_mse_fwd_bwd(pred_c, target, m, n_inst, n_prior, prior_weight, grad_scale)
     pred_c.backward(dpred)
     return loss
 

@@ -29,12 +29,20 @@ from .core import LoraInjectedLinear
 from .formats import load_checkpoint_file, save_checkpoint_file
 
 
-def ddpm_tables(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, device="cpu"):
+NUM_TRAIN_TIMESTEPS = 1000  # T of the training schedule: the tables' length, and that of a trainer's loss-weight table
+
+
+def ddpm_tables(num_train_timesteps=NUM_TRAIN_TIMESTEPS, beta_start=0.00085, beta_end=0.012, device="cpu"):
     """sqrt(ᾱ_t), sqrt(1-ᾱ_t) of the SD "scaled_linear" DDPM schedule (the constants come from the model's hub
     config, which is not part of the reference repo)."""
-    betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
-    acp = torch.cumprod(1.0 - betas, dim=0)
+    acp = ddpm_alphas_cumprod(num_train_timesteps, beta_start, beta_end)
     return acp.sqrt().to(device), (1.0 - acp).sqrt().to(device)
+
+
+def ddpm_alphas_cumprod(num_train_timesteps=NUM_TRAIN_TIMESTEPS, beta_start=0.00085, beta_end=0.012):
+    """ᾱ_t of that schedule, fp32 on the CPU: what `ddpm_tables` takes its roots of and `step.min_snr_weights` its SNR from."""
+    betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+    return torch.cumprod(1.0 - betas, dim=0)
 
 
 SCHEDULER_NAMES = ("linear", "cosine", "cosine_with_restarts", "polynomial", "constant", "constant_with_warmup")
@@ -697,7 +705,8 @@ class LoraTrainer:
                  group_projections=True, lr_embed: float = 5e-4, weight_decay_embed: Optional[float] = None,
                  lr_scheduler: str = "constant", lr_warmup_steps: int = 0, max_train_steps: Optional[int] = None,
                  scheduler_steps_first: bool = False, early_bucket: bool = False, scheduler_steps_per_call: int = 1,
-                 gradient_accumulation_steps: int = 1):
+                 gradient_accumulation_steps: int = 1, snr_gamma: Optional[float] = None,
+                 timestep_weights: Optional[torch.Tensor] = None, noise_offset: float = 0.0):
         """capture_graph: record add_noise → [text encoder] → UNet forward → loss → backward → factor gradients of a step
         once into a hipGraph and replay it on later steps with the same shapes (inputs are copied into static buffers).
         The gradient exchange and the optimizer stay outside the graph, so no collective is ever captured.  A step with a
@@ -735,10 +744,20 @@ class LoraTrainer:
         accumulation; the loss scale moves between windows only.  The schedule advances once per OPTIMIZER step: the script
         multiplies the step counts it hands its scheduler by n (:740-741) — pass `lr_warmup_steps` / `max_train_steps` multiplied
         like that to follow it.  Training the text encoder (LoRA or token table) with n > 1 under data parallelism is refused as
-        the script refuses it (:496-507)."""
+        the script refuses it (:496-507).
+        Objective (extensions beyond the reference, whose loss is the plain mean): `snr_gamma` = γ weights row b's loss by the
+        Min-SNR-γ weight of its timestep (Hang et al. 2023; `step.min_snr_weights`, the v-prediction form under
+        `v_prediction`); `timestep_weights` is the caller's own fp32 [T] table instead (finite, non-negative; the two exclude
+        each other).  The table lives in device memory and is read inside the loss kernel, so it works on every route — also
+        with the caller's `noise` and `timesteps`.  The loss a step returns is the weighted loss.  `noise_offset` adds
+        noise_offset·ξ[b, c], one normal per (row, channel), to the noise of the DEVICE draw (`ddpm_*_prologue_offset`); a step
+        with the caller's own `noise` raises when it is non-zero."""
         self.accum = int(gradient_accumulation_steps)
         if self.accum < 1:
             raise ValueError("gradient_accumulation_steps must be >= 1")
+        stp.check_objective(snr_gamma, timestep_weights, noise_offset, NUM_TRAIN_TIMESTEPS)
+        self.snr_gamma = None if snr_gamma is None else float(snr_gamma)
+        self.noise_offset = float(noise_offset)
         self._micro = 0  # index of the next micro-batch inside its accumulation window
         self.unet, self.text_encoder = unet, text_encoder
         self.early_bucket = bool(early_bucket)
@@ -796,6 +815,8 @@ class LoraTrainer:
         self.slab.enable_packed(self.dtype)
         self.v_prediction = v_prediction
         self.sqrt_acp, self.sqrt_1macp = ddpm_tables(device=self.device)
+        self.loss_weights = stp.objective_table(snr_gamma, timestep_weights, ddpm_alphas_cumprod(), v_prediction, self.device)
+        self._timestep_weights_digest = stp.table_digest(timestep_weights)
         self.pg = process_group
         self.exchange = SlabExchange(self.slab.grads, self.slab.numel, process_group, always_reduce=always_reduce)
         # A recorded step exchanges the slab in one all-reduce.  Once recording was ASKED for, every step of this trainer
@@ -896,7 +917,8 @@ class LoraTrainer:
                                       if m.__class__.__name__ == "FeedForward" and hasattr(m, "net") and len(m.net) == 3]
         ff2 = tuple((m.net[2].weight.data_ptr(), m.net[2].weight._version) for m in ffs if "forward" in m.__dict__)
         return (self.loss_scale, self.accum, self.v_prediction, tuple(float(l.scale) for l in layers),
-                tuple((l.linear.weight.data_ptr(), l.linear.weight._version) for l in layers), ff2)
+                tuple((l.linear.weight.data_ptr(), l.linear.weight._version) for l in layers), ff2,
+                self.noise_offset, stp.table_identity(self.loss_weights))
 
     def _scheduled_lr_factor(self) -> float:
         """λ for the optimizer launch of this step, and the scheduler's own step() before or after it."""
@@ -931,13 +953,15 @@ class LoraTrainer:
         With `gradient_accumulation_steps` = n > 1 this is one micro-batch: the device draw is keyed by (seed, optimizer step · n
         + index of the micro-batch), so the micro-batches of a window draw differently; the loss returned is the micro-batch's
         own, undivided, as the loop logs it."""
-        self._noising = stp.Noising(self.sqrt_acp, self.sqrt_1macp, self.dtype, self.v_prediction,
-                                    max(1, int(self.sqrt_acp.numel() * float(t_multiplier))), float(latent_scale))
         if (encoder_hidden_states is None) == (input_ids is None):
             raise ValueError("pass exactly one of encoder_hidden_states and input_ids")
         if input_ids is not None and self.text_encoder is None:
             raise ValueError("input_ids given but the trainer has no text encoder")
         stp.check_noise_inputs(latents, moments, noise, timesteps, posterior_noise, seed)
+        stp.check_noise_offset(self.noise_offset, noise)
+        self._noising = stp.Noising(self.sqrt_acp, self.sqrt_1macp, self.dtype, self.v_prediction,
+                                    max(1, int(self.sqrt_acp.numel() * float(t_multiplier))), float(latent_scale),
+                                    self.noise_offset, self.loss_weights)
         if self.token_table is not None and input_ids is not None and input_ids.device.type == "cpu":
             self.token_table.check_ids(input_ids)  # (free on the host; a replayed step cannot check device-resident ids)
         if self._micro == 0:  # (one loss scale per accumulation window: its micro-batches are summed)
@@ -967,7 +991,8 @@ class LoraTrainer:
         pred = self.unet(noisy, timesteps, ehs).sample
         rows = pred.shape[0]
         n_inst, n_prior = (rows // 2, rows // 2) if prior else (rows, 0)
-        loss = stp.loss_backward(pred, target, raw_mask, n_inst, n_prior, prior_weight, self.loss_scale / self.accum)
+        loss = stp.loss_backward(pred, target, raw_mask, n_inst, n_prior, prior_weight, self.loss_scale / self.accum,
+                                 timesteps, self.loss_weights)
         self.slab.flush()  # factor gradients of every layer that ran: batched launch + ordered fold into the slab
         return loss
 
@@ -1040,7 +1065,8 @@ class LoraTrainer:
                 "lr_scheduler": name, "lr_warmup_steps": warmup, "max_train_steps": max_steps,
                 "scheduler_steps_first": self.scheduler_steps_first, "scheduler_steps_per_call": self.scheduler_steps_per_call,
                 "v_prediction": bool(self.v_prediction),
-                "compute_dtype": str(self.dtype).replace("torch.", "")}
+                "compute_dtype": str(self.dtype).replace("torch.", ""),
+                **stp.objective_config(self.snr_gamma, self._timestep_weights_digest, self.noise_offset)}
 
     def state_dict(self) -> dict:
         """Everything a continuation needs to leave the bits of the uninterrupted run, as {"meta": scalars and the layout

@@ -308,6 +308,25 @@ int ddpm_mse_fwd_bwd(const void* pred, const void* target, const float* mask /* 
 int64_t lora_mse_workspace_bytes(void);
 
 /*
+ * The same loss with one weight per row, looked up on the device by the row's timestep: w_b = weights[t[b]].
+ *   instance part : (1/n_inst) Σ_b w_b · mean_chw((m·p − m·t)²)
+ *   prior part    : prior_weight · (1/n_prior) Σ_b w_b · mean_chw((m·p − m·t)²)       each row by its own timestep
+ * and dpred follows from them.  The table is the caller's: Min-SNR-γ weighting — T. Hang et al., "Efficient Diffusion
+ * Training via Min-SNR Weighting Strategy", ICCV 2023: min(SNR(t), γ)/SNR(t) for ε-prediction, min(SNR(t), γ)/(SNR(t) + 1)
+ * for v-prediction (`--snr_gamma` of the diffusers and kohya trainers; Python: step.min_snr_weights) — or any other.  An
+ * extension beyond the reference, whose objective is the plain mean; it lives here because the timesteps of a replayed step
+ * exist on the device only.  t int64 [n_inst + n_prior] and weights fp32 [n_weights], both device memory.
+ * The weight is folded into the row's coefficient (coef·w_b, read once per 16-byte chunk); everything else is
+ * ddpm_mse_fwd_bwd's arithmetic, fold, workspace and capturability: with a table of ones loss and dpred are bit-identical to
+ * its.  A t[b] outside [0, n_weights) is never used as an index: that row's weight is NaN (so are the loss and the row's
+ * dpred; the other rows' dpred is unaffected), the convention for token ids outside the embedding table.
+ */
+int ddpm_mse_weighted_fwd_bwd(const void* pred, const void* target, const float* mask /* nullable */, const int64_t* t,
+                              const float* weights, int n_weights, int n_inst, int n_prior, int64_t per_row /* C·H·W */,
+                              int64_t hw /* H·W */, float prior_weight, float grad_scale, float* loss_out,
+                              void* dpred /* nullable */, void* workspace, int dtype, void* stream);
+
+/*
  * Mask preparation of cli_lora_pti.py:222-241:
  *   out = nearest_resize(mask[B,1,Hin,Win] -> [B,1,H,W]) + 0.05 ;  out /= mean(out)
  * mask_in / mask_out fp32.  Single launch, deterministic.
@@ -416,6 +435,30 @@ int ddpm_posterior_prologue(const void* moments, int moments_dtype, const float*
                             int v_prediction, int dtype, void* stream);
 int ddpm_posterior_sample(const void* moments, int moments_dtype, const float* z, float* x0, int B, int64_t per_row,
                           float scale, void* stream);
+
+/*
+ * Offset noise inside the two device-drawn prologues — N. Guttenberg, "Diffusion with Offset Noise" (2023), the
+ * `--noise_offset` of the diffusers and kohya trainers; an extension beyond the reference.  One more normal ξ per
+ * (row, channel) is added to every element of that channel's noise, so the model can learn to move an image's mean:
+ *     eps' = fmaf(noise_offset, ξ[b, c], eps)        C = per_row / hw channels per row
+ * and eps' is the noise everywhere downstream: noisy, target (ε or velocity) and eps_out.
+ * ξ is a fourth Philox stream of the step's key (seed, step): with j = b·C + c, counter (j, j>>32, 3, 0), and
+ * ξ = sqrt(−2·ln u(r0))·cos(2π·u(r1)), the first normal of the Box–Muller mapping of the other streams.  t and — before the
+ * offset is added — eps and z keep their counters and arithmetic: for equal (seed, step) they are bit-identical to the plain
+ * entries'.  With noise_offset == 0 every output is the plain entry's bit for bit.
+ * Arguments: those of the plain entry, then hw (per_row % hw != 0 is LORA_E_BADARG, as is a non-finite noise_offset),
+ * noise_offset and xi_out (nullable, fp32 [B, C]: a copy of ξ).  Access paths, no workspace, capturable: as the plain entries.
+ */
+int ddpm_noise_prologue_offset(const float* x0, const float* sqrt_acp, const float* sqrt_1macp, void* noisy,
+                               void* target /* nullable */, float* eps_out /* nullable */, int64_t* t_out /* nullable */,
+                               int B, int64_t per_row, int n_timesteps, uint64_t seed, uint64_t step, int v_prediction,
+                               int dtype, int64_t hw, float noise_offset, float* xi_out /* nullable */, void* stream);
+int ddpm_posterior_prologue_offset(const void* moments, int moments_dtype, const float* sqrt_acp, const float* sqrt_1macp,
+                                   void* noisy, void* target /* nullable */, float* x0_out /* nullable */,
+                                   float* z_out /* nullable */, float* eps_out /* nullable */, int64_t* t_out /* nullable */,
+                                   int B, int64_t per_row, int n_timesteps, float scale, uint64_t seed, uint64_t step,
+                                   int v_prediction, int dtype, int64_t hw, float noise_offset,
+                                   float* xi_out /* nullable */, void* stream);
 
 /*
  * Latent sampler: the loop AROUND the UNet forward when one samples with the model being trained —
