@@ -139,6 +139,11 @@ SIGNATURES = {
     "conv3x3_small_plan_channels": (_i32, [_i32, _i32, _i32]),
     "conv3x3_small_pack": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "conv3x3_small": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "conv3x3_large_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "conv3x3_large_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "conv3x3_large_plan": (_i32, [_i64, _i32, _i32, _i32]),
+    "conv3x3_large_plan_channels": (_i32, [_i32, _i32, _i32]),
+    "conv3x3_large": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "add_layer_norm_max_channels": (_i32, []),
     "add_layer_norm_fwd": (_i32, [_vp] * 8 + [_i64, _i32, _f32, _i32, _vp]),
     "add_layer_norm_bwd": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _vp]),
@@ -1453,6 +1458,32 @@ def conv3x3_small(x, pack, bias, Cout: int):
     y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
     _check(lib().conv3x3_small(_ptr(x), _ptr(pack), _ptr(bias), _ptr(y), _ptr(ws), nbytes, N, Cin, Cout, H, W, code, _stream(x)),
            "conv3x3_small")
+    return y
+
+
+def conv3x3_large_supported(N: int, Cin: int, Cout: int, H: int, W: int, dtype) -> bool:
+    """Whether csrc/conv_large.hip covers a 3×3 / stride 1 / padding 1 convolution of this shape and dtype (no launch)."""
+    return dtype in (torch.float16, torch.bfloat16) and bool(lib().conv3x3_large_supported(N, Cin, Cout, H, W, dtype_code(dtype)))
+
+
+def conv3x3_large_plan(pixels: int, Cin: int, Cout: int, dtype) -> bool:
+    """Whether the library's planner routes a frozen convolution of this class to csrc/conv_large.hip (no launch)."""
+    return dtype in (torch.float16, torch.bfloat16) and bool(lib().conv3x3_large_plan(int(pixels), Cin, Cout, dtype_code(dtype)))
+
+
+def conv3x3_large_plan_channels(Cin: int, Cout: int, dtype) -> bool:
+    """Whether conv3x3_large_plan routes these channels at some pixel count (no launch)."""
+    return dtype in (torch.float16, torch.bfloat16) and bool(lib().conv3x3_large_plan_channels(Cin, Cout, dtype_code(dtype)))
+
+
+def conv3x3_large(x, pack, bias, Cout: int):
+    """y [N, Cout, H, W] of the 3×3 convolution of the NCHW-contiguous x with a pack of conv3x3_small_pack, on the many-pixel
+    kernel: one launch, no workspace."""
+    _require_device(x, pack, bias)
+    N, Cin, H, W = x.shape
+    y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
+    _check(lib().conv3x3_large(_ptr(x), _ptr(pack), _ptr(bias), _ptr(y), None, 0, N, Cin, Cout, H, W, dtype_code(x.dtype),
+                               _stream(x)), "conv3x3_large")
     return y
 
 

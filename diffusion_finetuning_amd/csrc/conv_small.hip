@@ -1,5 +1,6 @@
 // 3x3, stride 1, padding 1 convolution of NCHW f16 / bf16 tensors with FEW pixels and WIDE filters (the UNet's 8x8 and 16x16
 // levels), as an implicit GEMM on packed frozen weights:  y[n,k,h,w] = sum_{c,r,s} x[n,c,h+r-1,w+s-1] * w[k,c,r,s] (+ b[k]).
+// The 32x32 and 64x64 levels run on conv_large.hip, which reads the same packs.
 //
 // Decomposition.  GEMM M = N*H*W pixels, N = C_out, K = 9*C_in.  A workgroup (256 threads, 2 x 2 waves) owns MT consecutive
 // pixels (128, or 64 where 128 pixels with their halo exceed 256 padded positions), 128 output channels and one K-slice: a run of 32-channel
@@ -23,49 +24,11 @@
 //
 // Workgroups that share weights (the pixel tiles of one channel tile and slice) get consecutive places in the XCD remap below,
 // so they run on one XCD and the weights come from HBM once.
-#include "common.h"
+#include "conv_common.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kNT = 128;        // output channels per workgroup (2 waves x 4 tiles of 16)
-constexpr int kChunk = 32;      // input channels per staged chunk = one MFMA K-step
-constexpr int kPitch = 80;      // bytes per LDS position: 32 channels + 16 bytes (16 consecutive positions hit 16 distinct slots)
-constexpr int kCUs = 256;
-
-template <typename T> struct Mfma;
-template <> struct Mfma<half_t> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x4 run(Frag a, Frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mfma<bf16_t> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x4 run(Frag a, Frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
-
-// padded-coordinate position of pixel m (both host and device)
-__host__ __device__ __forceinline__ int padded_pos(int m, int H, int W) {
-    const int HW = H * W, img = m / HW, r = m - img * HW, h = r / W, w = r - h * W;
-    return img * (H + 2) * (W + 2) + (h + 1) * (W + 2) + (w + 1);
-}
-// positions a tile of pixels [m0, m0 + MT) ∩ [0, M) stages: from its first pixel's tap (0,0) to its last pixel's tap (2,2)
-__host__ __device__ __forceinline__ int tile_positions(int m0, int MT, int M, int H, int W) {
-    const int mlast = (m0 + MT < M ? m0 + MT : M) - 1;
-    return padded_pos(mlast, H, W) - padded_pos(m0, H, W) + 2 * (W + 3) + 1;
-}
-
-// n / d for 0 <= n < 2^22 (conv_geo bounds the padded positions) through the float reciprocal, corrected by one either way
-__device__ __forceinline__ int fast_div(int n, int d, float inv) {
-    int q = (int)((float)n * inv);
-    int r = n - q * d;
-    q += r >= d ? 1 : 0;
-    q -= r < 0 ? 1 : 0;
-    return q;
-}
 
 // MT pixels per workgroup; PER positions (all 32 channels of each) a thread stages per chunk: 256*PER >= positions of a tile.
 template <typename T, int MT, int PER>
@@ -266,11 +229,8 @@ struct Geo {
 // Tiling of one call: a function of the shape alone.
 Geo conv_geo(int N, int Cin, int Cout, int H, int W) {
     Geo g;
-    if (N < 1 || H < 1 || W < 1 || Cin < 32 || Cout < 32 || Cin % 32 || Cout % 32) return g;
-    const int64_t M64 = (int64_t)N * H * W;
-    if (M64 > (1 << 22) || M64 * Cin >= (1ll << 31) || M64 * Cout >= (1ll << 31) || (int64_t)(H + 2) * (W + 2) * N >= (1ll << 22))
-        return g;
-    const int M = (int)M64;
+    if (!conv_shape_in_range(N, Cin, Cout, H, W)) return g;
+    const int M = N * H * W;
     const int mts[2] = {128, 64}, per[2] = {1, 3};  // the instantiations of run_conv
     for (int v = 0; v < 2 && !g.ok; ++v) {
         const int MT = mts[v], mtiles = (M + MT - 1) / MT;

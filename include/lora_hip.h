@@ -741,6 +741,21 @@ int conv3x3_small(const void* x, const void* wpack, const void* bias /* nullable
                   int64_t workspace_bytes, int N, int C_in, int C_out, int H, int W, int dtype, void* stream);
 
 /*
+ * The same convolution, same contract and same packs (conv3x3_small_pack), where the pixels are MANY (csrc/conv_large.hip, the
+ * 32x32 and 64x64 levels): one launch, each workgroup owns its outputs over the whole K range and writes NCHW itself, so there
+ * are no fp32 partials and no workspace: conv3x3_large_workspace_bytes is 0 and a null workspace is accepted (a non-null one
+ * must still be 16-byte aligned).  conv3x3_large_supported: C_in, C_out multiples of 32, fewer than 2^31 elements per tensor,
+ * 64 pixels with their halo in 384 padded positions (W up to about 160).  conv3x3_large_plan / _plan_channels: as the small
+ * family's, set from profiles/r15_conv_large_sweep.log (tools/conv_large_sweep.py).  Statuses and their order as conv3x3_small.
+ */
+int conv3x3_large_supported(int N, int C_in, int C_out, int H, int W, int dtype);
+int64_t conv3x3_large_workspace_bytes(int N, int C_in, int C_out, int H, int W, int dtype);
+int conv3x3_large_plan(int64_t pixels, int C_in, int C_out, int dtype);
+int conv3x3_large_plan_channels(int C_in, int C_out, int dtype);
+int conv3x3_large(const void* x, const void* wpack, const void* bias /* nullable */, void* y, void* workspace /* nullable */,
+                  int64_t workspace_bytes, int N, int C_in, int C_out, int H, int W, int dtype, void* stream);
+
+/*
  * LayerNorm of the transformer blocks with the residual add in front of it folded in (csrc/layer_norm.hip), over rows [M, C]
  * with the last dimension contiguous; the caller's `attn(norm(x)) + x` chain, one launch each way:
  *     forward : h = x + delta, rounded to the storage type (bit-equal to the stock sum);  y = (h − mean)·rstd·gamma + beta,
