@@ -133,6 +133,8 @@ SIGNATURES = {
     "tokens_nchw_supported": (_i32, [_i32, _i32, _i32, _i32]),
     "tokens_to_nchw_add": (_i32, [_vp] * 3 + [_i32, _i32, _i32, _i32, _vp]),
     "nchw_to_tokens": (_i32, [_vp] * 2 + [_i32, _i32, _i32, _i32, _vp]),
+    "time_proj_supported": (_i32, [_i32, _i32, _i32]),
+    "time_proj_all": (_i32, [_vp] * 6 + [_i32, _i32, _i32, _i32, _vp]),
     "conv3x3_small_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "conv3x3_small_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "conv3x3_small_plan": (_i32, [_i64, _i32, _i32, _i32]),
@@ -1421,6 +1423,29 @@ def residual_bias_add(h, res, b1, b2):
     _check(lib().residual_bias_add(_ptr(h), _ptr(res), _ptr(b1), _ptr(b2), _ptr(out), N, C, H * W, dtype_code(h.dtype),
                                    _stream(h)), "residual_bias_add")
     return out
+
+
+def time_proj_supported(N: int, E: int, dtype) -> bool:
+    """Whether csrc/time_proj.hip takes a [N, E] time embedding of this dtype (no launch)."""
+    return dtype in (torch.float16, torch.bfloat16) and bool(lib().time_proj_supported(N, E, dtype_code(dtype)))
+
+
+def time_proj_all(temb, weights, biases, extra_biases):
+    """silu(temb) @ W_l.T + b_l + cb_l for every layer in one launch per 32 layers: temb [N, E], W_l [C_l, E], b_l / cb_l [C_l] or
+    None, all dense and of temb's 16-bit dtype.  Returns the [N, C_l] results, views of one allocation."""
+    _require_device(temb, *weights)
+    N, E = temb.shape
+    L = len(weights)
+    widths = [w.shape[0] for w in weights]
+    out = torch.empty(N * sum(widths), dtype=temb.dtype, device=temb.device)
+    ptrs = lambda ts: (_vp * L)(*[None if t is None else t.data_ptr() for t in ts])
+    _check(lib().time_proj_all(_ptr(temb), ptrs(weights), ptrs(biases), ptrs(extra_biases), (_i32 * L)(*widths), _ptr(out), L, N, E,
+                               dtype_code(temb.dtype), _stream(temb)), "time_proj_all")
+    outs, off = [], 0
+    for c in widths:
+        outs.append(out[off:off + N * c].view(N, c))
+        off += N * c
+    return outs
 
 
 def conv3x3_small_supported(N: int, Cin: int, Cout: int, H: int, W: int, dtype) -> bool:

@@ -14,7 +14,10 @@ of conv2 and conv_shortcut and the residual sum) is one pass, a transformer's NC
 with the exit residual added on the way, and the gradient of a block input that two branches read is joined inside the
 GroupNorm backward.  The frozen 3×3 stride-1 convolutions of the ResNets and the upsamplers go through
 diffusion_finetuning_amd.conv.conv3x3 (`_conv3x3` below), which runs the few-pixel, wide-filter classes (the 8×8 and 16×16 levels
-at batch 4) on packed weights in HIP and hands everything else to F.conv2d.  All of it sits behind `_fused_norms`.
+at batch 4) on packed weights in HIP and hands everything else to F.conv2d.  The ResNets' time-embedding branch
+(`time_emb_proj(silu(temb)) + conv1.bias`, which reads nothing from the trunk) is computed for all blocks at the top of the model's
+forward by diffusion_finetuning_amd.time_proj.time_projections, one launch, and handed to each block as its `addend`.
+All of it sits behind `_fused_norms`.
 Weights are random-init: there are no SD checkpoints offline.
 """
 import math
@@ -138,6 +141,13 @@ def _residual_bias_add(h, res, b1, b2=None):
     return residual_bias_add(h, res, b1, b2)
 
 
+def _time_projections(temb, layers):
+    """[time_emb_proj(silu(temb)) + conv1.bias per (weight, bias, conv1 bias)]: one launch for all of them (csrc/time_proj.hip)."""
+    from diffusion_finetuning_amd.time_proj import time_projections
+
+    return time_projections(temb, layers)
+
+
 def _layer_norm(norm: nn.LayerNorm, x):
     from diffusion_finetuning_amd import norm as dnorm
 
@@ -161,23 +171,34 @@ class ResnetBlock2D(nn.Module):
         self.conv2 = nn.Conv2d(cout, cout, 3, padding=1)
         self.conv_shortcut = nn.Conv2d(cin, cout, 1) if cin != cout else None
 
-    def forward(self, x, temb):
+    def time_addend_layer(self):
+        """(weight, bias, extra bias) of the addend `time_emb_proj(silu(temb)) + conv1.bias` for a batched projection, or None
+        where one of the two modules is not the stock one."""
+        if type(self.conv1) is nn.Conv2d and type(self.time_emb_proj) is nn.Linear:
+            return self.time_emb_proj.weight, self.time_emb_proj.bias, self.conv1.bias
+        return None
+
+    def forward(self, x, temb, addend=None):
+        """`addend`: this block's `time_emb_proj(silu(temb)) + conv1.bias` [N, C] where the model has computed it for all its blocks
+        at once; None = computed here."""
         if _fused_norms(x) and type(self.conv1) is nn.Conv2d:
             # conv1's bias and the time embedding are per-(n,c) constants over the image: both ride into norm2 as its addend
             # instead of one bias pass and one broadcast-add pass over the activation
+            if addend is None:
+                addend = self.time_emb_proj(F.silu(temb)) + self.conv1.bias
             if type(self.conv2) is nn.Conv2d and (self.conv_shortcut is None or type(self.conv_shortcut) is nn.Conv2d):
                 # the shortcut reads the x that norm1 hands through, so its gradient joins norm1's dx; conv2 and conv_shortcut
                 # run without their biases, which go into the one pass that sums the two branches
                 xp, n = _norm_act_res(self.norm1, x, True)
                 h = _conv3x3(n, self.conv1.weight)
-                n = _norm_act(self.norm2, h, True, self.time_emb_proj(F.silu(temb)) + self.conv1.bias)
+                n = _norm_act(self.norm2, h, True, addend)
                 h = _conv3x3(n, self.conv2.weight)
                 if self.conv_shortcut is None:
                     return _residual_bias_add(h, xp, self.conv2.bias)
                 return _residual_bias_add(h, F.conv2d(xp, self.conv_shortcut.weight, None), self.conv2.bias,
                                           self.conv_shortcut.bias)
             h = F.conv2d(_norm_act(self.norm1, x, True), self.conv1.weight, None, padding=1)
-            h = self.conv2(_norm_act(self.norm2, h, True, self.time_emb_proj(F.silu(temb)) + self.conv1.bias))
+            h = self.conv2(_norm_act(self.norm2, h, True, addend))
             return (x if self.conv_shortcut is None else self.conv_shortcut(x)) + h
         h = self.conv1(F.silu(self.norm1(x)))
         h = h + self.time_emb_proj(F.silu(temb))[:, :, None, None]
@@ -360,10 +381,10 @@ class DownBlock(nn.Module):
         self.resnets = nn.ModuleList([ResnetBlock2D(cin if i == 0 else cout, cout, temb, groups) for i in range(layers)])
         self.downsamplers = nn.ModuleList([Downsample2D(cout)]) if add_down else None
 
-    def forward(self, x, temb, context):
+    def forward(self, x, temb, context, addends=None):
         outs = []
         for i, res in enumerate(self.resnets):
-            x = res(x, temb)
+            x = res(x, temb, None if addends is None else addends[i])
             if len(self.attentions):
                 x = self.attentions[i](x, context)
             outs.append(x)
@@ -379,10 +400,10 @@ class MidBlock(nn.Module):
         self.attentions = nn.ModuleList([Transformer2DModel(c, heads, ctx, groups, linear_proj)])
         self.resnets = nn.ModuleList([ResnetBlock2D(c, c, temb, groups), ResnetBlock2D(c, c, temb, groups)])
 
-    def forward(self, x, temb, context):
-        x = self.resnets[0](x, temb)
+    def forward(self, x, temb, context, addends=None):
+        x = self.resnets[0](x, temb, None if addends is None else addends[0])
         x = self.attentions[0](x, context)
-        return self.resnets[1](x, temb)
+        return self.resnets[1](x, temb, None if addends is None else addends[1])
 
 
 class UpBlock(nn.Module):
@@ -399,9 +420,9 @@ class UpBlock(nn.Module):
         self.resnets = nn.ModuleList(resnets)
         self.upsamplers = nn.ModuleList([Upsample2D(cout)]) if add_up else None
 
-    def forward(self, x, skips, temb, context):
+    def forward(self, x, skips, temb, context, addends=None):
         for i, res in enumerate(self.resnets):
-            x = res(torch.cat([x, skips.pop()], dim=1), temb)
+            x = res(torch.cat([x, skips.pop()], dim=1), temb, None if addends is None else addends[i])
             if len(self.attentions):
                 x = self.attentions[i](x, context)
         if self.upsamplers is not None:
@@ -450,20 +471,35 @@ class UNet2DConditionModel(nn.Module):
         self.conv_norm_out = nn.GroupNorm(g, ch[0], eps=1e-5)
         self.conv_out = nn.Conv2d(ch[0], cfg.out_channels, 3, padding=1)
 
+    @staticmethod
+    def _time_addends(temb, blocks):
+        """{block: [addend of each of its ResNets | None]}: the time-embedding branch of every ResNet, which depends on nothing in
+        the trunk, in one call of the batched front; a ResNet whose projection is not the stock module computes its own."""
+        resnets = [(blk, i, res.time_addend_layer()) for blk in blocks for i, res in enumerate(blk.resnets)]
+        layers = [layer for _, _, layer in resnets if layer is not None]
+        outs = iter(_time_projections(temb, layers)) if layers else iter(())
+        addends = {blk: [None] * len(blk.resnets) for blk in blocks}
+        for blk, i, layer in resnets:
+            if layer is not None:
+                addends[blk][i] = next(outs)
+        return addends
+
     def forward(self, sample, timesteps, encoder_hidden_states):
         if not torch.is_tensor(timesteps):
             timesteps = torch.tensor([timesteps], device=sample.device)
         timesteps = timesteps.reshape(-1).expand(sample.shape[0])
         temb = self.time_embedding(self.time_proj(timesteps).to(sample.dtype))
         ctx = encoder_hidden_states.to(sample.dtype)
+        blocks = [*self.down_blocks, self.mid_block, *self.up_blocks]  # forward order
+        addends = self._time_addends(temb, blocks) if _fused_norms(sample) else {}
         x = self.conv_in(sample)
         skips: List[torch.Tensor] = [x]
         for blk in self.down_blocks:
-            x, outs = blk(x, temb, ctx)
+            x, outs = blk(x, temb, ctx, addends.get(blk))
             skips += outs
-        x = self.mid_block(x, temb, ctx)
+        x = self.mid_block(x, temb, ctx, addends.get(self.mid_block))
         for blk in self.up_blocks:
-            x = blk(x, skips, temb, ctx)
+            x = blk(x, skips, temb, ctx, addends.get(blk))
         x = _norm_act(self.conv_norm_out, x, True) if _fused_norms(x) else F.silu(self.conv_norm_out(x))
         x = self.conv_out(x)
         return UNetOutput(sample=x)

@@ -711,6 +711,22 @@ int tokens_to_nchw_add(const void* tok, const void* res /* nullable */, void* ou
 int nchw_to_tokens(const void* x, void* tok, int N, int C, int HW, int dtype, void* stream);
 
 /*
+ * The time-embedding projections of L layers in one launch per 32 layers (time_proj.hip):
+ *     out_l[n,c] = sum_e W_l[c,e] * silu(t[n,e]) + b_l[c] + cb_l[c],   t [N,E], W_l [C_l,E] row-major, b_l / cb_l [C_l],
+ * f16 / bf16 throughout, silu and all sums in fp32 with one rounding at the store, fixed summation order (bit-reproducible).
+ * W, b, cb are host arrays of L device pointers and C a host array of L widths, read during the call; b and cb may be null
+ * (no layer has that bias) and so may any of their entries.  out is one buffer of N * sum(C_l) elements: layer l is a dense
+ * [N, C_l] block at element offset N * sum_{j<l} C_j.  1 <= N <= 16, E % 8 == 0, any C_l >= 1 (at most 2^31 - 17 rows per 32
+ * layers).  Nothing is allocated, uploaded or retained: the descriptors travel in the kernel arguments (capturable).
+ * time_proj_supported answers 1 / 0 for (N, E, dtype) without touching a device.  Statuses, decided before any launch, in
+ * this order: LORA_E_BADARG (t, W, C, out or a W[l] null, L, N, E or a C[l] < 1, unknown dtype), LORA_E_UNSUPPORTED (f32,
+ * N > 16, E % 8 != 0), LORA_E_ALIGN (t or a W[l] off a 16-byte boundary).
+ */
+int time_proj_supported(int N, int E, int dtype);
+int time_proj_all(const void* t, const void* const* W, const void* const* b /* nullable */, const void* const* cb /* nullable */,
+                  const int* C, void* out, int L, int N, int E, int dtype, void* stream);
+
+/*
  * 3x3, stride 1, padding 1 convolution with FROZEN weights where the pixels are few and the filters wide (csrc/conv_small.hip):
  *     y[n,k,h,w] = sum_{c,r,s} x[n,c,h+r-1,w+s-1] * w[k,c,r,s] (+ bias[k]),   x [N,C_in,H,W], y [N,C_out,H,W] NCHW-contiguous,
  * f16 / bf16, fp32 accumulation, one rounding at the store.  C_in and C_out multiples of 32; any N, H, W >= 1 whose tiles fit
