@@ -28,6 +28,14 @@ template <> struct ElemTraits<bf16_t> {
 
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return static_cast<float>(v); }
 template <typename T> __device__ __forceinline__ T from_f32(float v) { return static_cast<T>(v); }
+// x as an fp32 value that has been rounded: where a kernel restates torch op by op, this keeps hipcc from folding the
+// operation that made x into the one that uses it — a product into an fma (fp contraction), or a product and its cast to
+// half into one mixed-precision instruction that rounds the exact product once, where torch rounds it to fp32 first (half
+// tensors scaled by 0.3 or 0.7 came out one ulp off in 2 % of their elements).  No instruction is emitted.
+__device__ __forceinline__ float rounded_f32(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
 
 // 16-byte chunk of VEC elements, usable as a register-resident vector.
 template <typename T> struct alignas(16) Chunk {

@@ -183,8 +183,8 @@ __global__ __launch_bounds__(256) void merge_kernel(T* W, const float* A, const 
         for (int j = 0; j < r; ++j) d = fmaf(B[(int64_t)n * r + j], A[(int64_t)j * K + k], d);
         if (factor_dtype == LORA_F16) d = to_f32<half_t>(from_f32<half_t>(d));
         if (factor_dtype == LORA_BF16) d = to_f32<bf16_t>(from_f32<bf16_t>(d));
-        const T dt = from_f32<T>(d);
-        const T upd = from_f32<T>(alpha * to_f32<T>(dt));
+        const T dt = from_f32<T>(rounded_f32(d));
+        const T upd = from_f32<T>(rounded_f32(alpha * to_f32<T>(dt)));  // (a product of its own: no fma with the add below)
         W[i] = from_f32<T>(to_f32<T>(W[i]) + to_f32<T>(upd));
     }
 }
@@ -201,8 +201,8 @@ __device__ __forceinline__ void merge_rows(T* W, const float* A, const float* B,
         for (int j = 0; j < r; ++j) d = fmaf(B[(int64_t)n * r + j], A[(int64_t)j * K + k], d);
         if (factor_dtype == LORA_F16) d = to_f32<half_t>(from_f32<half_t>(d));
         if (factor_dtype == LORA_BF16) d = to_f32<bf16_t>(from_f32<bf16_t>(d));
-        const T dt = from_f32<T>(d);
-        const T upd = from_f32<T>(alpha * to_f32<T>(dt));
+        const T dt = from_f32<T>(rounded_f32(d));
+        const T upd = from_f32<T>(rounded_f32(alpha * to_f32<T>(dt)));  // (a product of its own: no fma with the add below)
         W[i] = from_f32<T>(to_f32<T>(W[i]) + to_f32<T>(upd));
     }
 }
@@ -225,10 +225,11 @@ __global__ __launch_bounds__(256) void merge_batched_kernel(const int64_t* table
 template <typename T>
 __global__ __launch_bounds__(256) void lerp_kernel(T* x1, const T* x2, int64_t n, float a, float b) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        // separately rounded products and sum, as three torch ops give them (no fma contraction for fp32 tensors)
-        const T p = from_f32<T>(__fmul_rn(a, to_f32<T>(x1[i])));
-        const T q = from_f32<T>(__fmul_rn(b, to_f32<T>(x2[i])));
-        x1[i] = from_f32<T>(__fadd_rn(to_f32<T>(p), to_f32<T>(q)));
+        // separately rounded products and sum, as three torch ops give them: each product is rounded to fp32 before its
+        // cast to T and before the add (the sum of two T values needs no such care: fp32 holds it to within T's rounding)
+        const T p = from_f32<T>(rounded_f32(a * to_f32<T>(x1[i])));
+        const T q = from_f32<T>(rounded_f32(b * to_f32<T>(x2[i])));
+        x1[i] = from_f32<T>(to_f32<T>(p) + to_f32<T>(q));
     }
 }
 
@@ -328,6 +329,7 @@ extern "C" int lora_adamw_rows(float* param, const float* grad, float* exp_avg, 
                                void* stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || !active || V < 1 || D < 1 || step < 0) return LORA_E_BADARG;
     if (step == 0 && !norm_in) return LORA_E_BADARG;
+    if ((D & 3) == 0 && !aligned16(param)) return LORA_E_ALIGN;  // the untouched rows' float4 path (row starts keep param's alignment)
     AdamParams a{};
     a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.n = V * D; a.norm_in = norm_in;
     a.grad_mul = grad_mul; a.max_norm = max_norm; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2;

@@ -809,6 +809,9 @@ int embed_rows_bwd(const void* dE, const int64_t* ids, float* grad_table, unsign
 /* torch.optim.AdamW (`lora_adamw_step`'s arithmetic, same norm / skip / step-count inputs) over a [V, D] table of which only the
  * rows flagged in `active` (set by embed_rows_bwd, never cleared) have ever had a gradient: those get the full update, every
  * other row p ← p·(1 − lr·wd) — bit-identical to the dense update (g = m = v = 0 there), at a third of its traffic.
+ * Status, decided before any launch: LORA_E_BADARG (null pointer, `norm_in` excepted when step >= 1; V < 1, D < 1, step < 0,
+ * step == 0 with a null norm_in), then LORA_E_ALIGN when D % 4 == 0 and `param` is not 16-byte aligned (untouched rows of
+ * whole 16-byte chunks are read and written as float4; a table with D % 4 != 0 needs 4-byte alignment only).
  * Reference: the token table as an AdamW group, cli_lora_pti.py:706-738, stepped at :451. */
 int lora_adamw_rows(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const unsigned char* active, int64_t V,
                     int D, const float* norm_in, float grad_mul, float max_norm, float lr, float beta1, float beta2, float eps,

@@ -346,9 +346,9 @@ def test_merge_of_a_cpu_resident_model_like_lora_add_upl(golden_merge):
 def test_lerp_lora_lists_is_lora_add_lpl():
     """`lerp_lora_lists` = the LoRA ⊕ LoRA interpolation of cli_lora_add.py:44-60, op-by-op in the tensors' dtype
     (fp16 lists as `save_lora_weight` writes them).  fp32: bit-identical to the reference's torch expression on the CPU.
-    fp16: within one ulp OF THE LARGEST TERM — torch's own CPU half arithmetic is not the same on every host (the build
-    container's CPU agrees bit for bit with float-product-then-round, the GPU box's differs from it in 2 % of the elements
-    by one rounding of a product, which is more than an ulp of the SUM where the two terms cancel)."""
+    fp16: within one ulp OF THE LARGEST TERM against torch's own CPU half arithmetic, which is not the same on every host
+    (one rounding of a product apart is more than an ulp of the SUM where the two terms cancel).  The kernel itself is
+    float-product-then-round bit for bit on any host: tests/test_gpu_optim_edges.py::test_lerp_is_the_emulation_bit_for_bit."""
     g = torch.Generator().manual_seed(12)
     shapes = [(320, 4), (4, 320), (640, 4), (4, 768), (1280, 1), (1, 1280)]
     for dtype in (torch.float16, torch.float32):
