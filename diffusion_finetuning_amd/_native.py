@@ -85,6 +85,9 @@ SIGNATURES = {
     "lora_grad_sqnorm": (_i32, [_vp, _i64, _f32, _vp, _vp, _vp]),
     "lora_sqnorm_workspace_bytes": (_i64, []),
     "lora_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
+    "lora_adamw_ema_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _i32,
+                                   _vp]),
+    "lora_slab_swap": (_i32, [_vp, _vp, _i64, _vp]),
     "ddpm_add_noise": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp]),
     "ddpm_noise_prologue": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, ctypes.c_uint64, ctypes.c_uint64,
                                    _i32, _i32, _vp]),
@@ -710,6 +713,29 @@ def lora_adamw_step(param, grad, exp_avg, exp_avg_sq, norm_in, grad_mul, max_nor
                                  _ptr(norm_in), float(grad_mul), float(max_norm), float(lr), float(beta1),
                                  float(beta2), float(eps), float(weight_decay), int(step), _stream(param)),
            "lora_adamw_step")
+
+
+def lora_adamw_ema_step(param, grad, exp_avg, exp_avg_sq, shadow, norm_in, grad_mul, max_norm, lr, beta1, beta2, eps,
+                        weight_decay, step: int, ema_max_decay: float, ema_update_after: int) -> None:
+    """`lora_adamw_step` plus, in the same launch, the EMA of the parameters in `shadow` (fp32, like param); the decay follows
+    the device's applied-step counter norm_in[2], so `norm_in` is required (include/lora_hip.h)."""
+    _require_device(param, grad, exp_avg, exp_avg_sq, shadow, norm_in)
+    if shadow.dtype != torch.float32 or shadow.numel() != param.numel() or not shadow.is_contiguous():
+        raise ValueError("lora_adamw_ema_step: the shadow must be a contiguous fp32 tensor with the parameters' element count")
+    _check(lib().lora_adamw_ema_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(shadow), param.numel(),
+                                     _ptr(norm_in), float(grad_mul), float(max_norm), float(lr), float(beta1), float(beta2),
+                                     float(eps), float(weight_decay), int(step), float(ema_max_decay), int(ema_update_after),
+                                     _stream(param)), "lora_adamw_ema_step")
+
+
+def lora_slab_swap(a, b) -> None:
+    """Exchanges two flat fp32 device tensors of equal length in place (one launch).  The same buffer twice, or two ranges
+    that overlap, raise without a launch."""
+    _require_device(a, b)
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.numel() != b.numel() or not (a.is_contiguous()
+                                                                                              and b.is_contiguous()):
+        raise ValueError("lora_slab_swap: two contiguous fp32 tensors of equal length")
+    _check(lib().lora_slab_swap(_ptr(a), _ptr(b), a.numel(), _stream(a)), "lora_slab_swap")
 
 
 def ddpm_add_noise(x0, eps, t, sqrt_acp, sqrt_1macp, out_dtype: torch.dtype, v_prediction: bool, want_target=True):

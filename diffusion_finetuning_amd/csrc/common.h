@@ -97,6 +97,13 @@ __device__ __forceinline__ void adamw_element(float& p, float& m, float& v, floa
     p = p - step_size * (m / denom);
 }
 
+// Exponential moving average of a parameter on one element, diffusers' EMAModel.step op by op in fp32:
+//   s ← s − omd·(s − p),  omd = (float)(1 − decay).  The product stays a rounded fp32 value (rounded_f32): contracted into an
+// fma with the subtraction it would round once where torch rounds twice.  The one copy of this arithmetic (optim.hip).
+__device__ __forceinline__ void ema_element(float& s, float p, float omd) {
+    s = s - rounded_f32(omd * (s - p));
+}
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // Zeroes the 16-byte ticket header of a reduction workspace with a KERNEL, not hipMemsetAsync: inside a captured

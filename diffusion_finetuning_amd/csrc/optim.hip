@@ -120,6 +120,56 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamParams a) {
     }
 }
 
+// adamw_kernel with an exponential moving average of the parameters updated in the same pass (`shadow`, ema_element on the p
+// just computed): the parameters are in registers here, anywhere else the average costs another pass over the slab and another
+// launch.  A skipped step writes nothing, the shadow included.  The decay comes from the device's count of applied steps
+// t = norm_in[2] (this step included), diffusers' EMAModel.get_decay without warm-up (step.ema_decay_at is the host's copy):
+//   n = max(0, t − update_after − 1) ;  d = 0 if n <= 0 else min(max_decay, (1 + n)/(10 + n)) ;  omd = (float)(1 − d)
+// Scalar 4-byte accesses and adamw_kernel's stride: any n, any 4-byte-aligned view.
+__global__ __launch_bounds__(256) void adamw_ema_kernel(AdamParams a, float* shadow, float ema_max_decay, int ema_update_after) {
+    if (a.norm_in[1] != 0.f) return;  // overflow: skip the step (GradScaler semantics) and leave the average alone
+    float clip = 1.f;
+    if (a.max_norm > 0.f) {
+        const float c = a.max_norm / (sqrtf(a.norm_in[0]) + 1e-6f);
+        clip = c < 1.f ? c : 1.f;
+    }
+    const double t = (double)a.norm_in[2];
+    float bc1 = a.bc1, bc2_sqrt = a.bc2_sqrt;
+    if (bc1 <= 0.f) {
+        bc1 = (float)(1.0 - pow((double)a.beta1, t));
+        bc2_sqrt = (float)sqrt(1.0 - pow((double)a.beta2, t));
+    }
+    const double n_ema = t - (double)ema_update_after - 1.0;
+    double d = 0.0;
+    if (n_ema > 0.0) {
+        d = (1.0 + n_ema) / (10.0 + n_ema);
+        if (d > (double)ema_max_decay) d = (double)ema_max_decay;
+    }
+    const float omd = (float)(1.0 - d);
+    const float gm = a.grad_mul * clip;
+    const float step_size = a.lr / bc1;
+    const float decay = 1.f - a.lr * a.wd;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
+        const float g = a.g[i] * gm;
+        float p = a.p[i], m = a.m[i], v = a.v[i], s = shadow[i];
+        adamw_element(p, m, v, g, decay, step_size, a.beta1, a.beta2, bc2_sqrt, a.eps);
+        ema_element(s, p, omd);
+        a.p[i] = p;
+        a.m[i] = m;
+        a.v[i] = v;
+        shadow[i] = s;
+    }
+}
+
+// a ↔ b over n fp32 elements (disjoint ranges, any 4-byte alignment): every element is read and written by one thread only.
+__global__ __launch_bounds__(256) void slab_swap_kernel(float* a, float* b, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
+    }
+}
+
 // The same update for a ROW-structured parameter of which only a few rows ever receive a gradient — the token-embedding table of
 // cli_lora_pti.py's continue_inversion (:706-722; 49408 × 1024, a caption touches a few dozen rows).  torch's dense AdamW still
 // visits every element each step: decoupled weight decay on all rows, moment decay on the rows that were touched before.  For a
@@ -319,6 +369,37 @@ extern "C" int lora_adamw_step(float* param, const float* grad, float* exp_avg, 
     int64_t blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+extern "C" int lora_adamw_ema_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* shadow,
+                                   int64_t n, const float* norm_in, float grad_mul, float max_norm, float lr, float beta1,
+                                   float beta2, float eps, float weight_decay, int step, float ema_max_decay,
+                                   int ema_update_after, void* stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !shadow || !norm_in || n < 1 || step < 0) return LORA_E_BADARG;
+    if (!(ema_max_decay >= 0.f && ema_max_decay <= 1.f) || ema_update_after < 0) return LORA_E_BADARG;
+    AdamParams a{};
+    a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.n = n; a.norm_in = norm_in;
+    a.grad_mul = grad_mul; a.max_norm = max_norm; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2;
+    a.eps = eps; a.wd = weight_decay;
+    a.bc1 = step > 0 ? (float)(1.0 - pow((double)beta1, (double)step)) : 0.f;
+    a.bc2_sqrt = step > 0 ? (float)sqrt(1.0 - pow((double)beta2, (double)step)) : 0.f;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(adamw_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a, shadow,
+                       ema_max_decay, ema_update_after);
+    LORA_LAUNCH_CHECK();
+    return LORA_OK;
+}
+
+extern "C" int lora_slab_swap(float* a, float* b, int64_t n, void* stream) {
+    if (!a || !b || n < 1) return LORA_E_BADARG;
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * 4;
+    if (pa < pb + bytes && pb < pa + bytes) return LORA_E_BADARG;  // a == b or overlapping ranges: no launch
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(slab_swap_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a, b, n);
     LORA_LAUNCH_CHECK();
     return LORA_OK;
 }

@@ -165,6 +165,38 @@ def loss_backward(pred, target, raw, n_inst, n_prior, prior_weight, grad_scale, 
     return loss
 
 
+# -- EMA of the trained weights: the host's one statement of the decay `lora_adamw_ema_step` computes on the device -----------
+def _f32(x: float) -> float:
+    """The double that equals x rounded to fp32: what a float argument of the C ABI holds."""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def check_ema(ema_decay, ema_update_after_step):
+    """`LoraTrainer`'s rules for its two EMA arguments, on the host, before anything is built."""
+    if ema_decay is not None and not (0.0 < float(ema_decay) < 1.0 and 0.0 < _f32(ema_decay) < 1.0):
+        raise ValueError(f"ema_decay must lie strictly between 0 and 1 (None: no EMA); got {ema_decay!r}")
+    after = ema_update_after_step
+    if not isinstance(after, int) or isinstance(after, bool) or after < 0:
+        raise ValueError(f"ema_update_after_step must be a non-negative integer; got {after!r}")
+
+
+def ema_decay_at(applied_step: int, max_decay: float, update_after: int = 0) -> float:
+    """The EMA decay d of the optimizer step whose 1-based APPLIED index is `applied_step` (skipped steps do not count), in
+    double: diffusers' EMAModel.get_decay with use_ema_warmup=False, restated from its published definition —
+        n = max(0, applied_step − update_after − 1) ;  d = 0 if n <= 0 else min(max_decay, (1 + n)/(10 + n))
+    with `max_decay` rounded to fp32 first, as the kernel receives it.  d = 0 on the first counted step: the update
+    s − 1·(s − p) then moves the average onto the parameters."""
+    n = max(0, int(applied_step) - int(update_after) - 1)
+    if n <= 0:
+        return 0.0
+    return min(_f32(max_decay), (1.0 + n) / (10.0 + n))
+
+
+def ema_one_minus_decay_at(applied_step: int, max_decay: float, update_after: int = 0) -> float:
+    """omd = fp32(1 − d) of `ema_decay_at`, as a double: the factor of the update s ← s − omd·(s − p)."""
+    return _f32(1.0 - ema_decay_at(applied_step, max_decay, update_after))
+
+
 # -- checkpoints: what the two trainers share of validating one before anything is written ---------------------------------
 CHECKPOINT_VERSION = 1
 

@@ -14,6 +14,7 @@ slab, which is also the RCCL send/receive buffer — no packing, one or two coll
 and the optimizer is two launches over the slab.  Data parallelism is one process per GPU over
 `torch.distributed` (backend "nccl" = RCCL over xGMI); only the LoRA gradients (≈5 MB at rank 4) ever cross GPUs.
 """
+import contextlib
 import functools
 import math
 import warnings
@@ -439,7 +440,12 @@ class FusedClipAdamW:
     (the reference builds one param group for the UNet and one for the text encoder,
     train_lora_dreambooth.py:659-676)."""
 
-    def __init__(self, slab: LoraSlab, groups: Sequence[dict], betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0):
+    def __init__(self, slab: LoraSlab, groups: Sequence[dict], betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
+                 ema_decay: Optional[float] = None, ema_update_after: int = 0):
+        """ema_decay (None: no average, no buffer, the launches as they were): keeps `shadow`, an exponential moving average
+        of the LoRA region of the slab, updated INSIDE the AdamW launch of every group that is not row-structured
+        (lora_adamw_ema_step; the decay of a step is `step.ema_decay_at(applied steps, ema_decay, ema_update_after)`).  A
+        row-structured group (the token table) is not averaged: `shadow` covers the LoRA region only."""
         self.slab = slab
         self.groups = [dict(g) for g in groups]  # {"range": (a,b), "lr": .., "weight_decay": ..}
         self.betas, self.eps, self.max_grad_norm = betas, eps, max_grad_norm
@@ -447,6 +453,10 @@ class FusedClipAdamW:
         self.exp_avg_sq = torch.zeros_like(slab.params)
         self.norm = torch.zeros(4, dtype=torch.float32, device=slab.params.device)
         self.step_count = 0
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_update_after = int(ema_update_after)
+        if self.ema_decay is not None:
+            self.shadow = slab.params[: slab.stride].clone()
 
     def step(self, grad_mul: float = 1.0, lr_mul: float = 1.0):
         """One optimizer step on the current gradient slab; `grad_mul` = 1/(world_size·loss_scale); `lr_mul` = the learning-rate
@@ -468,6 +478,11 @@ class FusedClipAdamW:
                 nat.lora_adamw_rows(s.params[a:b].view(V, D), s.grads[a:b].view(V, D), self.exp_avg[a:b].view(V, D),
                                     self.exp_avg_sq[a:b].view(V, D), active, self.norm, grad_mul, self.max_grad_norm, g["lr"] * lr_mul,
                                     self.betas[0], self.betas[1], self.eps, g.get("weight_decay", 1e-2), 0)
+                continue
+            if self.ema_decay is not None:
+                nat.lora_adamw_ema_step(s.params[a:b], s.grads[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b], self.shadow[a:b],
+                                        self.norm, grad_mul, self.max_grad_norm, g["lr"] * lr_mul, self.betas[0], self.betas[1],
+                                        self.eps, g.get("weight_decay", 1e-2), 0, self.ema_decay, self.ema_update_after)
                 continue
             nat.lora_adamw_step(s.params[a:b], s.grads[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b], self.norm,
                                 grad_mul, self.max_grad_norm, g["lr"] * lr_mul, self.betas[0], self.betas[1], self.eps,
@@ -706,7 +721,8 @@ class LoraTrainer:
                  lr_scheduler: str = "constant", lr_warmup_steps: int = 0, max_train_steps: Optional[int] = None,
                  scheduler_steps_first: bool = False, early_bucket: bool = False, scheduler_steps_per_call: int = 1,
                  gradient_accumulation_steps: int = 1, snr_gamma: Optional[float] = None,
-                 timestep_weights: Optional[torch.Tensor] = None, noise_offset: float = 0.0):
+                 timestep_weights: Optional[torch.Tensor] = None, noise_offset: float = 0.0,
+                 ema_decay: Optional[float] = None, ema_update_after_step: int = 0):
         """capture_graph: record add_noise → [text encoder] → UNet forward → loss → backward → factor gradients of a step
         once into a hipGraph and replay it on later steps with the same shapes (inputs are copied into static buffers).
         The gradient exchange and the optimizer stay outside the graph, so no collective is ever captured.  A step with a
@@ -751,7 +767,16 @@ class LoraTrainer:
         each other).  The table lives in device memory and is read inside the loss kernel, so it works on every route — also
         with the caller's `noise` and `timesteps`.  The loss a step returns is the weighted loss.  `noise_offset` adds
         noise_offset·ξ[b, c], one normal per (row, channel), to the noise of the DEVICE draw (`ddpm_*_prologue_offset`); a step
-        with the caller's own `noise` raises when it is non-zero."""
+        with the caller's own `noise` raises when it is non-zero.
+        EMA (an extension beyond the reference; diffusers' `--use_ema` / EMAModel without warm-up): `ema_decay` in
+        (0, 1) keeps an exponential moving average of the LoRA factors, `opt.shadow` — updated inside the AdamW launch
+        (lora_adamw_ema_step), hence once per OPTIMIZER step: not on a step the loss scaler skipped, not on the micro-batches
+        inside an accumulation window — with the decay `step.ema_decay_at(applied steps, ema_decay, ema_update_after_step)`:
+        0 up to and including applied step ema_update_after_step + 1, then min(ema_decay, (1 + n)/(10 + n)).  The average is
+        part of a checkpoint ("lora.ema") and `ema_weights()` puts it in the model's place.  None (default): no buffer, no
+        other launch, the trainer as it was.  A trainable token table is NOT averaged: it keeps its live values.  Out of
+        scope: InversionTrainer, the power / `inv_gamma` warm-up form of the decay, averaging the token table."""
+        stp.check_ema(ema_decay, ema_update_after_step)
         self.accum = int(gradient_accumulation_steps)
         if self.accum < 1:
             raise ValueError("gradient_accumulation_steps must be >= 1")
@@ -792,7 +817,7 @@ class LoraTrainer:
         if train_emb:
             groups.append({"range": self.slab.dense_ranges[0], "lr": lr_embed,
                            "weight_decay": weight_decay if weight_decay_embed is None else weight_decay_embed})
-        self.opt = FusedClipAdamW(self.slab, groups, betas, eps, max_grad_norm)
+        self.opt = FusedClipAdamW(self.slab, groups, betas, eps, max_grad_norm, ema_decay, ema_update_after_step)
         self.device = self.slab.params.device
         self.dtype = stp.compute_dtype(unet)
         if self.device.type == "cuda" and getattr(unet, "conv3x3_front", False):
@@ -840,6 +865,8 @@ class LoraTrainer:
         """DDP construction broadcasts module state from rank 0 (train_lora_dreambooth.py:751-757); the frozen
         base is loaded identically everywhere, so only the LoRA slab travels."""
         dist.broadcast(self.slab.params, src=0, group=self.pg)
+        if self.opt.ema_decay is not None:  # the average starts from the parameters every rank now holds
+            self.opt.shadow.copy_(self.slab.params[: self.slab.stride])
 
     def _install_bucket_hook(self):
         """Two buckets in backward-completion order.  Enumeration order is down, up, mid; backward finishes the
@@ -953,6 +980,7 @@ class LoraTrainer:
         With `gradient_accumulation_steps` = n > 1 this is one micro-batch: the device draw is keyed by (seed, optimizer step · n
         + index of the micro-batch), so the micro-batches of a window draw differently; the loss returned is the micro-batch's
         own, undivided, as the loop logs it."""
+        self._refuse_inside_ema_weights("step()")
         if (encoder_hidden_states is None) == (input_ids is None):
             raise ValueError("pass exactly one of encoder_hidden_states and input_ids")
         if input_ids is not None and self.text_encoder is None:
@@ -1066,6 +1094,7 @@ class LoraTrainer:
                 "scheduler_steps_first": self.scheduler_steps_first, "scheduler_steps_per_call": self.scheduler_steps_per_call,
                 "v_prediction": bool(self.v_prediction),
                 "compute_dtype": str(self.dtype).replace("torch.", ""),
+                "ema_decay": self.opt.ema_decay, "ema_update_after_step": self.opt.ema_update_after,
                 **stp.objective_config(self.snr_gamma, self._timestep_weights_digest, self.noise_offset)}
 
     def state_dict(self) -> dict:
@@ -1076,7 +1105,9 @@ class LoraTrainer:
         trainable token table comes with its `active` mask and — rows that never had a gradient have exactly zero moments
         under the row-aware AdamW, which one reduction on the device confirms — the moment rows of the active rows only; the
         dense moments where that does not hold.  Waits for the device; never part of `step()`.  No collective: every rank may
-        call it.  Inside an accumulation window (the gradient slab holds a partial sum) it raises RuntimeError."""
+        call it.  Inside an accumulation window (the gradient slab holds a partial sum) it raises RuntimeError.  With
+        `ema_decay`: the average of the LoRA region as "lora.ema" (raises inside `ema_weights()`)."""
+        self._refuse_inside_ema_weights("state_dict()")
         if self._micro != 0:
             raise RuntimeError(f"LoraTrainer: micro-batch {self._micro} of {self.accum} of an accumulation window is pending — "
                                "a checkpoint is taken on optimizer steps only")
@@ -1084,6 +1115,8 @@ class LoraTrainer:
         n = s.numel
         tensors = {"lora.params": s.params[:n].cpu(), "lora.exp_avg": opt.exp_avg[:n].cpu(),
                    "lora.exp_avg_sq": opt.exp_avg_sq[:n].cpu(), "opt.norm": opt.norm[2:4].cpu()}
+        if opt.ema_decay is not None:
+            tensors["lora.ema"] = opt.shadow[:n].cpu()
         if self.token_table is not None:
             tt = self.token_table
             a, b = tt.range
@@ -1110,7 +1143,9 @@ class LoraTrainer:
         buffers, so the Parameter views, the row-aware optimizer group and the addresses a live recording has baked in stay
         valid: the next `step()` replays it (unless the loss scale changed — the fingerprint then asks for a new recording
         anyway).  Constructor arguments are the caller's: those the file records differently are listed in one warning.
-        An accumulation window in progress is dropped.  No collective: under data parallelism every rank loads the same file."""
+        An accumulation window in progress is dropped.  No collective: under data parallelism every rank loads the same file.
+        A trainer with `ema_decay` expects the average ("lora.ema") and a trainer without refuses a file that has it."""
+        self._refuse_inside_ema_weights("load_state_dict()")
         meta = stp.check_checkpoint_header(sd, "LoraTrainer")
         tensors = sd["tensors"]
         own = self._layout_signature()
@@ -1122,6 +1157,8 @@ class LoraTrainer:
         n, f32 = self.slab.numel, torch.float32
         expected = {"lora.params": ((n,), f32), "lora.exp_avg": ((n,), f32), "lora.exp_avg_sq": ((n,), f32),
                     "opt.norm": ((2,), f32)}
+        if self.opt.ema_decay is not None:
+            expected["lora.ema"] = ((n,), f32)
         tt = self.token_table
         compact = "dense.0.rows" in tensors
         if tt is not None:
@@ -1147,6 +1184,8 @@ class LoraTrainer:
         opt.exp_avg[:n].copy_(tensors["lora.exp_avg"])
         opt.exp_avg_sq[:n].copy_(tensors["lora.exp_avg_sq"])
         opt.norm[2:4].copy_(tensors["opt.norm"])
+        if opt.ema_decay is not None:
+            opt.shadow[:n].copy_(tensors["lora.ema"])
         if tt is not None:
             a, b = tt.range
             s.params[a:b].view(tt.V, tt.D).copy_(tensors["dense.0.param"])
@@ -1167,6 +1206,42 @@ class LoraTrainer:
         self._micro = 0
         s.zero_grad()  # (also forgets the factor-gradient problems a dropped window had deferred)
         s.repack()
+
+    # -- the averaged weights in the model's place -------------------------------------------------------------------------
+    _ema_active = False  # True inside `ema_weights()`: the slab holds the average, `opt.shadow` the live weights
+
+    def _refuse_inside_ema_weights(self, what: str):
+        if self._ema_active:
+            raise RuntimeError(f"LoraTrainer: {what} inside `ema_weights()` — the slab holds the averaged weights there; "
+                               "leave the block first")
+
+    def _swap_ema(self):
+        n = self.slab.numel
+        nat.lora_slab_swap(self.slab.params[:n], self.opt.shadow[:n])
+        self.slab.repack()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with trainer.ema_weights():` — inside the block the LoRA Parameters and the packed factors hold the AVERAGED
+        weights: a `LatentSampler` on this UNet, `save_lora_weight`, `save_safeloras*`, `save_all`, `weight_apply_lora` and a
+        plain forward all read the average.  Entry exchanges the LoRA region of the slab with `opt.shadow` BY VALUE
+        (lora_slab_swap, one launch) and re-packs; exit — also through an exception — does the same again, which restores the
+        live bits exactly.  No address changes, so a live training recording and a sampler's recording stay valid.  A trainable
+        token table is not averaged and keeps its live values.  Inside the block `step()`, `state_dict()`, `load_state_dict()`
+        and another `ema_weights()` raise RuntimeError; so does entering inside an accumulation window, or without `ema_decay`."""
+        if self.opt.ema_decay is None:
+            raise RuntimeError("LoraTrainer: ema_weights() needs a trainer built with ema_decay")
+        self._refuse_inside_ema_weights("ema_weights()")
+        if self._micro != 0:
+            raise RuntimeError(f"LoraTrainer: micro-batch {self._micro} of {self.accum} of an accumulation window is pending — "
+                               "the averaged weights are swapped in on optimizer steps only")
+        self._swap_ema()
+        self._ema_active = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_active = False
 
     def save_checkpoint(self, path):
         """`state_dict()` as ONE safetensors file (formats.save_checkpoint_file: scalars and signature as a JSON string in

@@ -385,6 +385,25 @@ int lora_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_
                     void* stream);
 
 /*
+ * Exponential moving average (EMA) of the trained parameters, kept inside the optimizer launch.  These two entries replace no
+ * line of the reference, which keeps no average: the rule is restated from its published definition ("EMA of
+ * parameters").
+ *   lora_adamw_ema_step : lora_adamw_step — same arithmetic, same bits in param / exp_avg / exp_avg_sq — and, in the same launch,
+ *                         on the parameter value p' just computed:   shadow ← shadow − omd·(shadow − p')   op by op in fp32, with
+ *                             t = norm_in[2] (applied steps, this one included), n = max(0, t − ema_update_after − 1),
+ *                             d = 0 if n <= 0 else min(ema_max_decay, (1 + n)/(10 + n)) in double, omd = (float)(1 − d).
+ *                         `norm_in` is required: the average always follows the device counter, whatever `step` gives the bias
+ *                         corrections.  norm_in[1] != 0 (overflow): nothing is written, the shadow included.
+ *                         LORA_E_BADARG: a null pointer, n < 1, step < 0, ema_max_decay outside [0, 1], ema_update_after < 0.
+ *   lora_slab_swap      : exchanges the fp32 buffers a and b (n elements each, any 4-byte alignment) in place, one launch.
+ *                         LORA_E_BADARG, and no launch, when a == b or the two ranges overlap.
+ */
+int lora_adamw_ema_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* shadow, int64_t n,
+                        const float* norm_in, float grad_mul, float max_norm, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int step, float ema_max_decay, int ema_update_after, void* stream);
+int lora_slab_swap(float* a, float* b, int64_t n, void* stream);
+
+/*
  * Step prologue — training_scripts/train_lora_dreambooth.py:824-853 (add_noise / target selection)
  * with the DDPM definitions (diffusers DDPMScheduler, not vendored in the reference):
  *     noisy  = sqrt_acp[t_b]·x0 + sqrt_1macp[t_b]·eps
