@@ -88,6 +88,10 @@ SIGNATURES = {
     "lora_adamw_ema_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _i32,
                                    _vp]),
     "lora_slab_swap": (_i32, [_vp, _vp, _i64, _vp]),
+    "lora_prodigy_moments": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32,
+                                    _f32, _f32, _f32, _i32, _i32, _vp]),
+    "lora_prodigy_apply": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _f32, _f32, _f32, _i32, _f32, _i32, _vp]),
+    "lora_prodigy_workspace_bytes": (_i64, []),
     "ddpm_add_noise": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp]),
     "ddpm_noise_prologue": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, ctypes.c_uint64, ctypes.c_uint64,
                                    _i32, _i32, _vp]),
@@ -736,6 +740,61 @@ def lora_slab_swap(a, b) -> None:
                                                                                               and b.is_contiguous()):
         raise ValueError("lora_slab_swap: two contiguous fp32 tensors of equal length")
     _check(lib().lora_slab_swap(_ptr(a), _ptr(b), a.numel(), _stream(a)), "lora_slab_swap")
+
+
+PRODIGY_MAX_RANGES = 4
+
+
+def prodigy_ranges(ends, lrs, wds=None):
+    """The host arrays `lora_prodigy_moments` / `lora_prodigy_apply` read their ranges from: (int64[k], float[k], float[k] or None)."""
+    k = len(ends)
+    if not (1 <= k <= PRODIGY_MAX_RANGES) or len(lrs) != k or (wds is not None and len(wds) != k):
+        raise ValueError(f"prodigy: 1..{PRODIGY_MAX_RANGES} ranges, each with a learning rate and a weight decay")
+    return ((_i64 * k)(*[int(e) for e in ends]), (_f32 * k)(*[float(x) for x in lrs]),
+            None if wds is None else (_f32 * k)(*[float(x) for x in wds]))
+
+
+def _require_prodigy_buffers(what: str, n: int, buffers, norm_in, scalars) -> None:
+    """The kernels move 16 bytes per lane over n fp32 elements of every buffer: each must be fp32, contiguous and n long."""
+    for name, t in buffers:
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise ValueError(f"{what}: `{name}` must be a contiguous fp32 tensor of the parameters' {n} elements; got "
+                             f"{t.dtype}, {t.numel()} elements, contiguous {t.is_contiguous()}")
+    for name, t, k in (("norm_in", norm_in, 4), ("scalars", scalars, 8)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < k:
+            raise ValueError(f"{what}: `{name}` must be a contiguous fp32 tensor of at least {k} elements")
+
+
+def lora_prodigy_moments(param, param0, grad, exp_avg, exp_avg_sq, s, ends, lrs, norm_in, scalars, grad_mul, max_norm, beta1,
+                         beta2, beta3, d0, d_coef, growth_rate, use_bias_correction: bool, safeguard_warmup: bool) -> None:
+    """Phase A of a Prodigy step and the scalar step d → d_new on the device (include/lora_hip.h: lora_prodigy_moments).  All
+    buffers fp32, contiguous, of param's length; `ends` / `lrs`: the contiguous ranges and their γ (python sequences)."""
+    _require_device(param, param0, grad, exp_avg, exp_avg_sq, s, norm_in, scalars)
+    _require_prodigy_buffers("lora_prodigy_moments", param.numel(), (("param", param), ("param0", param0), ("grad", grad),
+                                                                     ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("s", s)),
+                             norm_in, scalars)
+    e, l, _ = prodigy_ranges(ends, lrs)
+    ws = _workspace(param.device, int(lib().lora_prodigy_workspace_bytes()), "prodigy")
+    _check(lib().lora_prodigy_moments(_ptr(param), _ptr(param0), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(s), param.numel(),
+                                      e, l, len(ends), _ptr(norm_in), _ptr(scalars), _ptr(ws), float(grad_mul), float(max_norm),
+                                      float(beta1), float(beta2), float(beta3), float(d0), float(d_coef), float(growth_rate),
+                                      int(bool(use_bias_correction)), int(bool(safeguard_warmup)), _stream(param)),
+           "lora_prodigy_moments")
+
+
+def lora_prodigy_apply(param, exp_avg, exp_avg_sq, shadow, ends, lrs, wds, norm_in, scalars, beta1, beta2, eps,
+                       use_bias_correction: bool, ema_max_decay: float = 0.0, ema_update_after: int = 0) -> None:
+    """Phase B of a Prodigy step; `shadow` (None: no average) as in `lora_adamw_ema_step` (include/lora_hip.h: lora_prodigy_apply)."""
+    _require_device(param, exp_avg, exp_avg_sq, shadow, norm_in, scalars)
+    _require_prodigy_buffers("lora_prodigy_apply", param.numel(), (("param", param), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)),
+                             norm_in, scalars)
+    if shadow is not None and (shadow.dtype != torch.float32 or shadow.numel() != param.numel() or not shadow.is_contiguous()):
+        raise ValueError("lora_prodigy_apply: the shadow must be a contiguous fp32 tensor with the parameters' element count")
+    e, l, w = prodigy_ranges(ends, lrs, wds)
+    _check(lib().lora_prodigy_apply(_ptr(param), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(shadow), param.numel(), e, l, w, len(ends),
+                                    _ptr(norm_in), _ptr(scalars), float(beta1), float(beta2), float(eps),
+                                    int(bool(use_bias_correction)), float(ema_max_decay), int(ema_update_after), _stream(param)),
+           "lora_prodigy_apply")
 
 
 def ddpm_add_noise(x0, eps, t, sqrt_acp, sqrt_1macp, out_dtype: torch.dtype, v_prediction: bool, want_target=True):

@@ -197,6 +197,29 @@ def ema_one_minus_decay_at(applied_step: int, max_decay: float, update_after: in
     return _f32(1.0 - ema_decay_at(applied_step, max_decay, update_after))
 
 
+# -- Prodigy: the host's rules for the options `lora_prodigy_moments` takes ------------------------------------------------------
+OPTIMIZERS = ("adamw", "prodigy")
+
+
+def check_prodigy(optimizer, d0=1e-6, d_coef=1.0, growth_rate=math.inf, use_bias_correction=False, safeguard_warmup=False,
+                  betas=(0.9, 0.999)):
+    """`LoraTrainer`'s rules for `optimizer` and its Prodigy options, on the host, before anything is built (the options are
+    checked whichever optimizer is chosen: a typo does not wait for the switch).  Returns beta3 = sqrt(beta2)."""
+    if optimizer not in OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {OPTIMIZERS}; got {optimizer!r}")
+    for name, value in (("prodigy_d0", d0), ("prodigy_d_coef", d_coef)):
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or not _f32(value) > 0.0:
+            raise ValueError(f"{name} must be a positive finite number (also after rounding to fp32); got {value!r}")
+    if isinstance(growth_rate, bool) or not isinstance(growth_rate, (int, float)) or not growth_rate >= 1.0:
+        raise ValueError(f"prodigy_growth_rate must be >= 1 (inf: no limit); got {growth_rate!r}")
+    for name, value in (("prodigy_use_bias_correction", use_bias_correction), ("prodigy_safeguard_warmup", safeguard_warmup)):
+        if not isinstance(value, bool):
+            raise ValueError(f"{name} must be True or False; got {value!r}")
+    if optimizer == "prodigy" and not all(0.0 <= _f32(b) < 1.0 for b in betas):
+        raise ValueError(f"Prodigy needs betas in [0, 1); got {betas!r}")
+    return math.sqrt(_f32(betas[1])) if 0.0 <= _f32(betas[1]) < 1.0 else None
+
+
 # -- checkpoints: what the two trainers share of validating one before anything is written ---------------------------------
 CHECKPOINT_VERSION = 1
 
@@ -253,6 +276,24 @@ def check_checkpoint_tensors(tensors, expected):
     extra = sorted(set(tensors) - set(expected))
     if extra:
         raise ValueError(f"checkpoint tensor {extra[0]!r} is not part of this trainer's state")
+
+
+def check_checkpoint_optimizer(meta, owner: str, optimizer: str, options=None):
+    """The file was written under the optimizer this trainer runs ("adamw" where the header is silent) — AdamW's and Prodigy's
+    states do not convert — and, under Prodigy, with the same d0: the kernel's `d == d0` test is an exact fp32 comparison, so
+    another d0 would silently change which step takes the first, unlimited growth.  The other options are the caller's and go
+    through `warn_config_differences`."""
+    saved = meta.get("optimizer", "adamw")
+    if saved != optimizer:
+        raise ValueError(f"{owner}: the checkpoint was written under optimizer={saved!r}, this trainer runs {optimizer!r} — "
+                         "their states do not convert")
+    if optimizer == "prodigy":
+        recorded = meta.get("prodigy")
+        d0 = recorded.get("d0") if isinstance(recorded, dict) else None
+        if isinstance(d0, bool) or not isinstance(d0, (int, float)) or _f32(d0) != _f32(options["d0"]):
+            raise ValueError(f"{owner}: the checkpoint was written with prodigy_d0={d0!r}, this trainer has "
+                             f"prodigy_d0={options['d0']!r} — the estimate's first growth is decided by d == d0; build the "
+                             "trainer with the file's value")
 
 
 def check_checkpoint_counters(meta, names):

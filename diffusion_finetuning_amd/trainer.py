@@ -503,6 +503,91 @@ class FusedClipAdamW:
         return int(self.norm[3].item())
 
 
+class FusedProdigy:
+    """clip_grad_norm_ + Prodigy (Mishchenko & Defazio, arXiv:2306.06101; restated) over the LoRA region of the slab:
+    AdamW whose step size is d·lr, d an on-line estimate of the distance to the solution.  The surface of `FusedClipAdamW`; one
+    step is three launches (norm, lora_prodigy_moments, lora_prodigy_apply) whatever the number of groups, and d, d_max and the
+    numerator live in device memory (`scalars`) next to the step counter: no host sync, valid under a replayed graph.
+    `p0` is the LoRA region as it was when this object was built."""
+
+    def __init__(self, slab: LoraSlab, groups: Sequence[dict], betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
+                 ema_decay: Optional[float] = None, ema_update_after: int = 0, d0: float = 1e-6, d_coef: float = 1.0,
+                 growth_rate: float = math.inf, use_bias_correction: bool = False, safeguard_warmup: bool = False):
+        self.beta3 = stp.check_prodigy("prodigy", d0, d_coef, growth_rate, use_bias_correction, safeguard_warmup, betas)
+        self.slab = slab
+        self.groups = [dict(g) for g in groups]  # {"range": (a,b), "lr": .., "weight_decay": ..}: contiguous from 0
+        ends = [g["range"][1] for g in self.groups]
+        starts = [g["range"][0] for g in self.groups]
+        if (any(g.get("rows") is not None for g in self.groups) or not 1 <= len(ends) <= nat.PRODIGY_MAX_RANGES
+                or starts != [0] + ends[:-1] or ends[-1] != slab.numel or any(b <= a for a, b in zip(starts, ends))):
+            raise ValueError(f"FusedProdigy: 1..{nat.PRODIGY_MAX_RANGES} contiguous LoRA ranges that cover the slab's LoRA region "
+                             "(a row-structured group — the token table — is not supported)")
+        self.ends = ends
+        self.betas, self.eps, self.max_grad_norm = betas, eps, max_grad_norm
+        self.d0, self.d_coef, self.growth_rate = float(d0), float(d_coef), float(growth_rate)
+        self.use_bias_correction, self.safeguard_warmup = bool(use_bias_correction), bool(safeguard_warmup)
+        n, dev = slab.numel, slab.params.device
+        self.exp_avg = torch.zeros_like(slab.params)
+        self.exp_avg_sq = torch.zeros_like(slab.params)
+        self.s = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.p0 = slab.params[:n].clone()
+        self.norm = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.scalars = torch.zeros(8, dtype=torch.float32, device=dev)  # d, d_max, numerator, d_prev, d_hat, denom, 0, 0
+        self.scalars[:2] = self.d0
+        self.step_count = 0
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_update_after = int(ema_update_after)
+        if self.ema_decay is not None:
+            self.shadow = slab.params[: slab.stride].clone()
+
+    def options(self) -> dict:
+        """The Prodigy options as a checkpoint's header records them."""
+        return {"d0": self.d0, "d_coef": self.d_coef, "growth_rate": None if math.isinf(self.growth_rate) else self.growth_rate,
+                "use_bias_correction": self.use_bias_correction, "safeguard_warmup": self.safeguard_warmup, "beta3": self.beta3}
+
+    def step(self, grad_mul: float = 1.0, lr_mul: float = 1.0):
+        """One optimizer step on the current gradient slab; arguments and counters as `FusedClipAdamW.step`.  γ of a group is its
+        lr · `lr_mul` (with Prodigy lr = 1.0 is the normal setting)."""
+        s, n = self.slab, self.slab.numel
+        self.step_count += 1
+        nat.lora_grad_sqnorm(s.grads[:n] if s.total == s.stride else s.grads, grad_mul, self.norm)
+        lrs = [g["lr"] * lr_mul for g in self.groups]
+        wds = [g.get("weight_decay", 1e-2) for g in self.groups]
+        nat.lora_prodigy_moments(s.params[:n], self.p0, s.grads[:n], self.exp_avg[:n], self.exp_avg_sq[:n], self.s, self.ends, lrs,
+                                 self.norm, self.scalars, grad_mul, self.max_grad_norm, self.betas[0], self.betas[1], self.beta3,
+                                 self.d0, self.d_coef, self.growth_rate, self.use_bias_correction, self.safeguard_warmup)
+        nat.lora_prodigy_apply(s.params[:n], self.exp_avg[:n], self.exp_avg_sq[:n],
+                               self.shadow[:n] if self.ema_decay is not None else None, self.ends, lrs, wds, self.norm,
+                               self.scalars, self.betas[0], self.betas[1], self.eps, self.use_bias_correction,
+                               self.ema_decay or 0.0, self.ema_update_after)
+
+    def grad_norm(self) -> float:
+        """Total (pre-clip) gradient L2 norm of the last step (host sync)."""
+        return math.sqrt(float(self.norm[0].item()))
+
+    def overflowed(self) -> bool:
+        return bool(self.norm[1].item() != 0.0)
+
+    def applied_steps(self) -> int:
+        """Optimizer steps that really updated the parameters (host sync)."""
+        return int(self.norm[2].item())
+
+    def skipped_steps(self) -> int:
+        return int(self.norm[3].item())
+
+    def d(self) -> float:
+        """The current estimate d (host sync: for logging, never part of a step)."""
+        return float(self.scalars[0].item())
+
+    def d_history_entry(self) -> dict:
+        """What a log keeps of the last step's estimate (one host sync): d, d_max, the numerator, the d the step ran at, the
+        step's d_hat (0 where the step formed none: a zero denominator, every γ zero) and denominator, and the count of
+        applied steps."""
+        d, d_max, numerator, d_prev, d_hat, denom = self.scalars[:6].tolist()
+        return {"d": d, "d_max": d_max, "numerator": numerator, "d_prev": d_prev, "d_hat": d_hat, "denom": denom,
+                "applied_steps": self.applied_steps()}
+
+
 class SlabExchange:
     """Synchronous data-parallel exchange of the flat gradient slab: SUM all-reduce in at most two buckets
     (the mean's 1/world is folded into the optimizer's grad_mul).  The reference gets the same effect
@@ -722,7 +807,9 @@ class LoraTrainer:
                  scheduler_steps_first: bool = False, early_bucket: bool = False, scheduler_steps_per_call: int = 1,
                  gradient_accumulation_steps: int = 1, snr_gamma: Optional[float] = None,
                  timestep_weights: Optional[torch.Tensor] = None, noise_offset: float = 0.0,
-                 ema_decay: Optional[float] = None, ema_update_after_step: int = 0):
+                 ema_decay: Optional[float] = None, ema_update_after_step: int = 0, optimizer: str = "adamw",
+                 prodigy_d0: float = 1e-6, prodigy_d_coef: float = 1.0, prodigy_growth_rate: float = math.inf,
+                 prodigy_use_bias_correction: bool = False, prodigy_safeguard_warmup: bool = False):
         """capture_graph: record add_noise → [text encoder] → UNet forward → loss → backward → factor gradients of a step
         once into a hipGraph and replay it on later steps with the same shapes (inputs are copied into static buffers).
         The gradient exchange and the optimizer stay outside the graph, so no collective is ever captured.  A step with a
@@ -775,8 +862,20 @@ class LoraTrainer:
         0 up to and including applied step ema_update_after_step + 1, then min(ema_decay, (1 + n)/(10 + n)).  The average is
         part of a checkpoint ("lora.ema") and `ema_weights()` puts it in the model's place.  None (default): no buffer, no
         other launch, the trainer as it was.  A trainable token table is NOT averaged: it keeps its live values.  Out of
-        scope: InversionTrainer, the power / `inv_gamma` warm-up form of the decay, averaging the token table."""
+        scope: InversionTrainer, the power / `inv_gamma` warm-up form of the decay, averaging the token table.
+        Optimizer (an extension beyond the reference, PAPERS.md "Prodigy"): `optimizer="prodigy"` replaces AdamW by Prodigy
+        (`FusedProdigy`: AdamW at the step size d·lr, d estimated on the device from two sums over all LoRA elements — three
+        launches per step instead of two, no host sync).  `lr` / `lr_text` are then multipliers of d, 1.0 being the normal
+        setting; the schedule, `weight_decay`, `betas`, `eps`, clipping, the loss scaler, accumulation, `ema_decay` and a recorded
+        step work as under AdamW.  `prodigy_d0` (the first d), `prodigy_d_coef`, `prodigy_growth_rate` (inf: no limit on d's
+        growth per step), `prodigy_use_bias_correction`, `prodigy_safeguard_warmup` are the published options.  The LoRA factors
+        as they are when the trainer is built are the p0 the estimate measures from.  A trainable token table is refused.  A
+        checkpoint carries s, p0 and the three scalars; AdamW and Prodigy trainers refuse each other's files.  "adamw" (default):
+        no buffer, no other launch, the trainer as it was."""
         stp.check_ema(ema_decay, ema_update_after_step)
+        stp.check_prodigy(optimizer, prodigy_d0, prodigy_d_coef, prodigy_growth_rate, prodigy_use_bias_correction,
+                          prodigy_safeguard_warmup, betas)
+        self.optimizer = optimizer
         self.accum = int(gradient_accumulation_steps)
         if self.accum < 1:
             raise ValueError("gradient_accumulation_steps must be >= 1")
@@ -817,7 +916,14 @@ class LoraTrainer:
         if train_emb:
             groups.append({"range": self.slab.dense_ranges[0], "lr": lr_embed,
                            "weight_decay": weight_decay if weight_decay_embed is None else weight_decay_embed})
-        self.opt = FusedClipAdamW(self.slab, groups, betas, eps, max_grad_norm, ema_decay, ema_update_after_step)
+        if optimizer == "prodigy":
+            if train_emb:
+                raise ValueError('optimizer="prodigy" does not train a token table: it would need a second copy of the table '
+                                 "and a row-aware form of the estimate; freeze the input embeddings or use optimizer=\"adamw\"")
+            self.opt = FusedProdigy(self.slab, groups, betas, eps, max_grad_norm, ema_decay, ema_update_after_step, prodigy_d0,
+                                    prodigy_d_coef, prodigy_growth_rate, prodigy_use_bias_correction, prodigy_safeguard_warmup)
+        else:
+            self.opt = FusedClipAdamW(self.slab, groups, betas, eps, max_grad_norm, ema_decay, ema_update_after_step)
         self.device = self.slab.params.device
         self.dtype = stp.compute_dtype(unet)
         if self.device.type == "cuda" and getattr(unet, "conv3x3_front", False):
@@ -867,6 +973,8 @@ class LoraTrainer:
         dist.broadcast(self.slab.params, src=0, group=self.pg)
         if self.opt.ema_decay is not None:  # the average starts from the parameters every rank now holds
             self.opt.shadow.copy_(self.slab.params[: self.slab.stride])
+        if self.optimizer == "prodigy":  # the estimate measures from the factors every rank now holds
+            self.opt.p0.copy_(self.slab.params[: self.slab.numel])
 
     def _install_bucket_hook(self):
         """Two buckets in backward-completion order.  Enumeration order is down, up, mid; backward finishes the
@@ -1095,6 +1203,8 @@ class LoraTrainer:
                 "v_prediction": bool(self.v_prediction),
                 "compute_dtype": str(self.dtype).replace("torch.", ""),
                 "ema_decay": self.opt.ema_decay, "ema_update_after_step": self.opt.ema_update_after,
+                **({"optimizer": "prodigy", **{"prodigy_" + k: v for k, v in self.opt.options().items()}}
+                   if self.optimizer == "prodigy" else {}),
                 **stp.objective_config(self.snr_gamma, self._timestep_weights_digest, self.noise_offset)}
 
     def state_dict(self) -> dict:
@@ -1117,6 +1227,9 @@ class LoraTrainer:
                    "lora.exp_avg_sq": opt.exp_avg_sq[:n].cpu(), "opt.norm": opt.norm[2:4].cpu()}
         if opt.ema_decay is not None:
             tensors["lora.ema"] = opt.shadow[:n].cpu()
+        if self.optimizer == "prodigy":
+            tensors["lora.prodigy.s"], tensors["lora.prodigy.p0"] = opt.s.cpu(), opt.p0.cpu()
+            tensors["opt.prodigy"] = opt.scalars[:3].cpu()  # d, d_max, numerator
         if self.token_table is not None:
             tt = self.token_table
             a, b = tt.range
@@ -1134,6 +1247,9 @@ class LoraTrainer:
                 "scheduler_epoch": int(self.scheduler_epoch), "scaler": self.scaler.state_dict(),
                 "compute_dtype": str(self.dtype).replace("torch.", ""), "world_size": int(self.world),
                 "layout": self._layout_signature(), "config": self._config()}
+        if self.optimizer == "prodigy":
+            meta["optimizer"] = "prodigy"
+            meta["prodigy"] = self.opt.options()
         return {"meta": meta, "tensors": tensors}
 
     def load_state_dict(self, sd: dict):
@@ -1148,6 +1264,8 @@ class LoraTrainer:
         self._refuse_inside_ema_weights("load_state_dict()")
         meta = stp.check_checkpoint_header(sd, "LoraTrainer")
         tensors = sd["tensors"]
+        stp.check_checkpoint_optimizer(meta, "LoraTrainer", self.optimizer,
+                                       self.opt.options() if self.optimizer == "prodigy" else None)
         own = self._layout_signature()
         diff = stp.layout_difference(meta.get("layout") or {}, own)
         if diff is not None:
@@ -1159,6 +1277,9 @@ class LoraTrainer:
                     "opt.norm": ((2,), f32)}
         if self.opt.ema_decay is not None:
             expected["lora.ema"] = ((n,), f32)
+        if self.optimizer == "prodigy":
+            expected["lora.prodigy.s"] = expected["lora.prodigy.p0"] = ((n,), f32)
+            expected["opt.prodigy"] = ((3,), f32)
         tt = self.token_table
         compact = "dense.0.rows" in tensors
         if tt is not None:
@@ -1177,6 +1298,10 @@ class LoraTrainer:
             rows = tensors["dense.0.rows"]
             if not torch.equal(rows, tensors["dense.0.active"].nonzero().reshape(-1)):
                 raise ValueError("checkpoint tensor 'dense.0.rows' is not the list of rows that 'dense.0.active' marks")
+        if self.optimizer == "prodigy":
+            d, d_max, _ = tensors["opt.prodigy"].tolist()
+            if not (0.0 < d <= d_max):
+                raise ValueError(f"checkpoint tensor 'opt.prodigy': d = {d!r} and d_max = {d_max!r} are not an estimate's state")
         stp.warn_config_differences("LoraTrainer", meta.get("config"), self._config())
         # -- validated: from here on nothing raises --
         s, opt, dev = self.slab, self.opt, self.device
@@ -1186,6 +1311,11 @@ class LoraTrainer:
         opt.norm[2:4].copy_(tensors["opt.norm"])
         if opt.ema_decay is not None:
             opt.shadow[:n].copy_(tensors["lora.ema"])
+        if self.optimizer == "prodigy":
+            opt.s.copy_(tensors["lora.prodigy.s"])
+            opt.p0.copy_(tensors["lora.prodigy.p0"])
+            opt.scalars.zero_()
+            opt.scalars[:3].copy_(tensors["opt.prodigy"])
         if tt is not None:
             a, b = tt.range
             s.params[a:b].view(tt.V, tt.D).copy_(tensors["dense.0.param"])

@@ -404,6 +404,45 @@ int lora_adamw_ema_step(float* param, const float* grad, float* exp_avg, float* 
 int lora_slab_swap(float* a, float* b, int64_t n, void* stream);
 
 /*
+ * Prodigy (Mishchenko & Defazio, arXiv:2306.06101) over the flat slab: AdamW whose step size is d·lr, with d an on-line estimate
+ * of the distance to the solution kept in DEVICE memory.  These entries replace no line of the reference, which has no such
+ * optimizer: the rule is restated from its published definition ("Prodigy"; parity with the prodigyopt package is
+ * unpinned).  One step = lora_grad_sqnorm, lora_prodigy_moments, lora_prodigy_apply on one stream.
+ *   scalars (8 floats, device): [0] d  [1] d_max  [2] numerator  [3] d_prev  [4] d_hat  [5] denom  [6] [7] unused; the caller
+ *                      sets [0] = [1] = d0 and the rest to 0 once before the first step.
+ *   ranges           : n_ranges (1..4) contiguous ranges of the n elements, range j = [range_end[j-1], range_end[j]) with
+ *                      range_end[-1] = 0 and range_end[n_ranges-1] = n, each with γ_j = lr[j] (the group's lr times the schedule
+ *                      factor) and weight_decay[j].  HOST arrays, read during the call and passed to the launch by value.
+ *   lora_prodigy_moments : with g = grad_mul·grad·clip as lora_adamw_step forms it, t = norm_in[2], bc = sqrt(1−β2^t)/(1−β1^t)
+ *                      (in double; 1 unless use_bias_correction), dlr_j = d·γ_j·bc, on every element i of range j
+ *                          num_i = (d/d0)·dlr_j·g_i·(param0_i − param_i)
+ *                          m_i = β1·m_i + d·(1−β1)·g_i ;  v_i = β2·v_i + d²·(1−β2)·g_i²
+ *                          s_i = β3·s_i + (d/d0)·(d if safeguard_warmup else dlr_j)·g_i ;  den_i = |s_i| (the new s)
+ *                      then once, in double, in the block that finishes last (fp32 block partials, summed in a fixed order: the
+ *                      same bits on every run):  denom = Σ den_i ;  unless denom == 0: numerator = β3·numerator + Σ num_i and,
+ *                      if any γ_j > 0:  d_hat = d_coef·numerator/denom ;  d_new = max(d, d_hat) if d == d0 else d ;
+ *                      d_max = max(d_max, d_hat) ;  d_new = min(d_max, d_new·growth_rate).  Writes d_prev = d, then d = d_new;
+ *                      [4] and [5] are this step's d_hat and denom, d_hat = 0 on a step that forms none.
+ *                      `workspace`: lora_prodigy_workspace_bytes() bytes, 16-byte aligned.
+ *   lora_prodigy_apply   : dlr_j from d_prev;  param_i = param_i·(1 − weight_decay_j·dlr_j) − dlr_j·m_i/(sqrt(v_i) + d·eps)  with
+ *                      the NEW d;  with a non-null `shadow`, in the same launch, lora_adamw_ema_step's average on that param_i.
+ * Both skip entirely when norm_in[1] != 0 (overflow): no buffer, no scalar and no shadow element changes.
+ * Status, decided before any launch: LORA_E_BADARG for a null pointer (`shadow` excepted), n < 1, n_ranges outside 1..4, range
+ * ends that do not increase or do not end at n, a negative lr or weight decay, a beta outside [0, 1), d0 <= 0, d_coef <= 0,
+ * growth_rate < 1, eps < 0, and — with a shadow — ema_max_decay outside [0, 1] or ema_update_after < 0; then LORA_E_ALIGN for a
+ * device buffer or workspace off a 16-byte boundary (the bodies move 16 bytes per lane; any n >= 1).
+ */
+int lora_prodigy_moments(const float* param, const float* param0, const float* grad, float* exp_avg, float* exp_avg_sq, float* s,
+                         int64_t n, const int64_t* range_end, const float* lr, int n_ranges, const float* norm_in,
+                         float* scalars, void* workspace, float grad_mul, float max_norm, float beta1, float beta2, float beta3,
+                         float d0, float d_coef, float growth_rate, int use_bias_correction, int safeguard_warmup, void* stream);
+int lora_prodigy_apply(float* param, const float* exp_avg, const float* exp_avg_sq, float* shadow /* nullable: no EMA */, int64_t n,
+                       const int64_t* range_end, const float* lr, const float* weight_decay, int n_ranges, const float* norm_in,
+                       const float* scalars, float beta1, float beta2, float eps, int use_bias_correction, float ema_max_decay,
+                       int ema_update_after, void* stream);
+int64_t lora_prodigy_workspace_bytes(void);
+
+/*
  * Step prologue — training_scripts/train_lora_dreambooth.py:824-853 (add_noise / target selection)
  * with the DDPM definitions (diffusers DDPMScheduler, not vendored in the reference):
  *     noisy  = sqrt_acp[t_b]·x0 + sqrt_1macp[t_b]·eps
