@@ -118,6 +118,7 @@ SIGNATURES = {
     "ddpm_sample_multistep_keep_shared": (_i32, [_vp] * 13 + [_i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp]),
     "ddpm_sample_sigma_init": (_i32, [_vp] * 7 + [_i32, _i64, _i32, _i32, _f32, _f32, _f32, _i32, _i32, ctypes.c_uint64, _i32, _vp]),
     "ddpm_sample_sigma": (_i32, [_vp] * 14 + [_i32, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "ddpm_cfg_rescale": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _i32, _vp]),
     "embed_rows_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "embed_rows_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp]),
     "lora_adamw_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
@@ -1209,6 +1210,23 @@ def ddpm_sample_sigma(st: SigmaState, model_out, guidance_scale: float, z_out=No
                                    _ptr(st.keep_coef) if keep else 0, st.B, st.per_row, st.hw if keep else 1, st.S, int(st.cfg),
                                    int(st.shared_noise), float(guidance_scale), dtype_code(model_out.dtype), _stream(st.x)),
            "ddpm_sample_sigma")
+
+
+def ddpm_cfg_rescale(st: SampleState, model_out, guidance_scale: float, rescale: float, k_out=None) -> None:
+    """The guidance rescale of a guided iteration, in front of its step launch: both halves of `model_out` [2B, ...] (the model
+    input's dtype, unconditional rows first) are multiplied in place by k_b = rescale·σ(c)/σ(o) + (1 − rescale), o the guided
+    output of sample b (include/lora_hip.h: ddpm_cfg_rescale).  `k_out` (fp32 [B]) gets k.  Serves every state class."""
+    if not st.cfg:
+        raise ValueError("ddpm_cfg_rescale: the state has no guidance rows (a single pass has nothing to rescale)")
+    _require_device(model_out, k_out)
+    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
+        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
+                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
+    if k_out is not None and (k_out.dtype != torch.float32 or tuple(k_out.shape) != (st.B,) or not k_out.is_contiguous()):
+        raise ValueError(f"k_out must be a contiguous fp32 [{st.B}] tensor")
+    _check(lib().ddpm_cfg_rescale(_ptr(model_out), _ptr(k_out), st.B, st.per_row, float(guidance_scale), float(rescale),
+                                  dtype_code(model_out.dtype), _stream(st.x)),
+           "ddpm_cfg_rescale")
 
 
 def embed_rows_fwd(table, ids, out_dtype: torch.dtype):

@@ -71,7 +71,7 @@ class InversionTrainer:
                  lr_warmup_steps: int = 0, max_train_steps: Optional[int] = 1000, accum_iter: int = 4,
                  clip_ti_decay: bool = True, v_prediction: bool = False, capture_graph: bool = False, process_group=None,
                  snr_gamma: Optional[float] = None, timestep_weights: Optional[torch.Tensor] = None,
-                 noise_offset: float = 0.0):
+                 noise_offset: float = 0.0, zero_terminal_snr: bool = False):
         """Arguments are train()'s for this phase: `lr` = ti_lr, `weight_decay` = weight_decay_ti, `lr_scheduler` /
         `lr_warmup_steps` / `max_train_steps` = lr_scheduler, lr_warmup_steps, max_train_steps_ti (:659-664), `accum_iter` =
         gradient_accumulation_steps (:518,670).  The optimizer is AdamW(betas, eps) over the token table (:651-657).
@@ -80,7 +80,9 @@ class InversionTrainer:
         capture_graph: record noise → text encoder → UNet → loss → backward → ti_rows_grad once and replay it; the optimizer
         launch and the zeroing of the gradient buffer stay outside the recording.
         `snr_gamma`, `timestep_weights`, `noise_offset`: LoraTrainer's — Min-SNR-γ or the caller's per-timestep loss weights,
-        looked up inside the loss kernel, and offset noise in the device draw; extensions beyond the reference."""
+        looked up inside the loss kernel, and offset noise in the device draw; extensions beyond the reference.
+        `zero_terminal_snr`: LoraTrainer's — the tables of the schedule rescaled to zero SNR at T − 1; needs `v_prediction`."""
+        self.zero_terminal_snr = stp.check_zero_terminal_snr(zero_terminal_snr, v_prediction)
         stp.check_objective(snr_gamma, timestep_weights, noise_offset, NUM_TRAIN_TIMESTEPS)
         if process_group is not None:
             raise ValueError("InversionTrainer is single-process, as train_inversion is (cli_lora_pti.py:539)")
@@ -128,10 +130,12 @@ class InversionTrainer:
         self.grad = torch.zeros(self.P, D, dtype=torch.float32, device=self.device)
         self.exp_avg = torch.zeros_like(self.grad)
         self.exp_avg_sq = torch.zeros_like(self.grad)
-        self.sqrt_acp, self.sqrt_1macp = ddpm_tables(device=self.device)
+        self.sqrt_acp, self.sqrt_1macp = ddpm_tables(device=self.device, zero_terminal_snr=self.zero_terminal_snr)
         self.snr_gamma = None if snr_gamma is None else float(snr_gamma)
         self.noise_offset = float(noise_offset)
-        self.loss_weights = stp.objective_table(snr_gamma, timestep_weights, ddpm_alphas_cumprod(), self.v_prediction, self.device)
+        self.loss_weights = stp.objective_table(snr_gamma, timestep_weights,
+                                                ddpm_alphas_cumprod(zero_terminal_snr=self.zero_terminal_snr), self.v_prediction,
+                                                self.device)
         self._timestep_weights_digest = stp.table_digest(timestep_weights)
         self.global_step = 0      # micro-steps taken (train_inversion's global_step)
         self.optimizer_steps = 0  # AdamW steps taken (its bias-correction count)
@@ -167,7 +171,7 @@ class InversionTrainer:
         return {"lr": self.lr, "weight_decay": self.weight_decay, "betas": [float(b) for b in self.betas], "eps": self.eps,
                 "accum_iter": self.accum_iter, "lr_scheduler": name, "lr_warmup_steps": warmup, "max_train_steps": max_steps,
                 "clip_ti_decay": self.clip_ti_decay, "v_prediction": self.v_prediction,
-                "compute_dtype": str(self.dtype).replace("torch.", ""),
+                "zero_terminal_snr": self.zero_terminal_snr, "compute_dtype": str(self.dtype).replace("torch.", ""),
                 **stp.objective_config(self.snr_gamma, self._timestep_weights_digest, self.noise_offset)}
 
     def state_dict(self) -> dict:

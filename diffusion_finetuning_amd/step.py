@@ -50,6 +50,35 @@ def noise_prologue(nz: Noising, latents, noise, timesteps, seed, step_key, momen
     return noisy, target, timesteps
 
 
+def zero_terminal_snr(alphas_cumprod) -> torch.Tensor:
+    """ᾱ' float64 [T] on the CPU: the schedule rescaled so that its last timestep carries no signal (Lin et al., "Common
+    Diffusion Noise Schedules and Sample Steps are Flawed", WACV 2024, Algorithm 1), in float64 throughout:
+        s = √ᾱ;   s' = (s − s[T−1])·s[0]/(s[0] − s[T−1]);   ᾱ' = s'².
+    ᾱ'[T−1] is exactly 0, ᾱ'[0] is ᾱ[0] to rounding, and a strictly decreasing table stays one.  diffusers'
+    `rescale_zero_terminal_snr` goes on from ᾱ' to fp32 betas and a second cumprod; this form does not, so the last bits
+    differ from its table.  ValueError for an empty table, a table of one entry, values outside [0, 1] and a table that is not
+    strictly decreasing."""
+    acp = torch.as_tensor(alphas_cumprod).detach().to("cpu", torch.float64).reshape(-1)
+    if acp.numel() < 2:
+        raise ValueError(f"alphas_cumprod must hold at least two timesteps; got {acp.numel()}")
+    if bool(((acp < 0.0) | (acp > 1.0) | acp.isnan()).any()):
+        raise ValueError("alphas_cumprod must be a table of values in [0, 1]")
+    if not bool((acp[1:] < acp[:-1]).all()):
+        raise ValueError("alphas_cumprod must be strictly decreasing")
+    s = acp.sqrt()
+    s = (s - s[-1]) * s[0] / (s[0] - s[-1])
+    return s * s
+
+
+def check_zero_terminal_snr(zero_terminal_snr: bool, v_prediction: bool) -> bool:
+    """The trainers' rule for the flag: ε-prediction has nothing to learn at SNR 0 (the input is the target), and the ε-form of
+    Min-SNR divides by it."""
+    if zero_terminal_snr and not v_prediction:
+        raise ValueError("zero_terminal_snr=True needs v_prediction=True: at zero SNR the noisy input IS the noise, so "
+                         "ε-prediction learns nothing there")
+    return bool(zero_terminal_snr)
+
+
 def min_snr_weights(alphas_cumprod, gamma: float, v_prediction: bool = False) -> torch.Tensor:
     """The Min-SNR-γ loss weights per timestep (Hang et al. 2023), fp32 [T] on the CPU, computed in float64 from ᾱ_t:
     SNR = ᾱ/(1 − ᾱ); ε-prediction min(SNR, γ)/SNR — where SNR == 0 (a zero-terminal-SNR schedule) the weight is 1, the limit;
@@ -306,8 +335,10 @@ def check_checkpoint_counters(meta, names):
 
 
 def warn_config_differences(owner: str, saved, own):
-    """Constructor arguments are the caller's and are not restored: one warning lists those the file records differently."""
-    diff = [f"{k}: checkpoint {saved[k]!r}, trainer {own[k]!r}" for k in own if k in (saved or {}) and saved[k] != own[k]]
+    """Constructor arguments are the caller's and are not restored: one warning lists those the file records differently.  A
+    file from before `zero_terminal_snr` existed was written without it."""
+    saved = {"zero_terminal_snr": False, **(saved or {})}
+    diff =[f"{k}: checkpoint {saved[k]!r}, trainer {own[k]!r}" for k in own if k in (saved or {}) and saved[k] != own[k]]
     if diff:
         warnings.warn(f"{owner}.load_state_dict: the checkpoint was written with other arguments, which are NOT restored — "
                       + "; ".join(diff))

@@ -696,6 +696,27 @@ int ddpm_sample_sigma(float* x, float* xs, float* hist, const void* model_out, v
                       void* stream);
 
 /*
+ * Guidance rescale (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", WACV 2024, §3.4, in the
+ * model-output form of the pipelines' `rescale_noise_cfg`; restated from the paper and the published behaviour, parity unpinned
+ * beyond tests/zero_snr_reference.py).  The one part of a guided iteration that is not linear in the model output, hence a
+ * launch of its own IN FRONT of whichever step entry above follows it.  model_out [2B, per_row] in `dtype`, unconditional rows |
+ * conditional rows; per sample b, all fp32:
+ *     o_e = u_e + g·(c_e − u_e)                  as ddpm_sample_step forms it
+ *     σ_c, σ_o                                   standard deviations of c and of o over the row, centred (means first, then the
+ *                                                sums of squared deviations); their ratio does not depend on the ddof
+ *     k_b = φ·(σ_c/σ_o) + (1 − φ)                φ = rescale; 1 where σ_o == 0, per_row == 1 or the value is not finite (the
+ *                                                published function writes NaN there)
+ *     c_e ← dtype(k_b·c_e),  u_e ← dtype(k_b·u_e)   in place: one fp32 product each, rounded to nearest even
+ * so that the step behind it forms u' + g·(c' − u') = k_b·o up to the storage rounding of the two halves.  k_out (nullable,
+ * fp32 [B]) gets k_b.  One workgroup per sample: a row's result depends neither on B nor on the other rows; sums in a fixed
+ * order, no atomics — equal input gives equal bits.  Accesses under the alignment rule of ddpm_sample_step.  LORA_E_BADARG for a
+ * null model_out, B or per_row < 1, an unknown dtype, a rescale outside [0, 1] or NaN, a guidance_scale that is not finite —
+ * before any HIP call.  No workspace, nothing retained, capturable.
+ */
+int ddpm_cfg_rescale(void* model_out, float* k_out /* nullable */, int B, int64_t per_row, float guidance_scale, float rescale,
+                     int dtype, void* stream);
+
+/*
  * The two ops sandwiched by the hot path inside a transformer block, as streaming kernels.
  *   geglu_gate_fwd : out[M,C]  = h · gelu(g)  with [h | g] = y[M,2C], exact (erf) gelu — the body of diffusers'
  *                    GEGLU.forward, the caller of the `proj` LoraInjectedLinear (target class "GEGLU", lora.py:53).

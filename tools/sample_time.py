@@ -36,7 +36,15 @@ reference's `visualize_progress` / img2img comparison loops:
 in one process, alternating, medians and spreads over --reps; the first (untimed) round also prints how far member k of the
 batch is from member k sampled alone.  --batch is not read in this mode.
 
+--guidance-rescale PHI adds the route `rescaled` per configuration: the replayed route with `guidance_rescale=PHI`, that is
+ddpm_cfg_rescale in front of every step launch inside the recording — timed next to the plain `replayed` route, alternating in
+the same process.  --spacing trailing and --zero-terminal-snr add, for ddpm / ddim, the route `scheduled`: a replayed sampler on
+that spacing and table (v-prediction with the zero-terminal-SNR table; with PHI too if given) — other host tables, the same
+launches.  --routes NAME … times a subset of a configuration's routes.
+
     python tools/sample_time.py [--reps 5] [--steps 50] [--batch 4]
+    python tools/sample_time.py --batch 1 --reps 7 --guidance-rescale 0.7 --spacing trailing --zero-terminal-snr \
+        --routes replayed rescaled scheduled
     python tools/sample_time.py --sweep 4 --method ddpm plms --steps 50 50
     python tools/sample_time.py --batch 1 --method ddpm plms dpmpp_2m --steps 50 50 20
     python tools/sample_time.py --batch 1 --method plms --steps 50 --strength 0.75 --keep-mask
@@ -158,7 +166,8 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
-def routes_for(unet, method, steps, guidance, cond, neg, shape, gen, strength=None, keep_mask=False, karras=False):
+def routes_for(unet, method, steps, guidance, cond, neg, shape, gen, strength=None, keep_mask=False, karras=False, rescale=None,
+               spacing="leading", zero_snr=False):
     """(replayed sampler, {route: callable}, {route: iterations of its run}) of one configuration."""
     kw = dict(karras_sigmas=True) if karras and method in dfa.sampling.SAMPLER_SIGMA_METHODS else {}
     replayed = dfa.LatentSampler(unet, steps, guidance, method=method, **kw)
@@ -180,6 +189,16 @@ def routes_for(unet, method, steps, guidance, cond, neg, shape, gen, strength=No
         "host": lambda: host.sample(cond, neg, seed=7, latent_shape=shape),
         "stock": stock,
     }
+    extra = {}
+    if rescale is not None:  # the plain replayed route plus ddpm_cfg_rescale in front of every step launch
+        extra["rescaled"] = dfa.LatentSampler(unet, steps, guidance, method=method, guidance_rescale=rescale, **kw)
+    if (spacing != "leading" or zero_snr) and method in dfa.sampling.METHODS:  # other host tables, the same launches
+        extra["scheduled"] = dfa.LatentSampler(unet, steps, guidance, method=method, timestep_spacing=spacing,
+                                               zero_terminal_snr=zero_snr, v_prediction=zero_snr, guidance_rescale=rescale or 0.0)
+    for name, sampler in extra.items():
+        routes[name] = lambda sampler=sampler: sampler.sample(cond, neg, seed=7, latent_shape=shape)
+        sampler.begin(cond, neg, seed=7, latent_shape=shape)  # (records)
+        assert sampler.replaying, f"the recording failed: the {name} route would measure host launches"
     iterations = {name: replayed.num_model_evaluations for name in routes}
     if strength is not None:
         g = torch.Generator().manual_seed(4)
@@ -268,6 +287,13 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--strength", type=float, default=None, help="add a replayed image-to-image route at this strength")
     ap.add_argument("--keep-mask", action="store_true", help="with --strength: add the route with a keep mask too")
+    ap.add_argument("--guidance-rescale", type=float, default=None, metavar="PHI",
+                    help="add the route `rescaled`: the replayed route with guidance_rescale=PHI (ddpm_cfg_rescale per iteration)")
+    ap.add_argument("--spacing", default="leading", choices=dfa.sampling.SPACINGS,
+                    help="with ddpm / ddim: add the route `scheduled` on this timestep spacing")
+    ap.add_argument("--zero-terminal-snr", action="store_true",
+                    help="with ddpm / ddim: the route `scheduled` on the zero-terminal-SNR table (v-prediction)")
+    ap.add_argument("--routes", nargs="+", default=None, help="time these routes only (default: all of the configuration)")
     ap.add_argument("--sweep", type=int, default=None, metavar="K",
                     help="K members of a tune_lora_scale sweep one after another against one batched run (lora_scales=)")
     a = ap.parse_args()
@@ -294,12 +320,20 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(3)
     configs = {}
     for method, steps in zip(a.method, a.steps):
-        configs[f"{method} {steps}"] = (method, steps, *routes_for(unet, method, steps, guidance, cond, neg, shape, gen, a.strength, a.keep_mask, a.karras))
+        replayed, routes, its = routes_for(unet, method, steps, guidance, cond, neg, shape, gen, a.strength, a.keep_mask, a.karras,
+                                           a.guidance_rescale, a.spacing, a.zero_terminal_snr)
+        if a.routes:
+            unknown = [r for r in a.routes if r not in routes]
+            if unknown:
+                ap.error(f"--routes: {unknown} not among {list(routes)} of {method}")
+            routes = {name: routes[name] for name in a.routes}
+        configs[f"{method} {steps}"] = (method, steps, replayed, routes, its)
     first, same = {}, {}
     for label, (_, _, replayed, routes, _) in configs.items():  # untimed round: recording, solver searches, allocator
         first[label] = {name: timed(fn) for name, fn in routes.items()}
-        assert replayed.replaying, "the recording failed: the replayed route would measure host launches"
-        same[label] = bool(torch.equal(first[label]["replayed"][1], first[label]["host"][1]))
+        assert replayed.replaying or "replayed" not in routes, "the recording failed: the replayed route would measure host launches"
+        same[label] = bool(torch.equal(first[label]["replayed"][1], first[label]["host"][1])) if {"replayed", "host"} <= set(routes) \
+            else None
         print(f"[{label}] first (untimed) round, ms: " + ", ".join(f"{k} {v[0]:.1f}" for k, v in first[label].items()) +
               f"; replayed == host-launched bit for bit: {same[label]}", flush=True)
     times = {label: {name: [] for name in cfg[3]} for label, cfg in configs.items()}
@@ -314,15 +348,17 @@ def main():
                                                  f"(spread {min(times[label][k]) / its[k]:.3f} – {max(times[label][k]) / its[k]:.3f})"
                                                  for k, v in med.items()), flush=True)
         n_it = its["replayed"]
+        ratio = lambda x, y: med[x] / med[y] if x in med and y in med else None  # noqa: E731
         print(json.dumps({"gpu": torch.cuda.get_device_name(0), "unet": "sd15", "batch": a.batch, "rows": 2 * a.batch,
                           "method": method, "steps": steps, "iterations": n_it, "route_iterations": its, "strength": a.strength,
                           "karras": bool(a.karras and method in dfa.sampling.SAMPLER_SIGMA_METHODS),
+                          "guidance_rescale": a.guidance_rescale, "spacing": a.spacing, "zero_terminal_snr": a.zero_terminal_snr,
                           "dtype": "f16", "guidance": guidance,
                           "reps": a.reps, "median_ms": med, "all_ms": times[label],
                           "ms_per_iteration": {k: v / its[k] for k, v in med.items()},
                           "first_round_ms": {k: v[0] for k, v in first[label].items()}, "replayed_equals_host": same[label],
-                          "stock_over_replayed": med["stock"] / med["replayed"],
-                          "host_over_replayed": med["host"] / med["replayed"]}), flush=True)
+                          "stock_over_replayed": ratio("stock", "replayed"), "host_over_replayed": ratio("host", "replayed"),
+                          "rescaled_over_replayed": ratio("rescaled", "replayed")}), flush=True)
 
 
 if __name__ == "__main__":
