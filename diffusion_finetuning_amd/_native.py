@@ -92,6 +92,7 @@ SIGNATURES = {
                                     _f32, _f32, _f32, _i32, _i32, _vp]),
     "lora_prodigy_apply": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _f32, _f32, _f32, _i32, _f32, _i32, _vp]),
     "lora_prodigy_workspace_bytes": (_i64, []),
+    "lora_max_norm": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp]),
     "ddpm_add_noise": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp]),
     "ddpm_noise_prologue": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, ctypes.c_uint64, ctypes.c_uint64,
                                    _i32, _i32, _vp]),
@@ -796,6 +797,39 @@ def lora_prodigy_apply(param, exp_avg, exp_avg_sq, shadow, ends, lrs, wds, norm_
                                     _ptr(norm_in), _ptr(scalars), float(beta1), float(beta2), float(eps),
                                     int(bool(use_bias_correction)), float(ema_max_decay), int(ema_update_after), _stream(param)),
            "lora_prodigy_apply")
+
+
+MAX_NORM_MAX_RANK = 64
+
+
+def max_norm_table(rows, device):
+    """The device table `lora_max_norm` reads: `rows` = [(up_off, down_off, K, N, r, scale), ...] with element offsets into the
+    fp32 buffer the launch gets; the scale travels as the bits of its fp32 value."""
+    import struct
+
+    out = []
+    for up_off, down_off, K, N, r, scale in rows:
+        if not (1 <= int(r) <= MAX_NORM_MAX_RANK) or min(int(up_off), int(down_off)) < 0 or min(int(K), int(N)) < 1:
+            raise ValueError(f"lora_max_norm: layer (K={K}, N={N}, r={r}) at ({up_off}, {down_off}) is outside ranks 1..64")
+        out.append([int(up_off), int(down_off), int(K), int(N), int(r), struct.unpack("<i", struct.pack("<f", float(scale)))[0], 0, 0])
+    return torch.tensor(out, dtype=torch.int64).to(device)
+
+
+def lora_max_norm(params, table, max_r: int, max_norm: float, stats, counters=None) -> None:
+    """Per layer of `table` (max_norm_table): stats[l] = (‖scale·up·down‖_F before, factor applied), and the factors of a layer
+    above `max_norm` scaled by sqrt(max_norm/norm) in place; math.inf measures only (include/lora_hip.h: lora_max_norm)."""
+    _require_device(params, table, stats, counters)
+    n_layers = table.shape[0]
+    if params.dtype != torch.float32 or not params.is_contiguous():
+        raise ValueError("lora_max_norm: `params` must be a contiguous fp32 tensor")
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
+        raise ValueError("lora_max_norm: `table` must be a contiguous int64 [n_layers, 8] tensor")
+    if stats.dtype != torch.float32 or stats.numel() != 2 * n_layers or not stats.is_contiguous():
+        raise ValueError("lora_max_norm: `stats` must be a contiguous fp32 tensor of 2 values per layer")
+    if counters is not None and (counters.dtype != torch.int32 or counters.numel() < 1):
+        raise ValueError("lora_max_norm: `counters` must be an int32 tensor")
+    _check(lib().lora_max_norm(_ptr(params), _ptr(table), n_layers, int(max_r), float(max_norm), _ptr(stats), _ptr(counters),
+                               _stream(params)), "lora_max_norm")
 
 
 def ddpm_add_noise(x0, eps, t, sqrt_acp, sqrt_1macp, out_dtype: torch.dtype, v_prediction: bool, want_target=True):

@@ -19,6 +19,7 @@ from .formats import (
     save_lora_weight,
     save_safeloras_with_embeds,
 )
+from .max_norm import clamp_lora_norms_, lora_weight_norms  # noqa: F401  (inspection on the device, next to inspect_lora)
 
 
 def monkeypatch_or_replace_safeloras(models, safeloras):

@@ -249,6 +249,18 @@ def check_prodigy(optimizer, d0=1e-6, d_coef=1.0, growth_rate=math.inf, use_bias
     return math.sqrt(_f32(betas[1])) if 0.0 <= _f32(betas[1]) < 1.0 else None
 
 
+def check_max_weight_norm(max_weight_norm):
+    """`LoraTrainer`'s rule for `max_weight_norm`, on the host, before anything is built: None (no constraint) or a positive
+    finite number that is still positive and finite as the fp32 value the kernel receives.  Returns it as a float, or None."""
+    if max_weight_norm is None:
+        return None
+    v = max_weight_norm
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not v > 0.0 \
+            or not (math.isfinite(_f32(v)) and _f32(v) > 0.0):
+        raise ValueError(f"max_weight_norm must be a positive finite number (None: no constraint); got {max_weight_norm!r}")
+    return float(v)
+
+
 # -- checkpoints: what the two trainers share of validating one before anything is written ---------------------------------
 CHECKPOINT_VERSION = 1
 
@@ -336,8 +348,8 @@ def check_checkpoint_counters(meta, names):
 
 def warn_config_differences(owner: str, saved, own):
     """Constructor arguments are the caller's and are not restored: one warning lists those the file records differently.  A
-    file from before `zero_terminal_snr` existed was written without it."""
-    saved = {"zero_terminal_snr": False, **(saved or {})}
+    file from before `zero_terminal_snr` or `max_weight_norm` existed was written without it."""
+    saved = {"zero_terminal_snr": False, "max_weight_norm": None, **(saved or {})}
     diff =[f"{k}: checkpoint {saved[k]!r}, trainer {own[k]!r}" for k in own if k in (saved or {}) and saved[k] != own[k]]
     if diff:
         warnings.warn(f"{owner}.load_state_dict: the checkpoint was written with other arguments, which are NOT restored — "

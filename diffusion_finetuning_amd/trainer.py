@@ -28,6 +28,7 @@ from . import _native as nat
 from . import step as stp
 from .core import LoraInjectedLinear
 from .formats import load_checkpoint_file, save_checkpoint_file
+from .max_norm import LayerNorms
 
 
 NUM_TRAIN_TIMESTEPS = 1000  # T of the training schedule: the tables' length, and that of a trainer's loss-weight table
@@ -815,7 +816,7 @@ class LoraTrainer:
                  ema_decay: Optional[float] = None, ema_update_after_step: int = 0, optimizer: str = "adamw",
                  prodigy_d0: float = 1e-6, prodigy_d_coef: float = 1.0, prodigy_growth_rate: float = math.inf,
                  prodigy_use_bias_correction: bool = False, prodigy_safeguard_warmup: bool = False,
-                 zero_terminal_snr: bool = False):
+                 zero_terminal_snr: bool = False, max_weight_norm: Optional[float] = None):
         """capture_graph: record add_noise → [text encoder] → UNet forward → loss → backward → factor gradients of a step
         once into a hipGraph and replay it on later steps with the same shapes (inputs are copied into static buffers).
         The gradient exchange and the optimizer stay outside the graph, so no collective is ever captured.  A step with a
@@ -881,7 +882,21 @@ class LoraTrainer:
         `zero_terminal_snr` (an extension beyond the reference, PAPERS.md "Zero terminal SNR"): the noise tables — and the ᾱ the
         Min-SNR weights come from, 0 at T − 1 in the v-form — are those of the schedule rescaled to zero SNR at its last timestep
         (`ddpm_alphas_cumprod(zero_terminal_snr=True)`); needs `v_prediction`.  Only the tables' contents differ: the same
-        kernels read them through the same addresses.  False (default): the trainer as it was."""
+        kernels read them through the same addresses.  False (default): the trainer as it was.
+        `max_weight_norm` (an extension beyond the reference, PAPERS.md "Max-norm constraint"; `--scale_weight_norms` of the kohya
+        trainers): a positive finite bound on ‖scale·up·down‖_F of every LoRA layer of the slab — the UNet's, and the text
+        encoder's when it carries LoRA.  After every OPTIMIZER step (once per accumulation window, on the host-launched and the
+        replayed route alike: the tail is host-launched on both) one launch (lora_max_norm) measures every layer and multiplies
+        both factors of a layer above the bound by sqrt(bound/norm); a layer inside it, the slab's padding and a trainable token
+        table are not written.  It is a projection after the step and the optimizer does not know about it: the Adam moments,
+        Prodigy's s and p0 and the EMA shadow are not rescaled, and the EMA — updated inside the optimizer launch — averages the
+        values BEFORE the projection.  A step the loss scaler skipped projects the already projected values again (no host sync
+        is spent on avoiding it).  Every data-parallel rank applies the same deterministic function to the same parameters: no
+        collective.  The table is built once, here, from the slab's layout and each layer's `scale`: a later `tune_lora_scale` is
+        NOT followed.  `weight_norms()` / `max_norm_stats()` read the last step's norms back (a host read, only when called).  The
+        value is part of a checkpoint's recorded arguments; there is no new tensor.  None (default): no buffer, no other launch,
+        the trainer as it was.  Out of scope: InversionTrainer (it trains no LoRA factors)."""
+        self.max_weight_norm = stp.check_max_weight_norm(max_weight_norm)
         self.zero_terminal_snr = stp.check_zero_terminal_snr(zero_terminal_snr, v_prediction)
         stp.check_ema(ema_decay, ema_update_after_step)
         stp.check_prodigy(optimizer, prodigy_d0, prodigy_d_coef, prodigy_growth_rate, prodigy_use_bias_correction,
@@ -935,6 +950,8 @@ class LoraTrainer:
                                     prodigy_d_coef, prodigy_growth_rate, prodigy_use_bias_correction, prodigy_safeguard_warmup)
         else:
             self.opt = FusedClipAdamW(self.slab, groups, betas, eps, max_grad_norm, ema_decay, ema_update_after_step)
+        self._clamp = LayerNorms.of_slab(self.slab) if self.max_weight_norm is not None else None
+        self._clamp_ran = False  # True once `_clamp.stats` holds an optimizer step's norms
         self.device = self.slab.params.device
         self.dtype = stp.compute_dtype(unet)
         if self.device.type == "cuda" and getattr(unet, "conv3x3_front", False):
@@ -1169,9 +1186,36 @@ class LoraTrainer:
             self.token_table.collect(self.pg, self.world if self.exchange.active else 1, accumulate=micro > 0)
         self.opt.step(grad_mul=1.0 / (self.world * self.loss_scale), lr_mul=self._scheduled_lr_factor())
         self._watch_overflow()
+        if self._clamp is not None:
+            self._clamp_norms()
         self.slab.repack()  # forwards outside step() (sampling, evaluation, saving merged weights) see the new factors
         if tail is not None:
             tail[-1][1].record()
+
+    # -- max-norm constraint ----------------------------------------------------------------------------------------------
+    def _clamp_norms(self):
+        """The projection of `max_weight_norm`: one launch on the slab, no host sync (the caller re-packs)."""
+        self._clamp.launch(self.max_weight_norm)
+        self._clamp_ran = True
+
+    def weight_norms(self):
+        """(norms, factors), fp32 [n_layers] on the host, in slab order (the UNet's layers, then the text encoder's): per layer
+        ‖scale·up·down‖_F as the last optimizer step's projection found it — BEFORE scaling — and the factor it applied to both
+        LoRA factors (1 where the layer was inside the bound).  Without `max_weight_norm`, or before the first optimizer step,
+        the norms of the slab as it is now, measured on the spot (factors all 1).  Waits for the device; never part of `step()`."""
+        norms = self._clamp
+        if norms is None or not self._clamp_ran:
+            norms = LayerNorms.of_slab(self.slab)
+            norms.launch()
+        stats = norms.stats.cpu()
+        return stats[:, 0].clone(), stats[:, 1].clone()
+
+    def max_norm_stats(self) -> dict:
+        """The three numbers the trainers with `--scale_weight_norms` log, from `weight_norms()`: "keys_scaled" (layers the last
+        step scaled), and "mean_norm" / "max_norm" of the layers' norms AFTER it (norm·factor², in double)."""
+        norms, factors = (x.double() for x in self.weight_norms())
+        after = norms * factors * factors
+        return {"keys_scaled": int((factors != 1.0).sum()), "mean_norm": float(after.mean()), "max_norm": float(after.max())}
 
     def _step_eager(self, latents, noise, timesteps, encoder_hidden_states, input_ids, with_prior_preservation,
                     prior_loss_weight, mask, seed):
@@ -1216,6 +1260,7 @@ class LoraTrainer:
                 "v_prediction": bool(self.v_prediction), "zero_terminal_snr": self.zero_terminal_snr,
                 "compute_dtype": str(self.dtype).replace("torch.", ""),
                 "ema_decay": self.opt.ema_decay, "ema_update_after_step": self.opt.ema_update_after,
+                "max_weight_norm": self.max_weight_norm,
                 **({"optimizer": "prodigy", **{"prodigy_" + k: v for k, v in self.opt.options().items()}}
                    if self.optimizer == "prodigy" else {}),
                 **stp.objective_config(self.snr_gamma, self._timestep_weights_digest, self.noise_offset)}
@@ -1347,6 +1392,7 @@ class LoraTrainer:
         if self._flag_slots is None and self.scaler.initial != 1.0:  # (a trainer built without a loss scale takes one over)
             self._flag_slots = self._new_flag_slots()
         self._micro = 0
+        self._clamp_ran = False  # (the norms of the step before the save are not part of a file: measured on demand)
         s.zero_grad()  # (also forgets the factor-gradient problems a dropped window had deferred)
         s.repack()
 

@@ -443,6 +443,30 @@ int lora_prodigy_apply(float* param, const float* exp_avg, const float* exp_avg_
 int64_t lora_prodigy_workspace_bytes(void);
 
 /*
+ * Max-norm constraint on the learned update of every LoRA layer of the flat slab, one launch for any model.  This entry replaces
+ * no line of the reference, which has no such control: the rule is restated from its published definition ("Max-norm
+ * constraint"; parity with the trainers that call it --scale_weight_norms is unpinned).
+ *   table (device, int64, 8 per layer): {up_off, down_off, K, N, r, scale_bits, 0, 0} — up [N,r] and down [r,K], row-major fp32,
+ *                      at the ELEMENT offsets up_off / down_off from `params` (any 4-byte alignment; the two need not touch);
+ *                      scale_bits = the layer's fp32 `scale`, bit-cast to an integer.
+ *   per layer        : GA = down·downᵀ, GB = upᵀ·up (r×r, accumulated in fp32 in an order fixed by (K, N, r): no atomics, the
+ *                      same bits on every run);  n² = scale²·Σ_ij GA_ij·GB_ij in double = ‖scale·up·down‖_F²;
+ *                      norm = sqrt(max(n², 0));  factor = norm > max_norm ? (float)sqrt((double)max_norm/norm) : 1.0f;
+ *                      factor != 1: every element of up and of down is multiplied by factor (one fp32 multiply each), so the
+ *                      product shrinks by max_norm/norm;  factor == 1: the layer is not written at all.
+ *   stats  (device, [n_layers][2] floats): {(float)norm BEFORE the scaling, factor}.
+ *   counters (device, nullable): counters[0] += the number of layers with factor != 1 (an integer sum).
+ * max_norm = +inf measures only: stats is all that is written.  A layer with up = 0 has norm 0 and factor 1.  `max_r`: the largest
+ * rank in the table, 1..64 (it sizes the launch's LDS); a row with r outside 1..max_r, a size < 1 or a negative offset is left
+ * alone and reports {-1, 1}.  Nothing outside the layers of the table is read or written.
+ * Status, decided before the launch: LORA_E_BADARG for a null params / table / stats, n_layers < 1, max_norm <= 0 or NaN;
+ * LORA_E_RANK for max_r outside 1..64.
+ */
+int lora_max_norm(float* params, const int64_t* table, int n_layers, int max_r, float max_norm,
+                  float* stats /* [n_layers][2]: norm before, factor applied */,
+                  int* counters /* nullable: [0] += layers scaled */, void* stream);
+
+/*
  * Step prologue — training_scripts/train_lora_dreambooth.py:824-853 (add_noise / target selection)
  * with the DDPM definitions (diffusers DDPMScheduler, not vendored in the reference):
  *     noisy  = sqrt_acp[t_b]·x0 + sqrt_1macp[t_b]·eps
