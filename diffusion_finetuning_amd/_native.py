@@ -155,6 +155,8 @@ SIGNATURES = {
     "conv3x3_large_plan": (_i32, [_i64, _i32, _i32, _i32]),
     "conv3x3_large_plan_channels": (_i32, [_i32, _i32, _i32]),
     "conv3x3_large": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "conv3x3_large_tile_choice": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "conv3x3_large_tile": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "add_layer_norm_max_channels": (_i32, []),
     "add_layer_norm_fwd": (_i32, [_vp] * 8 + [_i64, _i32, _f32, _i32, _vp]),
     "add_layer_norm_bwd": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _vp]),
@@ -1646,6 +1648,24 @@ def conv3x3_large(x, pack, bias, Cout: int):
     y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
     _check(lib().conv3x3_large(_ptr(x), _ptr(pack), _ptr(bias), _ptr(y), None, 0, N, Cin, Cout, H, W, dtype_code(x.dtype),
                                _stream(x)), "conv3x3_large")
+    return y
+
+
+def conv3x3_large_tile_choice(N: int, Cin: int, Cout: int, H: int, W: int, dtype) -> int:
+    """The tile conv3x3_large runs this shape on (0: the shape rule's, 1: 256 × 80, 2: 128 × 80; -1: not covered).  No launch."""
+    if dtype not in (torch.float16, torch.bfloat16):
+        return -1
+    return int(lib().conv3x3_large_tile_choice(N, Cin, Cout, H, W, dtype_code(dtype)))
+
+
+def conv3x3_large_tile(x, pack, bias, Cout: int, tile: int):
+    """conv3x3_large on a named tile (0: the shape rule's, 1: 256 pixels × 80 channels, 2: 128 × 80); raises where the tile's
+    conditions fail.  For tools/conv_large_sweep.py and the tests."""
+    _require_device(x, pack, bias)
+    N, Cin, H, W = x.shape
+    y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
+    _check(lib().conv3x3_large_tile(_ptr(x), _ptr(pack), _ptr(bias), _ptr(y), None, 0, N, Cin, Cout, H, W, dtype_code(x.dtype),
+                                    int(tile), _stream(x)), "conv3x3_large_tile")
     return y
 
 

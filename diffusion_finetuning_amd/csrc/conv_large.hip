@@ -16,6 +16,10 @@
 //     zero selected at the LDS write), but a thread's unit of work is (position, 8 channels), so the 1056 units of a 128-pixel
 //     tile of a 64-wide image cost 512 threads three units each, and the area is sized to the tile.  Two activation buffers:
 //     the next chunk is written while the current one is multiplied, one barrier per three taps.
+//   - pixel-heavy tiles (256 or 128 pixels x 80 channels, MT / 32 x 1 waves) for the classes a sweep showed faster on them
+//     (measured_tile): a staged position serves nine taps, a weight fragment one, so per chunk a tile pulls about MT * 66 bytes of
+//     activations and 80 * WN * 9 * 64 bytes of weights, and 256 x 80 moves 80 KB where 128 x 160 moves 109 KB for the same
+//     FLOPs.  They stage whole image rows with 16-byte loads (the rows form, at the kernel): 4 loads a thread and chunk for 24.
 // Grid: pixel tiles fastest inside a channel tile, contiguous runs per XCD, so the tiles that share weights share an L2.
 #include <atomic>
 
@@ -23,12 +27,15 @@
 
 namespace {
 
-constexpr int kNTL = 160;                 // output channels per workgroup: 2 waves x 5 fragments of 16
-constexpr int kFragsN = kNTL / 16;        // 10
-constexpr int kGroupFrags = 3 * kFragsN;  // weight fragments of one step (three taps)
-constexpr int kWBuf = kGroupFrags * 1024; // bytes of one weight buffer
+constexpr int kNTL = 160;                 // output channels per workgroup of the channel-heavy tiles: 2 waves x 5 fragments of 16
+constexpr int kWaveFragsN = 5;            // 16-channel fragments of a wave: a workgroup has WN waves along the channels
 constexpr int kWBufs = 3;                 // weight buffers: step g uses buffer g % 3, i.e. its tap row
-constexpr int kPieceSlots = 32;           // LDS-DMA requests per workgroup and step (>= 30 fragments), an equal share a wave
+// per WN: fragments of one tap, of one step (three taps), bytes of one weight buffer, and the LDS-DMA requests per workgroup and
+// step (>= the step's fragments; 32 for 30, 16 for 15), an equal share a wave
+constexpr int frags_n(int WN) { return kWaveFragsN * WN; }
+constexpr int group_frags(int WN) { return 3 * frags_n(WN); }
+constexpr int wbuf_bytes(int WN) { return group_frags(WN) * 1024; }
+constexpr int piece_slots(int WN) { return 16 * WN; }
 
 // every wave's LDS reads and writes of the step are through, and all but its youngest N vector-memory operations have landed
 template <int N> __device__ __forceinline__ void wait_barrier() {
@@ -40,19 +47,28 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned char* lds_wave
                                      (__attribute__((address_space(3))) void*)(lds_wave_base), 16, 0, 0);
 }
 
-// MT pixels per workgroup on WM x 2 waves; PER staging units (one position, 8 channels) a thread handles per chunk:
-// threads * PER >= 4 * positions.
-template <typename T, int MT, int PER, int WM>
-__global__ __launch_bounds__(WM * 128) void conv_large_kernel(const T* __restrict__ x, const T* __restrict__ wp,
-                                                              const T* __restrict__ bias, T* __restrict__ y, int Cin, int Cout,
-                                                              int H, int W, int M, int mtiles, int chunks, int Pcap) {
+// MT pixels per workgroup on WM x WN waves, 80 * WN output channels.
+// ROWS = false: PER staging units (one position, 8 channels) a thread handles per chunk: threads * PER >= 4 * positions.
+// ROWS = true (W % 8 == 0, MT % W == 0, H*W % MT == 0, 2 * W <= MT: a tile is MT / W whole rows of one image): a unit is (staged
+// row, channel pair, 8-pixel segment), two unconditional 16-byte loads and eight ds_write_b32; PER = 2 units a thread cover the
+// 16 * (W / 8) * (MT / W + 2) = 2 * MT + 4 * W units of a chunk.  Lane -> unit: the low bit is the segment's low bit (where W / 8 is
+// even: two lanes load 32 consecutive bytes), the next four the channel pair, the rest the remaining segment bits and then the
+// row.  A ds_write_b32 is served in two groups of 32 lanes on 32 banks: a group is 16 channel pairs (16 consecutive dwords) x 2
+// positions that lie 8 pixels (160 dwords = bank + 0) or a row (20 * (W + 2) dwords = bank + 8 at W = 8, 16, 32, 64) apart:
+// two-way, which a ds_write_b32 hides behind its operand transfer.  The two padding columns of each staged row are zeroed once.
+template <typename T, int MT, int PER, int WM, int WN = 2, bool ROWS = false>
+__global__ __launch_bounds__(WM * WN * 64) void conv_large_kernel(const T* __restrict__ x, const T* __restrict__ wp,
+                                                                  const T* __restrict__ bias, T* __restrict__ y, int Cin, int Cout,
+                                                                  int H, int W, int M, int mtiles, int chunks, int Pcap) {
     using Frag = typename Mfma<T>::Frag;
-    constexpr int NTHR = WM * 128, NW = WM * 2, kPieces = kPieceSlots / NW;
+    constexpr int kFragsN = frags_n(WN), kGroupFrags = group_frags(WN), kWBuf = wbuf_bytes(WN);
+    constexpr int NTHR = WM * WN * 64, NW = WM * WN, kPieces = piece_slots(WN) / NW;
     constexpr int MF = MT / (16 * WM);  // 16-pixel fragments per wave (WM waves along the pixels)
-    constexpr int NF = kFragsN / 2;
+    constexpr int NF = kWaveFragsN;
+    constexpr int kLoads = ROWS ? 2 * PER : 8 * PER;  // activation loads a thread issues per chunk
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* const wlds = smem;                     // kWBufs x kWBuf
-    unsigned char* const alds = smem + kWBufs * kWBuf;    // 2 x Pcap positions, then 16 bytes per thread that nobody reads
+    unsigned char* const alds = smem + kWBufs * kWBuf;    // 2 x Pcap positions, then (not ROWS) 16 bytes per thread that nobody reads
     const int abytes = Pcap * kPitch;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave % WM, wn = wave / WM;
 
@@ -75,35 +91,86 @@ __global__ __launch_bounds__(WM * 128) void conv_large_kernel(const T* __restric
     int xoff[PER];  // element offset of the unit's first channel in x (chunk 0); -1: border (zero) or no unit
     int aoff[PER];  // its LDS byte offset; no unit: this thread's 16 bytes of the dump area behind the buffers (a store under
                     // a condition would let the compiler sink the unit's loads to the store, behind the barriers they must precede)
-#pragma unroll
-    for (int s = 0; s < PER; ++s) {
-        const int i = tid + s * NTHR, cg = fast_div(i, P, inv_p), p = i - cg * P;
-        const bool unit = cg < 4;
-        const int q = qlo + p, img = fast_div(q, PP, inv_pp), r = q - img * PP, hp = fast_div(r, W2, inv_w2), wq = r - hp * W2;
-        const bool inside = unit && hp >= 1 && hp <= H && wq >= 1 && wq <= W;
-        xoff[s] = inside ? (img * Cin + cg * 8) * HW + (hp - 1) * W + (wq - 1) : -1;
-        aoff[s] = unit ? p * kPitch + cg * 16 : 2 * abytes + tid * 16;  // (tid < NTHR)
-    }
-    T raw[PER][8];
-    auto load_stage = [&](int cc) {
-        const T* base = x + (size_t)cc * kChunk * HW;
+    // ROWS: xoff is the first channel's element offset of the unit's segment (a halo row outside the image: the nearest row inside,
+    // cleared by `keep` at the LDS write), aoff the LDS byte offset of its first pixel's dword; a thread past the last unit
+    // repeats its first unit, load and write: the same bytes to the same place, and no dump area
+    unsigned keep[PER];
+    if constexpr (ROWS) {
+        const int S = W >> 3, lb = (S & 1) ^ 1, S2 = S >> lb, rows = MT / W + 2;
+        const int img = fast_div(m0, HW, 1.f / (float)HW), h0 = (m0 - img * HW) / W;
+        const float inv_s2 = 1.f / (float)S2;
 #pragma unroll
         for (int s = 0; s < PER; ++s) {
-            // every lane loads (a border lane from offset 0, which is inside x): a conditional load makes a branch per element
-            const int o = xoff[s] >= 0 ? xoff[s] : 0;
+            const int i = tid + s * NTHR, cp = (i >> lb) & 15, rest = i >> (4 + lb);
+            const int sr = fast_div(rest, S2, inv_s2), seg = (i & lb) + ((rest - sr * S2) << lb);
+            const int hr = h0 - 1 + sr, hc = min(max(hr, 0), H - 1);
+            const bool unit = s == 0 || sr < rows;  // (unit 0 exists for every thread: 2 * MT threads)
+            xoff[s] = unit ? (img * Cin + 2 * cp) * HW + hc * W + 8 * seg : xoff[0];
+            aoff[s] = unit ? (sr * W2 + 1 + 8 * seg) * kPitch + cp * 4 : aoff[0];
+            keep[s] = unit ? (hr == hc ? 0xffffffffu : 0u) : keep[0];
+        }
+    } else {
 #pragma unroll
-            for (int c = 0; c < 8; ++c) raw[s][c] = base[o + c * HW];
+        for (int s = 0; s < PER; ++s) {
+            const int i = tid + s * NTHR, cg = fast_div(i, P, inv_p), p = i - cg * P;
+            const bool unit = cg < 4;
+            const int q = qlo + p, img = fast_div(q, PP, inv_pp), r = q - img * PP, hp = fast_div(r, W2, inv_w2), wq = r - hp * W2;
+            const bool inside = unit && hp >= 1 && hp <= H && wq >= 1 && wq <= W;
+            xoff[s] = inside ? (img * Cin + cg * 8) * HW + (hp - 1) * W + (wq - 1) : -1;
+            aoff[s] = unit ? p * kPitch + cg * 16 : 2 * abytes + tid * 16;  // (tid < NTHR)
+        }
+    }
+    T raw[ROWS ? 1 : PER][8];
+    uint4 rawr[ROWS ? PER : 1][2];  // ROWS: eight pixels of the unit's two channels
+    auto load_stage = [&](int cc) {
+        const T* base = x + (size_t)cc * kChunk * HW;
+        if constexpr (ROWS) {
+#pragma unroll
+            for (int s = 0; s < PER; ++s) {
+                rawr[s][0] = *reinterpret_cast<const uint4*>(base + xoff[s]);
+                rawr[s][1] = *reinterpret_cast<const uint4*>(base + xoff[s] + HW);
+            }
+        } else {
+#pragma unroll
+            for (int s = 0; s < PER; ++s) {
+                // every lane loads (a border lane from offset 0, which is inside x): a conditional load makes a branch per element
+                const int o = xoff[s] >= 0 ? xoff[s] : 0;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) raw[s][c] = base[o + c * HW];
+            }
         }
     };
     auto write_stage = [&](int buf) {
+        if constexpr (ROWS) {
 #pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            Frag v;
+            for (int s = 0; s < PER; ++s) {
+                unsigned char* dst = alds + buf * abytes + aoff[s];
+                const unsigned a[4] = {rawr[s][0].x, rawr[s][0].y, rawr[s][0].z, rawr[s][0].w};
+                const unsigned b[4] = {rawr[s][1].x, rawr[s][1].y, rawr[s][1].z, rawr[s][1].w};
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = xoff[s] >= 0 ? raw[s][j] : static_cast<T>(0.f);
-            *reinterpret_cast<Frag*>(alds + (aoff[s] < 2 * abytes ? buf * abytes : 0) + aoff[s]) = v;
+                for (int k = 0; k < 4; ++k) {  // dword k of a load: pixels 2k (low half) and 2k + 1 of one channel
+                    const unsigned ak = a[k] & keep[s], bk = b[k] & keep[s];
+                    *reinterpret_cast<unsigned*>(dst + (2 * k) * kPitch) = (ak & 0xffffu) | (bk << 16);
+                    *reinterpret_cast<unsigned*>(dst + (2 * k + 1) * kPitch) = (ak >> 16) | (bk & 0xffff0000u);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int s = 0; s < PER; ++s) {
+                Frag v;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = xoff[s] >= 0 ? raw[s][j] : static_cast<T>(0.f);
+                *reinterpret_cast<Frag*>(alds + (aoff[s] < 2 * abytes ? buf * abytes : 0) + aoff[s]) = v;
+            }
         }
     };
+    if constexpr (ROWS) {  // the padding columns of every staged row, both buffers: written here and by nobody else
+        const int rows = MT / W + 2;
+        for (int i = tid; i < rows * 16; i += NTHR) {
+            const int sr = i >> 4, b = (i >> 3) & 1, col = (i >> 2) & 1, piece = i & 3;
+            *reinterpret_cast<uint4*>(alds + b * abytes + (sr * W2 + (col ? W + 1 : 0)) * kPitch + piece * 16) = uint4{0u, 0u, 0u, 0u};
+        }
+    }
 
     // LDS byte address of tap (0,0) of this lane's pixel in each of the wave's fragments; pixels past M repeat the last one
     int lpos[MF];
@@ -141,16 +208,22 @@ __global__ __launch_bounds__(WM * 128) void conv_large_kernel(const T* __restric
         for (int g = 0; g < NF; ++g) acc[f][g] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // Vector-memory operations of a wave, in issue order: step g issues the kPieces requests of step g + 2 and, in the first
-    // step of a chunk, the 8 * PER activation loads of the next chunk.  The barrier that opens step g needs the requests of
+    // step of a chunk, the kLoads activation loads of the next chunk.  The barrier that opens step g needs the requests of
     // step g, issued during step g - 2, to have landed: all but the operations of step g - 1 (the counter retires in order).
-    // The source cannot enforce that count; it was read off the ISA of all six instantiations, and a compiler upgrade wants the
+    // The source cannot enforce that count; it was read off the ISA of all ten instantiations, and a compiler upgrade wants the
     // same reading (hipcc -S --cuda-device-only, the loop between the three s_barrier):
-    //   - between two s_barrier there are exactly kPieces global_load_lds_dwordx4, plus 8 * PER global_load_ushort after the
-    //     barrier of tap row 0 and none elsewhere (an earlier form lost eight of them to a conditional block behind a barrier);
-    //   - the s_waitcnt in front of the three s_barrier read vmcnt(kPieces), vmcnt(kPieces + 8 * PER), vmcnt(kPieces);
-    //   - any s_waitcnt vmcnt the compiler adds is stricter (it adds vmcnt(0) where the staged registers are first used);
+    //   - between two s_barrier there are exactly kPieces global_load_lds_dwordx4, plus kLoads activation loads (8 * PER
+    //     global_load_ushort; rows form: 2 * PER = 4 global_load_dwordx4) after the barrier of tap row 0 and none elsewhere (an
+    //     earlier form lost eight of them to a conditional block behind a barrier);
+    //   - the s_waitcnt in front of the three s_barrier read vmcnt(kPieces), vmcnt(kPieces + kLoads), vmcnt(kPieces): 4, 28, 4
+    //     (128 x 160), 8, 32, 8 and 8, 56, 8 (64 x 160), 2, 6, 2 (256 x 80), 4, 8, 4 (128 x 80);
+    //   - any s_waitcnt vmcnt the compiler adds is stricter: in every instantiation it adds one vmcnt(0), where the staged
+    //     registers are first used, and has hoisted that use (the selects, or the rows form's AND and pack) in front of the third
+    //     barrier's own wait.  It so sits behind the MFMAs of tap row 1 and in front of tap row 2's requests, and drains the
+    //     requests of tap row 1, one step old, a step early; moving the LDS scatter moves that wait to the same distance from
+    //     another step's requests, so it stays where the channel-heavy tiles have it;
     //   - no buffer_ / flat_ / scratch_ operation and no other global load sits inside the loop.
-    static_assert(kPieces + 8 * PER <= 63, "vmcnt is a 6-bit counter");
+    static_assert(kPieces + kLoads <= 63, "vmcnt is a 6-bit counter");
     constexpr int kP1 = (kPieces * 3 + 7) / 8 + (kPieces < 8), kP2 = kP1 + (kPieces - kP1 + 1) / 2;  // 8: 3, 6; 4: 3, 4
     const int steps = chunks * 3;
     load_stage(c0);
@@ -164,7 +237,7 @@ __global__ __launch_bounds__(WM * 128) void conv_large_kernel(const T* __restric
             const int st = cc * 3 + r, ahead = min(st + 2, steps - 1), aslot = (r + 2) % 3;
             // every wave is through step st - 1: the weight buffer that step read and the other activation buffer are free,
             // and this step's weights and activation are in place
-            if (r == 1) wait_barrier<kPieces + 8 * PER>();
+            if (r == 1) wait_barrier<kPieces + kLoads>();
             else wait_barrier<kPieces>();
             if (r == 2) write_stage((cc + 1) & 1);  // loaded two steps ago; read from the barrier of the next chunk on
             load_w(ahead, aslot, 0, kP1);  // (past the last step: the last step's again, into a free buffer, never read)
@@ -207,7 +280,7 @@ __global__ __launch_bounds__(WM * 128) void conv_large_kernel(const T* __restric
     struct alignas(8) Out4 { T v[4]; };
 #pragma unroll
     for (int g = 0; g < NF; ++g) {
-        const int k = nt * kNTL + (wn * NF + g) * 16 + (lane & 15);
+        const int k = nt * (kFragsN * 16) + (wn * NF + g) * 16 + (lane & 15);
         if (k >= Cout) continue;
         const float b = bias ? to_f32(bias[k]) : 0.f;
 #pragma unroll
@@ -235,8 +308,43 @@ __global__ __launch_bounds__(WM * 128) void conv_large_kernel(const T* __restric
 
 struct LGeo {
     int MT = 0, per = 0, mtiles = 0, ntiles = 0, chunks = 0, Pcap = 0, M = 0;
+    int tile = 0;  // 0: a channel-heavy tile of the shape rule (MT x 160); kTile256 / kTile128: a pixel-heavy rows-form tile
     bool ok = false;
 };
+
+// the pixel-heavy tiles (MT x 80 channels on MT / 32 x 1 waves, rows-form staging), named by conv3x3_large_tile
+constexpr int kTile256 = 1, kTile128 = 2;
+constexpr int kRowsPer = 2;                // units (two loads each) a thread stages per chunk
+constexpr int kLdsBytes = 160 * 1024;
+
+// Geometry of a rows-form tile, or !ok where its conditions fail: whole rows (W % 8 == 0 for the 16-byte loads, MT % W == 0)
+// inside one image (H*W % MT == 0), at most MT / 2 pixels a row (two units a thread), the staging area within a CU's LDS.
+LGeo rows_geo(int tile, int N, int Cin, int Cout, int H, int W) {
+    LGeo g;
+    if ((tile != kTile256 && tile != kTile128) || !conv_shape_in_range(N, Cin, Cout, H, W)) return g;
+    const int MT = tile == kTile256 ? 256 : 128, HW = H * W;
+    if (W % 8 || MT % W || HW % MT || 2 * W > MT) return g;
+    g.MT = MT, g.per = kRowsPer, g.tile = tile, g.M = N * HW, g.mtiles = g.M / MT, g.ntiles = (Cout + 79) / 80;
+    g.chunks = Cin / kChunk, g.Pcap = (MT / W + 2) * (W + 2);
+    g.ok = (int64_t)g.mtiles * g.ntiles <= (1 << 20) && kWBufs * wbuf_bytes(1) + 2 * g.Pcap * kPitch <= kLdsBytes;
+    return g;
+}
+
+// The classes profiles/r17_conv_large_tiles_sweep.log shows faster on a pixel-heavy tile than on the shape rule's tile in BOTH
+// directions, by more than the spread of the class's replays (tools/conv_large_sweep.py): the tile, or 0 for every other shape.
+// The backward of C_in -> C_out is the class C_out -> C_in, so the table is symmetric.  At 4096 pixels (32x32) 128 x 80 won for
+// 640 <-> {320, 640, 960, 1280, 1920} and 256 x 80 for 1280 <-> 1280; at 16384 pixels (64x64) 256 x 80 won for 320 <-> {320, 960}
+// and 640 <-> 640; 320 <-> 640 at 16384 pixels did not clear its spread and keeps the shape rule's tile.
+int measured_tile(int64_t pixels, int C_in, int C_out) {
+    const int lo = C_in < C_out ? C_in : C_out, hi = C_in < C_out ? C_out : C_in;
+    if (pixels == 4096) {
+        if (lo == 1280 && hi == 1280) return kTile256;
+        if ((lo == 320 && hi == 640) || (lo == 640 && (hi == 640 || hi == 960 || hi == 1280 || hi == 1920))) return kTile128;
+    } else if (pixels == 16384) {
+        if ((lo == 320 && (hi == 320 || hi == 960)) || (lo == 640 && hi == 640)) return kTile256;
+    }
+    return 0;
+}
 
 // the instantiations of run_large: pixels per tile, staging units per thread, waves along the pixels
 constexpr int kVariants = 3;
@@ -259,9 +367,9 @@ int max_positions(int MT, int M, int H, int W) {
     return pmax;
 }
 
-// Tiling of one call: a function of the shape alone.  128-pixel tiles where they fill the 256 CUs at least once and fit their
-// staging area; else 64-pixel tiles (three units a thread, or six for long rows).
-LGeo large_geo(int N, int Cin, int Cout, int H, int W) {
+// The shape rule: 128-pixel tiles where they fill the 256 CUs at least once and fit their staging area; else 64-pixel tiles (three
+// units a thread, or six for long rows).
+LGeo shape_geo(int N, int Cin, int Cout, int H, int W) {
     LGeo g;
     if (!conv_shape_in_range(N, Cin, Cout, H, W)) return g;
     const int M = N * H * W, ntiles = (Cout + kNTL - 1) / kNTL;
@@ -279,17 +387,30 @@ LGeo large_geo(int N, int Cin, int Cout, int H, int W) {
     return g;
 }
 
-template <typename T, int MT, int PER, int WM>
+// Tiling of one call: a function of the shape alone.  A measured class runs on its pixel-heavy tile, everything else by the
+// shape rule.
+LGeo large_geo(int N, int Cin, int Cout, int H, int W) {
+    // (the sweep's classes are batch 4 of square images: 4096 pixels of 32x32, 16384 of 64x64; no other geometry was measured)
+    const int tile = N == 4 && H == W && (H == 32 || H == 64) ? measured_tile((int64_t)N * H * W, Cin, Cout) : 0;
+    if (tile) {
+        const LGeo g = rows_geo(tile, N, Cin, Cout, H, W);
+        if (g.ok) return g;
+    }
+    return shape_geo(N, Cin, Cout, H, W);
+}
+
+template <typename T, int MT, int PER, int WM, int WN = 2, bool ROWS = false>
 bool launch_large(const T* x, const T* wp, const T* bias, T* y, int Cin, int Cout, int H, int W, const LGeo& g, hipStream_t s) {
-    const int lds = kWBufs * kWBuf + 2 * g.Pcap * kPitch + WM * 128 * 16;  // weights, activation x 2, dump area
-    auto kern = conv_large_kernel<T, MT, PER, WM>;
+    // weights, activation x 2, dump area (the rows form has none)
+    const int lds = kWBufs * wbuf_bytes(WN) + 2 * g.Pcap * kPitch + (ROWS ? 0 : WM * WN * 64 * 16);
+    auto kern = conv_large_kernel<T, MT, PER, WM, WN, ROWS>;
     static std::atomic<int> lds_allowed{0};  // per instantiation: the dynamic-LDS limit is raised once, not on every launch
     if (lds > lds_allowed.load(std::memory_order_relaxed)) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
             return false;
         lds_allowed.store(lds, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(kern, dim3(g.mtiles * g.ntiles), dim3(WM * 128), lds, s, x, wp, bias, y, Cin, Cout, H, W, g.M, g.mtiles,
+    hipLaunchKernelGGL(kern, dim3(g.mtiles * g.ntiles), dim3(WM * WN * 64), lds, s, x, wp, bias, y, Cin, Cout, H, W, g.M, g.mtiles,
                        g.chunks, g.Pcap);
     return true;
 }
@@ -299,7 +420,9 @@ int run_large(const void* x_, const void* wp_, const void* bias_, void* y_, int 
               hipStream_t s) {
     const T *x = static_cast<const T*>(x_), *wp = static_cast<const T*>(wp_), *bias = static_cast<const T*>(bias_);
     T* y = static_cast<T*>(y_);
-    const bool ok = g.MT == 128   ? launch_large<T, 128, 3, 4>(x, wp, bias, y, Cin, Cout, H, W, g, s)
+    const bool ok = g.tile == kTile256 ? launch_large<T, 256, kRowsPer, 8, 1, true>(x, wp, bias, y, Cin, Cout, H, W, g, s)
+                    : g.tile == kTile128 ? launch_large<T, 128, kRowsPer, 4, 1, true>(x, wp, bias, y, Cin, Cout, H, W, g, s)
+                    : g.MT == 128   ? launch_large<T, 128, 3, 4>(x, wp, bias, y, Cin, Cout, H, W, g, s)
                     : g.per == 3 ? launch_large<T, 64, 3, 2>(x, wp, bias, y, Cin, Cout, H, W, g, s)
                                  : launch_large<T, 64, 6, 2>(x, wp, bias, y, Cin, Cout, H, W, g, s);
     if (!ok) return LORA_E_LAUNCH;
@@ -343,15 +466,39 @@ extern "C" int conv3x3_large_plan_channels(int C_in, int C_out, int dtype) {
     return large_plan_channels(C_in, C_out, 0) ? 1 : 0;
 }
 
-extern "C" int conv3x3_large(const void* x, const void* wpack, const void* bias, void* y, void* workspace, int64_t workspace_bytes,
-                             int N, int C_in, int C_out, int H, int W, int dtype, void* stream) {
+// tile < 0: the tiling conv3x3_large chooses; 0: the shape rule's tile; kTile256 / kTile128: that pixel-heavy tile
+static int large_call(const void* x, const void* wpack, const void* bias, void* y, void* workspace, int64_t workspace_bytes, int N,
+                      int C_in, int C_out, int H, int W, int dtype, int tile, void* stream) {
     if (!x || !wpack || !y || N < 1 || C_in < 1 || C_out < 1 || H < 1 || W < 1) return LORA_E_BADARG;
     if (dtype != LORA_F16 && dtype != LORA_BF16) return dtype == LORA_F32 ? LORA_E_UNSUPPORTED : LORA_E_BADARG;
-    const LGeo g = large_geo(N, C_in, C_out, H, W);
+    const LGeo g = tile < 0 ? large_geo(N, C_in, C_out, H, W) : tile == 0 ? shape_geo(N, C_in, C_out, H, W)
+                                                                           : rows_geo(tile, N, C_in, C_out, H, W);
     if (!g.ok) return LORA_E_UNSUPPORTED;
     if (workspace_bytes < 0) return LORA_E_BADARG;  // no split: no workspace is needed, a null one is accepted
     if (!aligned16(x) || !aligned16(wpack) || !aligned16(y) || !aligned16(workspace)) return LORA_E_ALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return dtype == LORA_F16 ? run_large<half_t>(x, wpack, bias, y, C_in, C_out, H, W, g, s)
                              : run_large<bf16_t>(x, wpack, bias, y, C_in, C_out, H, W, g, s);
+}
+
+extern "C" int conv3x3_large(const void* x, const void* wpack, const void* bias, void* y, void* workspace, int64_t workspace_bytes,
+                             int N, int C_in, int C_out, int H, int W, int dtype, void* stream) {
+    return large_call(x, wpack, bias, y, workspace, workspace_bytes, N, C_in, C_out, H, W, dtype, -1, stream);
+}
+
+// The tile conv3x3_large runs a shape on: 0 (the shape rule's), kTile256 or kTile128; -1 where the family does not cover it.
+extern "C" int conv3x3_large_tile_choice(int N, int C_in, int C_out, int H, int W, int dtype) {
+    if (dtype != LORA_F16 && dtype != LORA_BF16) return -1;
+    const LGeo g = large_geo(N, C_in, C_out, H, W);
+    return g.ok ? g.tile : -1;
+}
+
+// conv3x3_large on a named tile, for the sweep and the tests: 0 is the shape rule's channel-heavy tile (whatever the measured
+// table says), 1 is 256 pixels x 80 channels, 2 is 128 pixels x 80 channels, both rows-form.  LORA_E_UNSUPPORTED, and nothing
+// written, where the tile's conditions fail; LORA_E_BADARG for an unknown tile.
+extern "C" int conv3x3_large_tile(const void* x, const void* wpack, const void* bias, void* y, void* workspace,
+                                  int64_t workspace_bytes, int N, int C_in, int C_out, int H, int W, int dtype, int tile,
+                                  void* stream) {
+    if (tile < 0 || tile > kTile128) return LORA_E_BADARG;
+    return large_call(x, wpack, bias, y, workspace, workspace_bytes, N, C_in, C_out, H, W, dtype, tile, stream);
 }

@@ -873,6 +873,15 @@ int conv3x3_large_plan(int64_t pixels, int C_in, int C_out, int dtype);
 int conv3x3_large_plan_channels(int C_in, int C_out, int dtype);
 int conv3x3_large(const void* x, const void* wpack, const void* bias /* nullable */, void* y, void* workspace /* nullable */,
                   int64_t workspace_bytes, int N, int C_in, int C_out, int H, int W, int dtype, void* stream);
+/*
+ * conv3x3_large on a named tile, for the sweep (tools/conv_large_sweep.py) and the tests.  tile 0: the channel-heavy tile the shape
+ * rule gives (MT pixels x 160 channels), whatever the measured table of conv3x3_large says; 1: 256 pixels x 80 channels; 2: 128
+ * pixels x 80 channels.  Tiles 1 and 2 stage whole image rows with 16-byte loads and need W % 8 == 0, MT % W == 0, H*W % MT == 0
+ * and 2*W <= MT: LORA_E_UNSUPPORTED, with nothing launched, otherwise.  LORA_E_BADARG for any other tile.
+ */
+int conv3x3_large_tile_choice(int N, int C_in, int C_out, int H, int W, int dtype); /* the tile conv3x3_large runs; -1: none */
+int conv3x3_large_tile(const void* x, const void* wpack, const void* bias /* nullable */, void* y, void* workspace /* nullable */,
+                       int64_t workspace_bytes, int N, int C_in, int C_out, int H, int W, int dtype, int tile, void* stream);
 
 /*
  * LayerNorm of the transformer blocks with the residual add in front of it folded in (csrc/layer_norm.hip), over rows [M, C]
