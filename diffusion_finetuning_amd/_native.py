@@ -150,7 +150,9 @@ SIGNATURES = {
     "conv3x3_small_plan_channels": (_i32, [_i32, _i32, _i32]),
     "conv3x3_small_pack": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "conv3x3_small": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
-    "conv3x3_large_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "conv3x3_small_form_choice": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "conv3x3_small_form": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "conv3x3_large_supported":(_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "conv3x3_large_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "conv3x3_large_plan": (_i32, [_i64, _i32, _i32, _i32]),
     "conv3x3_large_plan_channels": (_i32, [_i32, _i32, _i32]),
@@ -1622,6 +1624,27 @@ def conv3x3_small(x, pack, bias, Cout: int):
     y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
     _check(lib().conv3x3_small(_ptr(x), _ptr(pack), _ptr(bias), _ptr(y), _ptr(ws), nbytes, N, Cin, Cout, H, W, code, _stream(x)),
            "conv3x3_small")
+    return y
+
+
+def conv3x3_small_form_choice(N: int, Cin: int, Cout: int, H: int, W: int, dtype) -> int:
+    """The staging form conv3x3_small takes for this shape (0: positions, 1: rows; -1: not covered).  No launch."""
+    if dtype not in (torch.float16, torch.bfloat16):
+        return -1
+    return int(lib().conv3x3_small_form_choice(N, Cin, Cout, H, W, dtype_code(dtype)))
+
+
+def conv3x3_small_form(x, pack, bias, Cout: int, form: int):
+    """conv3x3_small with a named staging form (0: positions, 1: rows); raises where the form does not cover the shape.  For
+    tools/conv_small_sweep.py and the tests."""
+    _require_device(x, pack, bias)
+    N, Cin, H, W = x.shape
+    code = dtype_code(x.dtype)
+    nbytes = int(lib().conv3x3_small_workspace_bytes(N, Cin, Cout, H, W, code))
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=x.device)
+    y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
+    _check(lib().conv3x3_small_form(_ptr(x), _ptr(pack), _ptr(bias), _ptr(y), _ptr(ws), nbytes, N, Cin, Cout, H, W, code, int(form),
+                                    _stream(x)), "conv3x3_small_form")
     return y
 
 

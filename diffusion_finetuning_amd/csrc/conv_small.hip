@@ -24,19 +24,34 @@
 //
 // Workgroups that share weights (the pixel tiles of one channel tile and slice) get consecutive places in the XCD remap below,
 // so they run on one XCD and the weights come from HBM once.
+#include <atomic>
+
 #include "conv_common.h"
 
 namespace {
 
 constexpr int kNT = 128;        // output channels per workgroup (2 waves x 4 tiles of 16)
 
-// MT pixels per workgroup; PER positions (all 32 channels of each) a thread stages per chunk: 256*PER >= positions of a tile.
-template <typename T, int MT, int PER>
+// every wave's LDS reads and writes so far are through; vector-memory requests stay in flight across the barrier (a __syncthreads()
+// would drain them all)
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// MT pixels per workgroup, two LDS stage buffers of PER * 256 positions each.
+// RU = 0, the position form: a thread stages PER positions (all 32 channels of each) per chunk with 2-byte loads, 256*PER >=
+// positions of a tile; a thread past the tile's last position writes zeros to a position of its own that nobody reads.
+// RU = 1 or 2, the rows form (rows_units below: W % 8 == 0, a tile is whole rows, MT = 128, PER = 1): a unit is (image row, channel
+// pair, 8-pixel segment), two unconditional 16-byte loads and eight ds_write_b32, RU units a thread; lane -> unit as in
+// conv_large.hip.  The border positions and the halo rows outside the image are zeroed once, in both buffers, and never written
+// again.  A thread without a unit repeats an existing one: the same bytes to the same place.
+template <typename T, int MT, int PER, int RU>
 __global__ __launch_bounds__(kThreads) void conv_small_kernel(const T* __restrict__ x, const T* __restrict__ wp,
                                                               float* __restrict__ part, int Cin, int Cout, int H, int W, int M,
                                                               int mtiles, int ntiles, int cps, int chunks, int Mpad) {
     using Frag = typename Mfma<T>::Frag;
     constexpr int MF = MT / 32;  // 16-pixel fragments per wave (two waves along the pixels)
+    constexpr bool ROWS = RU > 0;
+    constexpr int kBuf = PER * kThreads * kPitch;  // bytes of one stage buffer
+    constexpr int NU = ROWS ? RU : 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
 
@@ -60,30 +75,94 @@ __global__ __launch_bounds__(kThreads) void conv_small_kernel(const T* __restric
     const int qlo = q0 - (W2 + 1);
     const float inv_pp = 1.f / (float)PP, inv_w2 = 1.f / (float)W2;
 
-    // staging plan of this thread, chunk-invariant: positions tid, tid + 256, ... (PER of them), four 8-channel groups of each
-    int xoff[PER];     // element offset of (position, channel 0 of the chunk) in x; -1: border or past the tile (zero / nothing)
-    bool in_tile[PER];
+    // staging plan of this thread, chunk-invariant
+    // position form: positions tid, tid + 256, ... (PER of them), four 8-channel groups of each; xoff is the element offset of
+    // (position, channel 0 of the chunk) in x, -1: border or past the tile (zeros are written)
+    // rows form: xoff is the element offset of the unit's first channel and pixel, aoff the LDS byte offset of that pixel's dword
+    int xoff[ROWS ? NU : PER];
+    int aoff[NU];
+    if constexpr (ROWS) {
+        const int S = W >> 3, lb = (S & 1) ^ 1, S2 = S >> lb;
+        const int img0 = m0 / HW, h0 = (m0 - img0 * HW) / W;
+        const bool whole = MT % HW == 0;  // the tile is whole images (else: MT / W rows of one image and their two halo rows)
+        const int images = min(MT / HW, (M - m0) / HW);
 #pragma unroll
-    for (int s = 0; s < PER; ++s) {
-        const int p = tid + s * kThreads;
-        const int q = qlo + p, img = fast_div(q, PP, inv_pp), r = q - img * PP, hp = fast_div(r, W2, inv_w2), wq = r - hp * W2;
-        in_tile[s] = p < P;
-        const bool inside = in_tile[s] && hp >= 1 && hp <= H && wq >= 1 && wq <= W;
-        xoff[s] = inside ? img * Cin * HW + (hp - 1) * W + (wq - 1) : -1;
-    }
-    // the loaded elements stay as they arrive until they are written to LDS a chunk later; zero selection and packing happen
-    // there, so nothing waits for these loads while the current chunk is multiplied
-    T raw[PER][32];
-    auto load_stage = [&](int cc) {
-        const T* base = x + (size_t)cc * kChunk * HW;
+        for (int s = 0; s < RU; ++s) {
+            const int i = tid + s * kThreads, cp = (i >> lb) & 15, rest = i >> (4 + lb);
+            int k = rest / S2;
+            const int seg = (i & lb) + ((rest - k * S2) << lb);
+            const bool unit = whole ? k < images * H : (k < MT / W + 2 && h0 - 1 + k >= 0 && h0 - 1 + k < H);
+            if (!unit) k = whole ? 0 : 1;  // a row that every tile has
+            const int im = whole ? k / H : 0, hr = whole ? k - im * H : h0 - 1 + k;
+            const int j = whole ? im * (H + 2) + hr + 1 : k;  // staged (padded) row
+            xoff[s] = ((img0 + im) * Cin + 2 * cp) * HW + hr * W + 8 * seg;
+            aoff[s] = (j * W2 + 1 + 8 * seg) * kPitch + cp * 4;
+        }
+    } else {
 #pragma unroll
         for (int s = 0; s < PER; ++s) {
-            // every lane loads (a border lane from offset 0, which is inside x): a conditional load makes a branch per element
-            const int o = xoff[s] >= 0 ? xoff[s] : 0;
+            const int p = tid + s * kThreads;
+            const int q = qlo + p, img = fast_div(q, PP, inv_pp), r = q - img * PP, hp = fast_div(r, W2, inv_w2), wq = r - hp * W2;
+            const bool inside = p < P && hp >= 1 && hp <= H && wq >= 1 && wq <= W;
+            xoff[s] = inside ? img * Cin * HW + (hp - 1) * W + (wq - 1) : -1;
+        }
+    }
+    // the loaded elements stay as they arrive until they are written to LDS at the end of the chunk; zero selection and packing
+    // happen there, so nothing waits for these loads while the current chunk is multiplied
+    T raw[ROWS ? 1 : PER][32];
+    uint4 rawr[NU][2];  // rows form: eight pixels of the unit's two channels
+    auto load_stage = [&](int cc) {
+        const T* base = x + (size_t)cc * kChunk * HW;
+        if constexpr (ROWS) {
 #pragma unroll
-            for (int c = 0; c < 32; ++c) raw[s][c] = base[o + c * HW];
+            for (int s = 0; s < RU; ++s) {
+                rawr[s][0] = *reinterpret_cast<const uint4*>(base + xoff[s]);
+                rawr[s][1] = *reinterpret_cast<const uint4*>(base + xoff[s] + HW);
+            }
+        } else {
+#pragma unroll
+            for (int s = 0; s < PER; ++s) {
+                // every lane loads (a border lane from offset 0, which is inside x): a conditional load makes a branch per element
+                const int o = xoff[s] >= 0 ? xoff[s] : 0;
+#pragma unroll
+                for (int c = 0; c < 32; ++c) raw[s][c] = base[o + c * HW];
+            }
         }
     };
+    // unconditional: a store under a condition puts a branch around the first use of the loaded registers, and the compiler then
+    // drains every request in front of it
+    auto write_stage = [&](int buf) {
+        unsigned char* dstb = smem + buf * kBuf;
+        if constexpr (ROWS) {
+#pragma unroll
+            for (int s = 0; s < RU; ++s) {
+                unsigned char* dst = dstb + aoff[s];
+                const unsigned a[4] = {rawr[s][0].x, rawr[s][0].y, rawr[s][0].z, rawr[s][0].w};
+                const unsigned b[4] = {rawr[s][1].x, rawr[s][1].y, rawr[s][1].z, rawr[s][1].w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {  // dword k of a load: pixels 2k (low half) and 2k + 1 of one channel
+                    *reinterpret_cast<unsigned*>(dst + (2 * k) * kPitch) = (a[k] & 0xffffu) | (b[k] << 16);
+                    *reinterpret_cast<unsigned*>(dst + (2 * k + 1) * kPitch) = (a[k] >> 16) | (b[k] & 0xffff0000u);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int s = 0; s < PER; ++s)
+#pragma unroll
+                for (int c8 = 0; c8 < 4; ++c8) {
+                    Frag v;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = xoff[s] >= 0 ? raw[s][c8 * 8 + j] : static_cast<T>(0.f);
+                    *reinterpret_cast<Frag*>(dstb + (tid + s * kThreads) * kPitch + c8 * 16) = v;
+                }
+        }
+    };
+    if constexpr (ROWS) {  // both buffers: the borders and the halo rows outside the image stay zero, the rest is overwritten
+#pragma unroll
+        for (int i = 0; i < 2 * kBuf / (16 * kThreads); ++i)
+            *reinterpret_cast<uint4*>(smem + (i * kThreads + tid) * 16) = uint4{0u, 0u, 0u, 0u};
+        lds_barrier();
+    }
 
     // LDS byte address of tap (0,0) of this lane's pixel in each of the wave's fragments; pixels past M repeat the last one
     int lpos[MF];
@@ -114,34 +193,36 @@ __global__ __launch_bounds__(kThreads) void conv_small_kernel(const T* __restric
 #pragma unroll
         for (int g = 0; g < 4; ++g) acc[f][g] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+    // Vector-memory requests of a wave, in issue order: the activation loads of a chunk, then the 36 weight requests of the NEXT
+    // use of each tap.  The prologue keeps that order (the sched_barrier), so on every path into the loop the activation loads
+    // are the oldest requests and the compiler can count: the stage write waits for all but the 36 weight requests behind the
+    // loads, tap t's MFMAs for all but what was issued after tap t's request a chunk earlier.  The request count of an
+    // iteration is fixed: past the last chunk the loads repeat the last chunk and the weight requests the last tap.
+    //
+    // Stage buffers: chunk cc is read from buffer cc & 1; at the end of chunk cc the next chunk is written to the other buffer,
+    // then ONE barrier.  That buffer was last read during chunk cc - 1, and every wave has passed the barrier that ended chunk
+    // cc - 1 before any wave writes here: a buffer is rewritten one barrier after its last read, and read one barrier after
+    // its write.
     load_stage(c_begin);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < 9; ++t) load_w(t, c_begin * 9 + t);
+    __builtin_amdgcn_sched_barrier(0);
+    write_stage(c_begin & 1);
+    lds_barrier();
     for (int cc = c_begin; cc < c_end; ++cc) {
-        __syncthreads();  // the previous chunk has been read by every wave
-#pragma unroll
-        for (int s = 0; s < PER; ++s)
-            if (in_tile[s]) {
-#pragma unroll
-                for (int c8 = 0; c8 < 4; ++c8) {
-                    Frag v;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = xoff[s] >= 0 ? raw[s][c8 * 8 + j] : static_cast<T>(0.f);
-                    *reinterpret_cast<Frag*>(smem + (tid + s * kThreads) * kPitch + c8 * 16) = v;
-                }
-            }
-        __syncthreads();
+        const unsigned char* ab = smem + (cc & 1) * kBuf;
         load_stage(min(cc + 1, c_end - 1));
         __builtin_amdgcn_sched_barrier(0);
         Frag xf[2][MF];
 #pragma unroll
-        for (int f = 0; f < MF; ++f) xf[0][f] = *reinterpret_cast<const Frag*>(smem + lpos[f]);
+        for (int f = 0; f < MF; ++f) xf[0][f] = *reinterpret_cast<const Frag*>(ab + lpos[f]);
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             if (t + 1 < 9) {  // the next tap's pixels come out of LDS while this one is multiplied
                 const int sh = (((t + 1) / 3) * W2 + ((t + 1) % 3)) * kPitch;
 #pragma unroll
-                for (int f = 0; f < MF; ++f) xf[(t + 1) & 1][f] = *reinterpret_cast<const Frag*>(smem + lpos[f] + sh);
+                for (int f = 0; f < MF; ++f) xf[(t + 1) & 1][f] = *reinterpret_cast<const Frag*>(ab + lpos[f] + sh);
             }
 #pragma unroll
             for (int f = 0; f < MF; ++f)
@@ -151,6 +232,8 @@ __global__ __launch_bounds__(kThreads) void conv_small_kernel(const T* __restric
             // keeps the request here, a chunk ahead of its use: left alone, the scheduler gathers all nine at the loop's end
             __builtin_amdgcn_sched_barrier(0);
         }
+        write_stage((cc + 1) & 1);  // (past the last chunk: the last chunk again, into the buffer nobody reads any more)
+        lds_barrier();
     }
 
     // partial tile: [slice][channel][pixel], a lane's four registers are four consecutive pixels of one channel
@@ -259,25 +342,45 @@ Geo conv_geo(int N, int Cin, int Cout, int H, int W) {
     return g;
 }
 
-template <typename T, int MT, int PER>
+// the forms of the main kernel's staging, named by conv3x3_small_form
+constexpr int kFormPosition = 0, kFormRows = 1;
+
+// Units a thread stages in the rows form (1 or 2), or 0 where that form does not cover the shape.  It needs 16-byte row segments
+// (W % 8 == 0), the 128-pixel instantiation, and tiles that are whole rows laid out one of two ways: whole images (128 % H*W == 0:
+// 2 * 128 = 256 units, one a thread), or 128 / W rows of one image with their two halo rows (H*W % 128 == 0: 256 + 4 * W units,
+// two a thread).
+int rows_units(const Geo& g, int H, int W) {
+    if (!g.ok || g.MT != 128 || W % 8 || 128 % W) return 0;
+    const int HW = H * W;
+    if (128 % HW == 0) return 1;
+    return HW % 128 == 0 && 256 + 4 * W <= 2 * kThreads ? 2 : 0;
+}
+
+template <typename T, int MT, int PER, int RU>
 bool launch_main(const T* x, const T* wp, float* part, int Cin, int Cout, int H, int W, const Geo& g, hipStream_t s) {
-    const int lds = g.Pcap * kPitch;
-    auto kern = conv_small_kernel<T, MT, PER>;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return false;
+    constexpr int lds = 2 * PER * kThreads * kPitch;  // two stage buffers
+    auto kern = conv_small_kernel<T, MT, PER, RU>;
+    static std::atomic<bool> raised{false};  // per instantiation: the dynamic-LDS limit is raised once, not on every launch
+    if (lds > 48 * 1024 && !raised.load(std::memory_order_relaxed)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+            return false;
+        raised.store(true, std::memory_order_relaxed);
+    }
     hipLaunchKernelGGL(kern, dim3(g.mtiles * g.ntiles * g.S), dim3(kThreads), lds, s, x, wp, part, Cin, Cout, H, W, g.M, g.mtiles,
                        g.ntiles, g.cps, g.chunks, g.Mpad);
     return true;
 }
 
+// ru: units a thread of the rows form (rows_units), 0 for the position form
 template <typename T>
 int run_conv(const void* x_, const void* wp_, const void* bias_, void* y_, void* ws, int Cin, int Cout, int H, int W, const Geo& g,
-             hipStream_t s) {
+             int ru, hipStream_t s) {
     const T *x = static_cast<const T*>(x_), *wp = static_cast<const T*>(wp_), *bias = static_cast<const T*>(bias_);
     float* part = static_cast<float*>(ws);
-    const bool ok = g.MT == 128 ? launch_main<T, 128, 1>(x, wp, part, Cin, Cout, H, W, g, s)
-                                : launch_main<T, 64, 3>(x, wp, part, Cin, Cout, H, W, g, s);
+    const bool ok = ru == 1     ? launch_main<T, 128, 1, 1>(x, wp, part, Cin, Cout, H, W, g, s)
+                    : ru == 2   ? launch_main<T, 128, 1, 2>(x, wp, part, Cin, Cout, H, W, g, s)
+                    : g.MT == 128 ? launch_main<T, 128, 1, 0>(x, wp, part, Cin, Cout, H, W, g, s)
+                                  : launch_main<T, 64, 3, 0>(x, wp, part, Cin, Cout, H, W, g, s);
     if (!ok) return LORA_E_LAUNCH;
     if ((H * W) % 4 == 0) {
         const int total = Cout * (g.M / 4);
@@ -314,6 +417,31 @@ bool plan_channels(int C_in, int C_out, int64_t pixels /* 0: any measured pixel 
     const bool at256 = other == 1280 || other == 2560;
     const bool at1024 = other == 640 || other == 1280 || other == 1920 || other == 2560;
     return pixels == 256 ? at256 : pixels == 1024 ? at1024 : pixels == 0 ? (at256 || at1024) : false;
+}
+
+// The form conv3x3_small stages a shape with: the rows form for the classes profiles/r18_conv_small_pipeline_sweep.log shows
+// faster on it than on the position form in BOTH directions by more than the spread of the replays (batch 4 of the 8x8 and 16x16
+// levels, the planner's classes: no other geometry was measured); the position form for everything else.
+int measured_form(const Geo& g, int N, int Cin, int Cout, int H, int W) {
+    const bool swept = N == 4 && H == W && (H == 8 || H == 16) && plan_channels(Cin, Cout, (int64_t)N * H * W);
+    return swept && rows_units(g, H, W) ? kFormRows : kFormPosition;
+}
+
+// form < 0: the form conv3x3_small chooses
+int small_call(const void* x, const void* wpack, const void* bias, void* y, void* workspace, int64_t workspace_bytes, int N, int C_in,
+               int C_out, int H, int W, int dtype, int form, void* stream) {
+    if (!x || !wpack || !y || !workspace || N < 1 || C_in < 1 || C_out < 1 || H < 1 || W < 1) return LORA_E_BADARG;
+    if (dtype != LORA_F16 && dtype != LORA_BF16) return dtype == LORA_F32 ? LORA_E_UNSUPPORTED : LORA_E_BADARG;
+    const Geo g = conv_geo(N, C_in, C_out, H, W);
+    if (!g.ok) return LORA_E_UNSUPPORTED;
+    if (form < 0) form = measured_form(g, N, C_in, C_out, H, W);
+    const int ru = form == kFormRows ? rows_units(g, H, W) : 0;
+    if (form == kFormRows && !ru) return LORA_E_UNSUPPORTED;
+    if (workspace_bytes < g.ws_bytes) return LORA_E_BADARG;
+    if (!aligned16(x) || !aligned16(wpack) || !aligned16(y) || !aligned16(workspace)) return LORA_E_ALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == LORA_F16 ? run_conv<half_t>(x, wpack, bias, y, workspace, C_in, C_out, H, W, g, ru, s)
+                             : run_conv<bf16_t>(x, wpack, bias, y, workspace, C_in, C_out, H, W, g, ru, s);
 }
 }  // namespace
 
@@ -352,13 +480,22 @@ extern "C" int conv3x3_small_pack(const void* w, void* packed, int C_in, int C_o
 
 extern "C" int conv3x3_small(const void* x, const void* wpack, const void* bias, void* y, void* workspace, int64_t workspace_bytes,
                              int N, int C_in, int C_out, int H, int W, int dtype, void* stream) {
-    if (!x || !wpack || !y || !workspace || N < 1 || C_in < 1 || C_out < 1 || H < 1 || W < 1) return LORA_E_BADARG;
-    if (dtype != LORA_F16 && dtype != LORA_BF16) return dtype == LORA_F32 ? LORA_E_UNSUPPORTED : LORA_E_BADARG;
+    return small_call(x, wpack, bias, y, workspace, workspace_bytes, N, C_in, C_out, H, W, dtype, -1, stream);
+}
+
+// The form conv3x3_small stages a shape with: 0 (position) or 1 (rows); -1 where the family does not cover the shape.
+extern "C" int conv3x3_small_form_choice(int N, int C_in, int C_out, int H, int W, int dtype) {
+    if (dtype != LORA_F16 && dtype != LORA_BF16) return -1;
     const Geo g = conv_geo(N, C_in, C_out, H, W);
-    if (!g.ok) return LORA_E_UNSUPPORTED;
-    if (workspace_bytes < g.ws_bytes) return LORA_E_BADARG;
-    if (!aligned16(x) || !aligned16(wpack) || !aligned16(y) || !aligned16(workspace)) return LORA_E_ALIGN;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == LORA_F16 ? run_conv<half_t>(x, wpack, bias, y, workspace, C_in, C_out, H, W, g, s)
-                             : run_conv<bf16_t>(x, wpack, bias, y, workspace, C_in, C_out, H, W, g, s);
+    return g.ok ? measured_form(g, N, C_in, C_out, H, W) : -1;
+}
+
+// conv3x3_small with a named form of the staging, for the sweep and the tests: 0 stages positions with 2-byte loads (every
+// shape), 1 stages whole rows with 16-byte loads.  LORA_E_UNSUPPORTED, and nothing launched, where the form does not cover the
+// shape; LORA_E_BADARG for an unknown form.  The two forms give the same bits.
+extern "C" int conv3x3_small_form(const void* x, const void* wpack, const void* bias, void* y, void* workspace,
+                                  int64_t workspace_bytes, int N, int C_in, int C_out, int H, int W, int dtype, int form,
+                                  void* stream) {
+    if (form != kFormPosition && form != kFormRows) return LORA_E_BADARG;
+    return small_call(x, wpack, bias, y, workspace, workspace_bytes, N, C_in, C_out, H, W, dtype, form, stream);
 }

@@ -858,6 +858,15 @@ int conv3x3_small_plan_channels(int C_in, int C_out, int dtype);
 int conv3x3_small_pack(const void* w, void* packed, int C_in, int C_out, int backward, int dtype, void* stream);
 int conv3x3_small(const void* x, const void* wpack, const void* bias /* nullable */, void* y, void* workspace,
                   int64_t workspace_bytes, int N, int C_in, int C_out, int H, int W, int dtype, void* stream);
+/*
+ * conv3x3_small with a named form of the activation staging, for the sweep (tools/conv_small_sweep.py) and the tests.  form 0:
+ * positions, 2-byte loads (every supported shape); 1: whole image rows with 16-byte loads, which needs W % 8 == 0, 128-pixel tiles
+ * and 128 % (H*W) == 0 or (H*W) % 128 == 0: LORA_E_UNSUPPORTED, with nothing launched, otherwise.  LORA_E_BADARG for any other
+ * form.  Both forms give the same bits.  conv3x3_small_form_choice: the form conv3x3_small takes for a shape; -1: not covered.
+ */
+int conv3x3_small_form_choice(int N, int C_in, int C_out, int H, int W, int dtype);
+int conv3x3_small_form(const void* x, const void* wpack, const void* bias /* nullable */, void* y, void* workspace,
+                       int64_t workspace_bytes, int N, int C_in, int C_out, int H, int W, int dtype, int form, void* stream);
 
 /*
  * The same convolution, same contract and same packs (conv3x3_small_pack), where the pixels are MANY (csrc/conv_large.hip, the

@@ -9,7 +9,10 @@ weight tensors of the class, about `--weight-mb` MB of them, so that a filter co
 gigabytes pass between two uses of it, and not from the 256 MB Infinity Cache.  The stock side runs as the model pays for it:
 `torch.backends.cudnn.benchmark` on and MIOPEN_USER_DB_PATH on a copy of the shipped find-db, as bench.conv_autotune sets
 them, so its figure covers all of its launches (re-layouts, zero fill, GEMM).  A class belongs in `conv3x3_small_plan` only if
-the HIP kernel wins in BOTH directions; the last column says what the planner does now."""
+the HIP kernel wins in BOTH directions; the `plan` column says what the planner does now.  The HIP side is timed once per
+staging form (`conv3x3_small_form`: positions, and rows where that form covers the shape; a library without that entry is timed
+through `conv3x3_small` alone, which is how a parent commit's tree is measured with this file), each figure with the max − min
+of its replays behind a ±; the `form` column says which one `conv3x3_small` takes now."""
 import argparse
 import faulthandler
 import glob
@@ -63,7 +66,7 @@ def main():
         lines.append(s)
 
     def timed(fn):
-        """µs per call of fn inside a replayed graph of args.calls calls."""
+        """(median, max − min) over the replays of the µs per call of fn inside a replayed graph of args.calls calls."""
         for i in range(2):
             fn(i)
         torch.cuda.synchronize()
@@ -86,7 +89,7 @@ def main():
             e1.synchronize()
             ts.append(e0.elapsed_time(e1) * 1e3 / args.calls)
         ts.sort()
-        return ts[len(ts) // 2]
+        return ts[len(ts) // 2], ts[-1] - ts[0]
 
     cases = set()
     for batch, latent in (tuple(int(v) for v in c.split("x")) for c in args.configs.split(",")):
@@ -96,7 +99,14 @@ def main():
                 cases.add((batch, side, cin, cout))
     say(f"# conv_small sweep: f16, graph of {args.calls} calls over ~{args.weight_mb} MB of distinct filters, median of "
         f"{args.replays} replays, µs per call")
-    say(f"# {'N':>2} {'HxW':>7} {'pixels':>6} {'C_in':>5} {'C_out':>5} | {'fwd stock':>9} {'fwd hip':>8} | {'bwd stock':>9} {'bwd hip':>8} | wins plan")
+    forms = hasattr(nat, "conv3x3_small_form")
+    names = ["position", "rows"] if forms else ["hip"]
+    cols = " | ".join(f"{'fwd ' + n:>14} {'bwd ' + n:>14}" for n in names)
+    say(f"# {'N':>2} {'HxW':>7} {'pixels':>6} {'C_in':>5} {'C_out':>5} | {'fwd stock':>14} {'bwd stock':>14} | {cols} | wins plan form")
+
+    def cell(t):
+        return f"{t[0]:>8.1f} ±{t[1]:>4.1f}" if t else f"{'-':>14}"
+
     for batch, side, cin, cout in sorted(cases, key=lambda c: (c[0] * c[1] * c[1], c[2], c[3], c[0])):
         if not nat.conv3x3_small_supported(batch, cin, cout, side, side, torch.float16):
             continue
@@ -111,12 +121,27 @@ def main():
         t_fs = timed(lambda i: F.conv2d(x, ws[i % nw], None, padding=1))
         t_bs = timed(lambda i: torch.ops.aten.convolution_backward(dy, x, ws[i % nw], None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
                                                                    [True, False, False]))
-        t_fh = timed(lambda i: nat.conv3x3_small(x, fwd[i % nw], None, cout))
-        t_bh = timed(lambda i: nat.conv3x3_small(dy, bwd[i % nw], None, cin))
-        wins = t_fh < t_fs and t_bh < t_bs
+        hip = []  # (fwd, bwd) per column; None where the form does not cover the shape
+        if forms:
+            for form in (0, 1):
+                try:
+                    nat.conv3x3_small_form(x, fwd[0], None, cout, form), nat.conv3x3_small_form(dy, bwd[0], None, cin, form)
+                except RuntimeError:
+                    hip.append((None, None))
+                    continue
+                hip.append((timed(lambda i: nat.conv3x3_small_form(x, fwd[i % nw], None, cout, form)),
+                            timed(lambda i: nat.conv3x3_small_form(dy, bwd[i % nw], None, cin, form))))
+            chosen = nat.conv3x3_small_form_choice(batch, cin, cout, side, side, torch.float16)
+        else:
+            hip.append((timed(lambda i: nat.conv3x3_small(x, fwd[i % nw], None, cout)),
+                        timed(lambda i: nat.conv3x3_small(dy, bwd[i % nw], None, cin))))
+            chosen = 0
+        t_fh, t_bh = hip[chosen]
+        wins = t_fh[0] < t_fs[0] and t_bh[0] < t_bs[0]
         plan = nat.conv3x3_small_plan(batch * side * side, cin, cout, torch.float16)
-        say(f"  {batch:>2} {side:>3}x{side:<3} {batch * side * side:>6} {cin:>5} {cout:>5} | {t_fs:>9.1f} {t_fh:>8.1f} | {t_bs:>9.1f} {t_bh:>8.1f} | "
-            f"{'yes' if wins else 'no':>4} {'hip' if plan else 'stock'}")
+        say(f"  {batch:>2} {side:>3}x{side:<3} {batch * side * side:>6} {cin:>5} {cout:>5} | {cell(t_fs)} {cell(t_bs)} | "
+            + " | ".join(f"{cell(f)} {cell(b)}" for f, b in hip)
+            + f" | {'yes' if wins else 'no':>4} {'hip' if plan else 'stock':>5} {names[chosen]}")
         del x, dy, ws, fwd, bwd
     if args.out:
         with open(args.out, "w") as f:
