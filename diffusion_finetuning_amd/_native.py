@@ -992,22 +992,46 @@ class SampleState:
         self.init, self.mask, self.keep_coef = init, mask, keep_coef
         self.hw = None if mask is None else mask[0].numel()
 
+    # What a subclass changes: the dtype of t_model / timesteps, the width of a coef row, what the dtype error says, and the
+    # buffers it adds (_HistoryState below).
+    T_DTYPE, COEF_WIDTH = torch.int64, 3
+    KINDS = "x fp32, t_model / timesteps int64, cursor int32 [2], coef fp32 [S, 3]"
+    _own = ()
+
+    def _own_shapes_ok(self, x) -> bool:
+        return True
+
+    def _own_kinds_ok(self, S, timesteps) -> bool:
+        return True
+
+    def _own_shapes(self) -> str:
+        return ""
+
     def __init__(self, x, model_in, t_model, cursor, timesteps, coef, cfg: bool, init=None, mask=None, keep_coef=None):
-        B, rows = x.shape[0], model_in.shape[0]
-        if rows != (2 * B if cfg else B) or model_in.shape[1:] != x.shape[1:] or t_model.shape != (rows,):
-            raise ValueError(f"sampler buffers disagree: state {tuple(x.shape)}, model input {tuple(model_in.shape)}, "
-                             f"timesteps {tuple(t_model.shape)}, guidance {cfg}")
-        S = timesteps.shape[0]
-        if (x.dtype != torch.float32 or t_model.dtype != torch.int64 or cursor.dtype != torch.int32 or cursor.numel() != 2 or
-                timesteps.dtype != torch.int64 or coef.dtype != torch.float32 or tuple(coef.shape) != (S, 3) or S < 1):
-            raise ValueError("sampler buffers: x fp32, t_model / timesteps int64, cursor int32 [2], coef fp32 [S, 3]")
-        for t in (x, model_in, t_model, timesteps, coef):
+        B, rows, S = x.shape[0], model_in.shape[0], timesteps.shape[0]
+        if (rows != (2 * B if cfg else B) or model_in.shape[1:] != x.shape[1:] or t_model.shape != (rows,) or
+                not self._own_shapes_ok(x)):
+            raise ValueError(f"sampler buffers disagree: state {tuple(x.shape)}, {self._own_shapes()}model input "
+                             f"{tuple(model_in.shape)}, timesteps {tuple(t_model.shape)}, guidance {cfg}")
+        if (x.dtype != torch.float32 or t_model.dtype != self.T_DTYPE or cursor.dtype != torch.int32 or cursor.numel() != 2 or
+                timesteps.dtype != self.T_DTYPE or coef.dtype != torch.float32 or tuple(coef.shape) != (S, self.COEF_WIDTH) or
+                S < 1 or not self._own_kinds_ok(S, timesteps)):
+            raise ValueError("sampler buffers: " + self.KINDS)
+        for t in (x, model_in, t_model, timesteps, coef, *self._own):
             if not t.is_contiguous():
                 raise ValueError("sampler buffers must be contiguous")
         self._set_keep(x, S, init, mask, keep_coef)
-        _require_device(x, model_in, t_model, cursor, timesteps, coef)
+        _require_device(x, model_in, t_model, cursor, timesteps, coef, *self._own)
         self.x, self.model_in, self.t_model, self.cursor, self.timesteps, self.coef = x, model_in, t_model, cursor, timesteps, coef
         self.cfg, self.B, self.per_row, self.S = bool(cfg), B, x[0].numel(), S
+
+    @classmethod
+    def _alloc_run(cls, shape, dtype, cfg, device):
+        """(x, model_in, t_model, cursor) of a run."""
+        rows = (2 if cfg else 1) * shape[0]
+        return (torch.empty(shape, dtype=torch.float32, device=device),
+                torch.empty((rows, *shape[1:]), dtype=dtype, device=device),
+                torch.empty(rows, dtype=cls.T_DTYPE, device=device), torch.zeros(2, dtype=torch.int32, device=device))
 
     @staticmethod
     def _alloc_keep(shape, n_rows, device, with_init, with_mask):
@@ -1022,12 +1046,20 @@ class SampleState:
     def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, device, with_init: bool = False,
               with_mask: bool = False):
         """`shape`: of the state, [B, C, h, w]; `timesteps` / `coef`: host or device tensors of sampler_schedule."""
-        rows = (2 if cfg else 1) * shape[0]
-        return cls(torch.empty(shape, dtype=torch.float32, device=device),
-                   torch.empty((rows, *shape[1:]), dtype=dtype, device=device),
-                   torch.empty(rows, dtype=torch.int64, device=device), torch.zeros(2, dtype=torch.int32, device=device),
-                   timesteps.to(device).contiguous(), coef.to(device).contiguous(), cfg,
-                   *cls._alloc_keep(shape, timesteps.shape[0], device, with_init, with_mask))
+        return cls(*cls._alloc_run(shape, dtype, cfg, device), timesteps.to(device).contiguous(), coef.to(device).contiguous(),
+                   cfg, *cls._alloc_keep(shape, timesteps.shape[0], device, with_init, with_mask))
+
+
+def _require_model_out(st, model_out) -> None:
+    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
+        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
+                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
+
+
+def _require_like_state(st, name: str, t) -> None:
+    """`t` (z_out, eps_out: optional outputs shaped like the state) is None or a contiguous fp32 tensor of the state's shape."""
+    if t is not None and (t.dtype != torch.float32 or t.shape != st.x.shape or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous fp32 {tuple(st.x.shape)} tensor")
 
 
 def ddpm_sample_init(st: SampleState, seed: int) -> None:
@@ -1042,11 +1074,8 @@ def ddpm_sample_step(st: SampleState, model_out, guidance_scale: float, z_out=No
     """One denoising step at the device-resident cursor (and seed): guidance, x ← a·x + b·o + σ·z in place, the next model input and
     timestep tensor.  `model_out` [rows, ...] in the model input's dtype.  Does not move the cursor: ddpm_sample_advance."""
     _require_device(model_out, z_out)
-    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
-        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
-                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
-    if z_out is not None and (z_out.dtype != torch.float32 or z_out.shape != st.x.shape or not z_out.is_contiguous()):
-        raise ValueError(f"z_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
+    _require_model_out(st, model_out)
+    _require_like_state(st, "z_out", z_out)
     _check(st._entry("ddpm_sample_step")(_ptr(st.x), _ptr(model_out), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor),
                                   _ptr(st.timesteps), _ptr(st.coef), _ptr(z_out), st.B, st.per_row, st.S, int(st.cfg),
                                   float(guidance_scale), dtype_code(model_out.dtype), _stream(st.x)),
@@ -1059,8 +1088,7 @@ def ddpm_sample_init_from(st: SampleState, seed: int, start: int, k: float, n: f
     if st.init is None:
         raise ValueError("ddpm_sample_init_from: the state has no init buffer")
     _require_device(eps_out)
-    if eps_out is not None and (eps_out.dtype != torch.float32 or eps_out.shape != st.x.shape or not eps_out.is_contiguous()):
-        raise ValueError(f"eps_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
+    _require_like_state(st, "eps_out", eps_out)
     _check(st._entry("ddpm_sample_init_from")(_ptr(st.x), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps),
                                        _ptr(st.init), _ptr(eps_out), st.B, st.per_row, st.S, int(start), float(k), float(n),
                                        int(st.cfg), int(seed) & (2**64 - 1), dtype_code(st.model_in.dtype), _stream(st.x)),
@@ -1077,11 +1105,8 @@ def ddpm_sample_step_keep(st: SampleState, model_out, guidance_scale: float, z_o
     `st.keep_coef` and the run's start draw; the model input is the blended state."""
     _require_mask(st, "ddpm_sample_step_keep")
     _require_device(model_out, z_out)
-    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
-        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
-                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
-    if z_out is not None and (z_out.dtype != torch.float32 or z_out.shape != st.x.shape or not z_out.is_contiguous()):
-        raise ValueError(f"z_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
+    _require_model_out(st, model_out)
+    _require_like_state(st, "z_out", z_out)
     _check(st._entry("ddpm_sample_step_keep")(_ptr(st.x), _ptr(model_out), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor),
                                        _ptr(st.timesteps), _ptr(st.coef), _ptr(z_out), _ptr(st.mask), _ptr(st.init),
                                        _ptr(st.keep_coef), st.B, st.per_row, st.hw, st.S, int(st.cfg), float(guidance_scale),
@@ -1094,47 +1119,46 @@ def ddpm_sample_advance(st: SampleState) -> None:
     _check(lib().ddpm_sample_advance(_ptr(st.cursor), st.S, _stream(st.x)), "ddpm_sample_advance")
 
 
-class MultistepState(SampleState):
+class _HistoryState(SampleState):
+    """What MultistepState and SigmaState add to SampleState alike: the saved state `xs` (fp32, like x), the history `hist`
+    (fp32, HIST_SLOTS + the state's shape) and `plan` int32 [I, 5], checked inside SampleState's constructor."""
+
+    HIST_SLOTS = ()
+
+    def __init__(self, x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan, cfg: bool, init=None, mask=None,
+                 keep_coef=None):
+        self.xs, self.hist, self.plan = self._own = xs, hist, plan
+        super().__init__(x, model_in, t_model, cursor, timesteps, coef, cfg, init, mask, keep_coef)
+
+    def _own_shapes_ok(self, x) -> bool:
+        return self.xs.shape == x.shape and tuple(self.hist.shape) == (*self.HIST_SLOTS, *x.shape)
+
+    def _own_kinds_ok(self, S, timesteps) -> bool:
+        return (self.xs.dtype == torch.float32 and self.hist.dtype == torch.float32 and self.plan.dtype == torch.int32 and
+                tuple(self.plan.shape) == (S, 5))
+
+    def _own_shapes(self) -> str:
+        return f"saved state {tuple(self.xs.shape)}, history {tuple(self.hist.shape)}, "
+
+    @classmethod
+    def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, plan, device, with_init: bool = False,
+              with_mask: bool = False):
+        """`shape`: of the state, [B, C, h, w]; `timesteps` / `coef` / `plan`: host or device tensors of the class's schedule
+        (sampling.multistep_schedule, sampling.sigma_schedule)."""
+        x, *run = cls._alloc_run(shape, dtype, cfg, device)
+        return cls(x, torch.empty_like(x), torch.empty((*cls.HIST_SLOTS, *shape), dtype=torch.float32, device=device), *run,
+                   timesteps.to(device).contiguous(), coef.to(device).contiguous(), plan.to(device).contiguous(), cfg,
+                   *cls._alloc_keep(shape, timesteps.shape[0], device, with_init, with_mask))
+
+
+class MultistepState(_HistoryState):
     """SampleState for the linear multistep methods (include/lora_hip.h: ddpm_sample_multistep): next to its buffers the saved
     state `xs` (fp32, like x), the history ring `hist` (fp32 [4, B, ...]), `coef` fp32 [I, 7] = (p, q, a, c0..c3) and `plan`
     int32 [I, 5] = (w, s1, s2, s3, flags) of sampling.multistep_schedule.  `S` is I, the number of model evaluations, so
     ddpm_sample_init and ddpm_sample_advance serve it as they are.  `xs` and `hist` need no clearing."""
 
-    def __init__(self, x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan, cfg: bool, init=None, mask=None,
-                 keep_coef=None):
-        B, rows = x.shape[0], model_in.shape[0]
-        if (rows != (2 * B if cfg else B) or model_in.shape[1:] != x.shape[1:] or t_model.shape != (rows,) or
-                xs.shape != x.shape or tuple(hist.shape) != (4, *x.shape)):
-            raise ValueError(f"sampler buffers disagree: state {tuple(x.shape)}, saved state {tuple(xs.shape)}, history "
-                             f"{tuple(hist.shape)}, model input {tuple(model_in.shape)}, timesteps {tuple(t_model.shape)}, "
-                             f"guidance {cfg}")
-        n = timesteps.shape[0]
-        if (x.dtype != torch.float32 or xs.dtype != torch.float32 or hist.dtype != torch.float32 or
-                t_model.dtype != torch.int64 or cursor.dtype != torch.int32 or cursor.numel() != 2 or
-                timesteps.dtype != torch.int64 or coef.dtype != torch.float32 or tuple(coef.shape) != (n, 7) or
-                plan.dtype != torch.int32 or tuple(plan.shape) != (n, 5) or n < 1):
-            raise ValueError("sampler buffers: x / xs / hist fp32, t_model / timesteps int64, cursor int32 [2], coef fp32 "
-                             "[I, 7], plan int32 [I, 5]")
-        for t in (x, xs, hist, model_in, t_model, timesteps, coef, plan):
-            if not t.is_contiguous():
-                raise ValueError("sampler buffers must be contiguous")
-        self._set_keep(x, n, init, mask, keep_coef)
-        _require_device(x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan)
-        self.x, self.model_in, self.t_model, self.cursor, self.timesteps, self.coef = x, model_in, t_model, cursor, timesteps, coef
-        self.xs, self.hist, self.plan = xs, hist, plan
-        self.cfg, self.B, self.per_row, self.S = bool(cfg), B, x[0].numel(), n
-
-    @classmethod
-    def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, plan, device, with_init: bool = False,
-              with_mask: bool = False):
-        """`shape`: of the state, [B, C, h, w]; `timesteps` / `coef` / `plan`: host or device tensors of multistep_schedule."""
-        rows = (2 if cfg else 1) * shape[0]
-        return cls(torch.empty(shape, dtype=torch.float32, device=device), torch.empty(shape, dtype=torch.float32, device=device),
-                   torch.empty((4, *shape), dtype=torch.float32, device=device),
-                   torch.empty((rows, *shape[1:]), dtype=dtype, device=device),
-                   torch.empty(rows, dtype=torch.int64, device=device), torch.zeros(2, dtype=torch.int32, device=device),
-                   timesteps.to(device).contiguous(), coef.to(device).contiguous(), plan.to(device).contiguous(), cfg,
-                   *cls._alloc_keep(shape, timesteps.shape[0], device, with_init, with_mask))
+    COEF_WIDTH, HIST_SLOTS = 7, (4,)
+    KINDS = "x / xs / hist fp32, t_model / timesteps int64, cursor int32 [2], coef fp32 [I, 7], plan int32 [I, 5]"
 
 
 def ddpm_sample_multistep(st: MultistepState, model_out, guidance_scale: float) -> None:
@@ -1142,9 +1166,7 @@ def ddpm_sample_multistep(st: MultistepState, model_out, guidance_scale: float) 
     place, the saved state and the pushed history slot as plan[i] says, the next model input and timestep tensor.  `model_out`
     [rows, ...] in the model input's dtype.  Does not move the cursor: ddpm_sample_advance."""
     _require_device(model_out)
-    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
-        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
-                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
+    _require_model_out(st, model_out)
     _check(lib().ddpm_sample_multistep(_ptr(st.x), _ptr(st.xs), _ptr(st.hist), _ptr(model_out), _ptr(st.model_in),
                                        _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps), _ptr(st.coef), _ptr(st.plan),
                                        st.B, st.per_row, st.S, int(st.cfg), float(guidance_scale),
@@ -1157,9 +1179,7 @@ def ddpm_sample_multistep_keep(st: MultistepState, model_out, guidance_scale: fl
     state before the update, as they do without a mask)."""
     _require_mask(st, "ddpm_sample_multistep_keep")
     _require_device(model_out)
-    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
-        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
-                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
+    _require_model_out(st, model_out)
     _check(st._entry("ddpm_sample_multistep_keep")(_ptr(st.x), _ptr(st.xs), _ptr(st.hist), _ptr(model_out), _ptr(st.model_in),
                                             _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps), _ptr(st.coef),
                                             _ptr(st.plan), _ptr(st.mask), _ptr(st.init), _ptr(st.keep_coef), st.B, st.per_row,
@@ -1168,48 +1188,23 @@ def ddpm_sample_multistep_keep(st: MultistepState, model_out, guidance_scale: fl
            "ddpm_sample_multistep_keep")
 
 
-class SigmaState(SampleState):
+class SigmaState(_HistoryState):
     """SampleState for the sigma-space methods (include/lora_hip.h: ddpm_sample_sigma): the saved state `xs` and the ONE history
     slot `hist` (fp32, like x), `t_model` [rows] and `timesteps` [I] in FP32 — the grid is fractional — `coef` fp32 [I, 8] = (p, q,
     a, c0, c1, s, n, σ_eval) and `plan` int32 [I, 5] of sampling.sigma_schedule.  `S` is I, the number of model evaluations, so
     ddpm_sample_advance serves it as it is.  `xs` and `hist` need no clearing."""
 
-    def __init__(self, x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan, cfg: bool, init=None, mask=None,
-                 keep_coef=None):
-        B, rows = x.shape[0], model_in.shape[0]
-        if (rows != (2 * B if cfg else B) or model_in.shape[1:] != x.shape[1:] or t_model.shape != (rows,) or
-                xs.shape != x.shape or hist.shape != x.shape):
-            raise ValueError(f"sampler buffers disagree: state {tuple(x.shape)}, saved state {tuple(xs.shape)}, history "
-                             f"{tuple(hist.shape)}, model input {tuple(model_in.shape)}, timesteps {tuple(t_model.shape)}, "
-                             f"guidance {cfg}")
-        n = timesteps.shape[0]
-        if (x.dtype != torch.float32 or xs.dtype != torch.float32 or hist.dtype != torch.float32 or
-                t_model.dtype != torch.float32 or cursor.dtype != torch.int32 or cursor.numel() != 2 or
-                timesteps.dtype != torch.float32 or timesteps.dim() != 1 or coef.dtype != torch.float32 or
-                tuple(coef.shape) != (n, 8) or plan.dtype != torch.int32 or tuple(plan.shape) != (n, 5) or n < 1):
-            raise ValueError("sampler buffers: x / xs / hist fp32, t_model / timesteps fp32, cursor int32 [2], coef fp32 "
-                             "[I, 8], plan int32 [I, 5]")
-        for t in (x, xs, hist, model_in, t_model, timesteps, coef, plan):
-            if not t.is_contiguous():
-                raise ValueError("sampler buffers must be contiguous")
-        self._set_keep(x, n, init, mask, keep_coef)
-        _require_device(x, xs, hist, model_in, t_model, cursor, timesteps, coef, plan)
-        self.x, self.model_in, self.t_model, self.cursor, self.timesteps, self.coef = x, model_in, t_model, cursor, timesteps, coef
-        self.xs, self.hist, self.plan = xs, hist, plan
-        self.cfg, self.B, self.per_row, self.S = bool(cfg), B, x[0].numel(), n
+    T_DTYPE, COEF_WIDTH = torch.float32, 8
+    KINDS = "x / xs / hist fp32, t_model / timesteps fp32, cursor int32 [2], coef fp32 [I, 8], plan int32 [I, 5]"
+
+    def _own_kinds_ok(self, S, timesteps) -> bool:
+        return super()._own_kinds_ok(S, timesteps) and timesteps.dim() == 1
 
     @classmethod
     def alloc(cls, shape, dtype: torch.dtype, cfg: bool, timesteps, coef, plan, device, with_init: bool = False,
               with_mask: bool = False):
-        """`shape`: of the state, [B, C, h, w]; `timesteps` / `coef` / `plan`: host or device tensors of sigma_schedule (the
-        float64 timesteps are rounded to fp32 here)."""
-        rows = (2 if cfg else 1) * shape[0]
-        return cls(torch.empty(shape, dtype=torch.float32, device=device), torch.empty(shape, dtype=torch.float32, device=device),
-                   torch.empty(shape, dtype=torch.float32, device=device),
-                   torch.empty((rows, *shape[1:]), dtype=dtype, device=device),
-                   torch.empty(rows, dtype=torch.float32, device=device), torch.zeros(2, dtype=torch.int32, device=device),
-                   timesteps.to(device=device, dtype=torch.float32).contiguous(), coef.to(device).contiguous(),
-                   plan.to(device).contiguous(), cfg, *cls._alloc_keep(shape, timesteps.shape[0], device, with_init, with_mask))
+        """As _HistoryState.alloc, with sigma_schedule's float64 timesteps rounded to fp32 here."""
+        return super().alloc(shape, dtype, cfg, timesteps.to(torch.float32), coef, plan, device, with_init, with_mask)
 
 
 def ddpm_sample_sigma_init(st: SigmaState, seed: int, start: int, k: float, nn: float, c_in: float, from_init: bool = False,
@@ -1220,8 +1215,7 @@ def ddpm_sample_sigma_init(st: SigmaState, seed: int, start: int, k: float, nn: 
     if from_init and st.init is None:
         raise ValueError("ddpm_sample_sigma_init: the state has no init buffer")
     _require_device(eps_out)
-    if eps_out is not None and (eps_out.dtype != torch.float32 or eps_out.shape != st.x.shape or not eps_out.is_contiguous()):
-        raise ValueError(f"eps_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
+    _require_like_state(st, "eps_out", eps_out)
     _check(lib().ddpm_sample_sigma_init(_ptr(st.x), _ptr(st.model_in), _ptr(st.t_model), _ptr(st.cursor), _ptr(st.timesteps),
                                         _ptr(st.init) if from_init else 0, _ptr(eps_out), st.B, st.per_row, st.S, int(start),
                                         float(k), float(nn), float(c_in), int(st.cfg), int(st.shared_noise),
@@ -1237,11 +1231,8 @@ def ddpm_sample_sigma(st: SigmaState, model_out, guidance_scale: float, z_out=No
     if keep:
         _require_mask(st, "ddpm_sample_sigma")
     _require_device(model_out, z_out)
-    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
-        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
-                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
-    if z_out is not None and (z_out.dtype != torch.float32 or z_out.shape != st.x.shape or not z_out.is_contiguous()):
-        raise ValueError(f"z_out must be a contiguous fp32 {tuple(st.x.shape)} tensor")
+    _require_model_out(st, model_out)
+    _require_like_state(st, "z_out", z_out)
     _check(lib().ddpm_sample_sigma(_ptr(st.x), _ptr(st.xs), _ptr(st.hist), _ptr(model_out), _ptr(st.model_in), _ptr(st.t_model),
                                    _ptr(st.cursor), _ptr(st.timesteps), _ptr(st.coef), _ptr(st.plan), _ptr(z_out),
                                    _ptr(st.mask) if keep else 0, _ptr(st.init) if keep else 0,
@@ -1257,9 +1248,7 @@ def ddpm_cfg_rescale(st: SampleState, model_out, guidance_scale: float, rescale:
     if not st.cfg:
         raise ValueError("ddpm_cfg_rescale: the state has no guidance rows (a single pass has nothing to rescale)")
     _require_device(model_out, k_out)
-    if model_out.dtype != st.model_in.dtype or model_out.shape != st.model_in.shape or not model_out.is_contiguous():
-        raise ValueError(f"the model output must be a contiguous {st.model_in.dtype} {tuple(st.model_in.shape)} tensor; got "
-                         f"{model_out.dtype} {tuple(model_out.shape)}, strides {model_out.stride()}")
+    _require_model_out(st, model_out)
     if k_out is not None and (k_out.dtype != torch.float32 or tuple(k_out.shape) != (st.B,) or not k_out.is_contiguous()):
         raise ValueError(f"k_out must be a contiguous fp32 [{st.B}] tensor")
     _check(lib().ddpm_cfg_rescale(_ptr(model_out), _ptr(k_out), st.B, st.per_row, float(guidance_scale), float(rescale),

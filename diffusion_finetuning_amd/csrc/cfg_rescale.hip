@@ -24,7 +24,7 @@ template <typename T, int V> struct alignas(V * sizeof(T)) Pack {
     T v[V];
 };
 
-// the guided output, as `guided` of ddpm_loss.hip: the difference, the product and the sum each rounded to fp32
+// the guided output, as `guided` of ddpm_sample.hip: the difference, the product and the sum each rounded to fp32
 __device__ __forceinline__ float guided(float u, float c, float g) {
 #pragma clang fp contract(off)
     const float d = c - u;

@@ -7,7 +7,7 @@ images prior preservation trains on (training_scripts/train_lora_dreambooth.py:5
 and train_lora_pt_caption.py:583), and `visualize_progress` over saved checkpoints (utils.py:166-214) — each time through a
 stock diffusers pipeline.  The forward is the fused LoRA GEMMs / attention cores / fused norms of this library already; what
 is here is the loop around it: classifier-free guidance, the scheduler step, the variance noise and the re-assembly of the
-doubled model input are ONE HIP launch per denoising step (csrc/ddpm_loss.hip: ddpm_sample_step), the step index lives in
+doubled model input are ONE HIP launch per denoising step (csrc/ddpm_sample.hip: ddpm_sample_step), the step index lives in
 device memory, and one denoising iteration — forward, step, cursor advance — is recorded once into a hipGraph and replayed.
 
 Every supported scheduler step is linear in the state x and the guided output o (SD's clip_sample=False, no thresholding):
@@ -28,7 +28,7 @@ Image-to-image ("Making Img2Img Inference with LoRA", README.md:287-289 and scri
 `pipe(image=init_image, strength=0.75)`, repeated at equal seed under `tune_lora_scale(unet, 0.0 / 0.7 / 1.0)`).  With S =
 num_inference_steps and `strength` in (0, 1], n = min(int(S·strength), S) grid steps are run (n == 0 is an error), from k0 = S − n
 and t0 = grid[k0]; the start state is x = fp32(√ᾱ[t0]·init) + fp32(√(1−ᾱ[t0])·ε), ε the x_T draw of the same seed, `init` the
-caller's `vae.encode(...).sample() * 0.18215` (csrc/ddpm_loss.hip: ddpm_sample_init_from).  "ddpm" / "ddim" run iterations
+caller's `vae.encode(...).sample() * 0.18215` (csrc/ddpm_sample.hip: ddpm_sample_init_from).  "ddpm" / "ddim" run iterations
 k0 … S−1 of their tables unchanged, the variance noise keyed by the absolute index; "plms" / "dpmpp_2m" start FRESH on grid[k0:]
 with empty history (`multistep_schedule(first_step=k0)`: plms warms up there, n + 1 evaluations for n ≥ 2; dpmpp_2m's first
 iteration is first order, its last when S < 15).  The cursor lives in device memory, so a partial run is the same recorded
@@ -49,13 +49,13 @@ rows), is rewritten in place per run and installed on the LoRA layers only while
 on WHETHER there is a table and on R, never on its values — one recording serves every sweep and every mix — and a trainer that
 shares the UNet never sees it.  The grouped q/k/v and context-K/V launches stand aside while it is installed.  `shared_noise=True`
 gives every sample the draws of the B = 1 run of the same seed (x_T, the variance noise, the start noise the keep blend
-regenerates: the `_shared` entries of csrc/ddpm_loss.hip) — "equal seed" in the reference's loops.
+regenerates: the `_shared` entries of csrc/ddpm_sample.hip) — "equal seed" in the reference's loops.
 Sigma-space methods ("k_euler", "euler_a", "heun"; `karras_sigmas=True`; plain Euler is spelt "k_euler" here because
 `LatentSampler(method="euler")` is an unknown-method error that callers rely on — `sigma_schedule` itself calls it "euler"):
 two of the reference's notebooks set `EulerAncestralDiscreteScheduler` before they sample (scripts/lora_training_process_visualized.ipynb:57, 40 and 50 steps;
 scripts/merge_lora_with_lora.ipynb:74, 30 steps).  `sigma_schedule` computes k-diffusion's Euler, Euler-ancestral and Heun steps
 on a FRACTIONAL timestep grid; the state lives in sigma space (x_T = σ₀·z) and the model is fed x/√(σ²+1) with the σ of the next
-evaluation, written by the step launch itself (csrc/ddpm_loss.hip: ddpm_sample_sigma — fp32 timesteps, the variance noise of the
+evaluation, written by the step launch itself (csrc/ddpm_sample.hip: ddpm_sample_sigma — fp32 timesteps, the variance noise of the
 one-step kernel and the saved state / history slot of the multistep kernel in one launch).  `timesteps`, `run_timesteps` and the
 callback's timestep are floats there; `latents` mid-run are in sigma space — √(σ²+1) times the model input — and are model-space
 latents once the run completes (σ = 0).  Image-to-image starts at table row k0 (2·k0 for heun) from init + σ_{k0}·ε: Heun needs

@@ -2,7 +2,7 @@
 
 Philox4x32-10 (Salmon et al., "Parallel Random Numbers: As Easy as 1, 2, 3", SC'11 — the published algorithm and
 constants; known-answer vectors from the Random123 distribution are checked in tests/test_oracle_golden.py) and the
-Box–Muller / integer-range mapping that csrc/ddpm_loss.hip applies.  Integer streams are bit-exact with the GPU;
+Box–Muller / integer-range mapping that csrc/ddpm_common.h applies.  Integer streams are bit-exact with the GPU;
 the normals differ only by libm vs GPU logf/sincosf rounding.  There is no reference file to cite: the reference
 draws its noise from torch's global generator (train_lora_dreambooth.py:824-833); this replaces that draw with a
 counter-based stream that is identical on every rank and on CPU and GPU (SURVEY §8 d, f-3).

@@ -176,6 +176,28 @@ def test_init_draws_the_first_state_from_a_stream_of_its_own(B, per_row, dtype, 
         assert torch.equal(sh.x.cpu(), x)
 
 
+@pytest.mark.parametrize("shifted", [False, True])
+def test_init_and_the_sigma_start_with_unit_factors_are_one_computation(shifted):
+    """ddpm_sample_init is the start kernel of ddpm_sample_sigma_init at init = None, start = 0, nn = 1, c_in = 1 (a strict fp32
+    multiply by 1 changes no bit): the state is the draw ε itself and the model input its cast, bit for bit, on the ragged
+    3 x 37 f16 state, both access paths."""
+    B, per_row, dtype, cfg, n = 3, 37, torch.float16, True, 4
+    st, _, _, _ = _state(B, per_row, dtype, cfg, "ddim", 0.0, False, S=n, shifted=shifted)
+    nat.ddpm_sample_init(st, 77)
+    place = (lambda t: _shifted(t.to(DEV))) if shifted else (lambda t: t.to(DEV))
+    rows = 2 * B
+    sg = nat.SigmaState(place(torch.zeros(B, per_row)), place(torch.zeros(B, per_row)), place(torch.zeros(B, per_row)),
+                        place(torch.zeros(rows, per_row, dtype=dtype)), place(torch.zeros(rows)),
+                        place(torch.zeros(2, dtype=torch.int32)), place(st.timesteps.cpu().float()), place(torch.zeros(n, 8)),
+                        place(torch.zeros(n, 5, dtype=torch.int32)), cfg)
+    eps = place(torch.full((B, per_row), 7.0))
+    nat.ddpm_sample_sigma_init(sg, 77, 0, 0.0, 1.0, 1.0, eps_out=eps)
+    assert torch.equal(st.x, eps) and torch.equal(st.x, sg.x)
+    assert torch.equal(st.model_in, sg.model_in)
+    assert sg.t_model.cpu().tolist() == [float(t) for t in st.t_model.cpu().tolist()]
+    assert st.cursor.cpu().tolist() == sg.cursor.cpu().tolist() == [0, 77]
+
+
 # -- whole chains ----------------------------------------------------------------------------------------------------------------
 class _Out:
     def __init__(self, sample):

@@ -1,5 +1,5 @@
 """Dev tool: device time of the flash backward kernels alone (dispatch events), for ablation builds of the library
-(tools/build_variant.sh abl<N> -DFLASH_ABL=<N>; DFA_LIB_PATH selects one).  Results of an ablation build are wrong: timing only."""
+(python -m diffusion_finetuning_amd.build_native --variant abl<N> -DFLASH_ABL=<N>; DFA_LIB_PATH selects one).  Results of an ablation build are wrong: timing only."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
