@@ -306,43 +306,6 @@ def lora_pack_factors_batched(table, n_layers: int, max_len: int, params, packed
                                            dtype_code(packed.dtype), _stream(params)), "lora_pack_factors_batched")
 
 
-def lora_linear_fwd(x2, w, bias, a, b, scale: float, packs=None):
-    """x2 [M,K], w [N,K], bias [N]|None (dtype of x2); a [r,K], b [N,r] fp32 masters; packs = (Apack, Bpack)
-    (made here when not given). Returns (y [M,N], T [M,r] fp32)."""
-    _require_device(x2, w, bias, a, b)
-    M, K = x2.shape
-    N, r = b.shape
-    if packs is None:
-        packs = lora_pack_factors(a, b, x2.dtype)
-    y = torch.empty((M, N), dtype=x2.dtype, device=x2.device)
-    t = torch.empty((M, r), dtype=torch.float32, device=x2.device)
-    ws = _splitk_workspace(M, K, N, x2)
-    _check(
-        lib().lora_linear_fwd_ws(_ptr(x2), _ptr(w), _ptr(bias), _ptr(a), _ptr(b), _ptr(packs[0]), _ptr(packs[1]), _ptr(y),
-                                 _ptr(t), M, K, N, r, float(scale), dtype_code(x2.dtype), _ptr(ws),
-                                 0 if ws is None else ws.numel() * 4, _stream(x2)),
-        "lora_linear_fwd",
-    )
-    return y, t
-
-
-def lora_linear_geglu_fwd(x2, w, bias, r: int, scale: float, packs, want_y: bool):
-    """`proj` forward with the GEGLU gate in the epilogue: x2 [M,K], w [2F,K], packs = (Apack, Bpack).
-    Returns (out [M,F], y [M,2F] | None, T [M,r] fp32), or None when the library has no fused kernel for the shape/dtype."""
-    _require_device(x2, w, bias)
-    M, K = x2.shape
-    N = w.shape[0]
-    out = torch.empty((M, N // 2), dtype=x2.dtype, device=x2.device)
-    y = torch.empty((M, N), dtype=x2.dtype, device=x2.device) if want_y else None
-    t = torch.empty((M, r), dtype=torch.float32, device=x2.device)
-    st = lib().lora_linear_geglu_fwd(_ptr(x2), _ptr(w), _ptr(bias), _ptr(packs[0]), _ptr(packs[1]), _ptr(y), _ptr(out),
-                                     _ptr(t), M, K, N, r, float(scale), dtype_code(x2.dtype), _stream(x2))
-    if st == -5:
-        return None
-    _check(st, "lora_linear_geglu_fwd")
-    return out, y, t
-
-
 def _require_row_scales(table, M: int, r: int, what: str) -> None:
     """The gate table of a `_rows` entry: fp32 [n_samples, R >= r] on the device, rows dense, M a multiple of n_samples."""
     _require_device(table)
@@ -352,47 +315,79 @@ def _require_row_scales(table, M: int, r: int, what: str) -> None:
         raise ValueError(f"{what}: a [{table.shape[0]}, {table.shape[1]}] gate table does not fit {M} rows at rank {r}")
 
 
-def lora_linear_fwd_rows(x2, w, bias, a, b, scale: float, row_scales, packs=None):
-    """`lora_linear_fwd` with per-sample, per-rank-slot gates: row_scales fp32 [n_samples, R >= r], sample b = rows
-    [b·M/n_samples, (b+1)·M/n_samples) of x2, effective factor scale·row_scales[b, j].  Inference only.  Returns (y, T)."""
+def _row_scale_args(table) -> tuple:
+    """What a `_rows` entry takes between `scale` and `dtype`."""
+    return _ptr(table), table.shape[0], table.stride(0)
+
+
+def _linear_fwd(what: str, x2, w, bias, a, b, scale: float, row_scales, packs):
+    """The one body of lora_linear_fwd (row_scales None: the `_ws` entry) and lora_linear_fwd_rows."""
     _require_device(x2, w, bias, a, b)
     M, K = x2.shape
     N, r = b.shape
-    _require_row_scales(row_scales, M, r, "lora_linear_fwd_rows")
+    if row_scales is not None:
+        _require_row_scales(row_scales, M, r, what)
     if packs is None:
         packs = lora_pack_factors(a, b, x2.dtype)
     y = torch.empty((M, N), dtype=x2.dtype, device=x2.device)
     t = torch.empty((M, r), dtype=torch.float32, device=x2.device)
     ws = _splitk_workspace(M, K, N, x2)
-    _check(
-        lib().lora_linear_fwd_rows(_ptr(x2), _ptr(w), _ptr(bias), _ptr(a), _ptr(b), _ptr(packs[0]), _ptr(packs[1]), _ptr(y),
-                                   _ptr(t), M, K, N, r, float(scale), _ptr(row_scales), row_scales.shape[0],
-                                   row_scales.stride(0), dtype_code(x2.dtype), _ptr(ws), 0 if ws is None else ws.numel() * 4,
-                                   _stream(x2)),
-        "lora_linear_fwd_rows",
-    )
+    head = (_ptr(x2), _ptr(w), _ptr(bias), _ptr(a), _ptr(b), _ptr(packs[0]), _ptr(packs[1]), _ptr(y), _ptr(t), M, K, N, r,
+            float(scale))
+    tail = (dtype_code(x2.dtype), _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream(x2))
+    if row_scales is None:
+        _check(lib().lora_linear_fwd_ws(*head, *tail), what)
+    else:
+        _check(lib().lora_linear_fwd_rows(*head, *_row_scale_args(row_scales), *tail), what)
     return y, t
+
+
+def lora_linear_fwd(x2, w, bias, a, b, scale: float, packs=None):
+    """x2 [M,K], w [N,K], bias [N]|None (dtype of x2); a [r,K], b [N,r] fp32 masters; packs = (Apack, Bpack)
+    (made here when not given). Returns (y [M,N], T [M,r] fp32)."""
+    return _linear_fwd("lora_linear_fwd", x2, w, bias, a, b, scale, None, packs)
+
+
+def lora_linear_fwd_rows(x2, w, bias, a, b, scale: float, row_scales, packs=None):
+    """`lora_linear_fwd` with per-sample, per-rank-slot gates: row_scales fp32 [n_samples, R >= r], sample b = rows
+    [b·M/n_samples, (b+1)·M/n_samples) of x2, effective factor scale·row_scales[b, j].  Inference only.  Returns (y, T)."""
+    return _linear_fwd("lora_linear_fwd_rows", x2, w, bias, a, b, scale, row_scales, packs)
+
+
+def _linear_geglu_fwd(what: str, x2, w, bias, r: int, scale: float, row_scales, packs, want_y: bool):
+    """The one body of lora_linear_geglu_fwd (row_scales None) and lora_linear_geglu_fwd_rows."""
+    _require_device(x2, w, bias)
+    M, K = x2.shape
+    N = w.shape[0]
+    if row_scales is not None:
+        _require_row_scales(row_scales, M, r, what)
+        if packs is None or packs[0] is None:
+            return None
+    out = torch.empty((M, N // 2), dtype=x2.dtype, device=x2.device)
+    y = torch.empty((M, N), dtype=x2.dtype, device=x2.device) if want_y else None
+    t = torch.empty((M, r), dtype=torch.float32, device=x2.device)
+    head = (_ptr(x2), _ptr(w), _ptr(bias), _ptr(packs[0]), _ptr(packs[1]), _ptr(y), _ptr(out), _ptr(t), M, K, N, r, float(scale))
+    tail = (dtype_code(x2.dtype), _stream(x2))
+    if row_scales is None:
+        st = lib().lora_linear_geglu_fwd(*head, *tail)
+    else:
+        st = lib().lora_linear_geglu_fwd_rows(*head, *_row_scale_args(row_scales), *tail)
+    if st == -5:
+        return None
+    _check(st, what)
+    return out, y, t
+
+
+def lora_linear_geglu_fwd(x2, w, bias, r: int, scale: float, packs, want_y: bool):
+    """`proj` forward with the GEGLU gate in the epilogue: x2 [M,K], w [2F,K], packs = (Apack, Bpack).
+    Returns (out [M,F], y [M,2F] | None, T [M,r] fp32), or None when the library has no fused kernel for the shape/dtype."""
+    return _linear_geglu_fwd("lora_linear_geglu_fwd", x2, w, bias, r, scale, None, packs, want_y)
 
 
 def lora_linear_geglu_fwd_rows(x2, w, bias, r: int, scale: float, row_scales, packs, want_y: bool):
     """`lora_linear_geglu_fwd` with the gates of `lora_linear_fwd_rows`; None when the library has no fused kernel for the
     shape / dtype."""
-    _require_device(x2, w, bias)
-    M, K = x2.shape
-    N = w.shape[0]
-    _require_row_scales(row_scales, M, r, "lora_linear_geglu_fwd_rows")
-    if packs is None or packs[0] is None:
-        return None
-    out = torch.empty((M, N // 2), dtype=x2.dtype, device=x2.device)
-    y = torch.empty((M, N), dtype=x2.dtype, device=x2.device) if want_y else None
-    t = torch.empty((M, r), dtype=torch.float32, device=x2.device)
-    st = lib().lora_linear_geglu_fwd_rows(_ptr(x2), _ptr(w), _ptr(bias), _ptr(packs[0]), _ptr(packs[1]), _ptr(y), _ptr(out),
-                                          _ptr(t), M, K, N, r, float(scale), _ptr(row_scales), row_scales.shape[0],
-                                          row_scales.stride(0), dtype_code(x2.dtype), _stream(x2))
-    if st == -5:
-        return None
-    _check(st, "lora_linear_geglu_fwd_rows")
-    return out, y, t
+    return _linear_geglu_fwd("lora_linear_geglu_fwd_rows", x2, w, bias, r, scale, row_scales, packs, want_y)
 
 
 def lora_linear_bwd_input(dy2, wt, a, b, scale: float, need_dx: bool, packs=None):

@@ -12,7 +12,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "liblora_hip.so")
-SOURCES = ["lora_gemm.hip", "lora_grad.hip", "ddpm_loss.hip", "ddpm_prologue.hip", "ddpm_sample.hip", "cfg_rescale.hip", "optim.hip", "prodigy.hip", "max_norm.hip", "sandwich.hip", "norm.hip", "trunk_edges.hip", "time_proj.hip", "conv_small.hip", "conv_large.hip", "layer_norm.hip", "attn_ctx.hip", "attn_causal.hip", "attn_flash.hip", "attn_f32.hip", "embed.hip", "distill.hip", "distill_wide.hip", "prof.hip"]
+SOURCES = ["lora_gemm.hip", "lora_pack.hip", "lora_grad.hip", "ddpm_loss.hip", "ddpm_prologue.hip", "ddpm_sample.hip", "cfg_rescale.hip", "optim.hip", "prodigy.hip", "max_norm.hip", "sandwich.hip", "norm.hip", "trunk_edges.hip", "time_proj.hip", "conv_small.hip", "conv_large.hip", "layer_norm.hip", "attn_ctx.hip", "attn_causal.hip", "attn_flash.hip", "attn_f32.hip", "embed.hip", "distill.hip", "distill_wide.hip", "prof.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-source flags (none at present).  A kernel that runs at ONE wave per SIMD (> 256 registers) wants

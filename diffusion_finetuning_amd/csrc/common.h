@@ -26,6 +26,33 @@ template <> struct ElemTraits<bf16_t> {
     static constexpr int kVec = 8;
 };
 
+constexpr int kRP = 16;  // rank padded to one MFMA fragment: the rank slots of a packed LoRA factor (lora_pack.hip, lora_gemm_kernel.h)
+
+inline bool known_dtype(int dtype) { return dtype == LORA_F32 || dtype == LORA_F16 || dtype == LORA_BF16; }
+
+// Element type by LORA_* dtype code.  status_by_dtype calls f with the tag of the type `dtype` names (`using T = typename
+// decltype(tag)::type`) and returns f's own status; by_dtype is the form for an f that only launches: it checks the launch f made.
+// Both: LORA_E_BADARG, and no call, for a dtype that names none.
+template <typename T> struct TypeTag {
+    using type = T;
+};
+template <typename F>
+int status_by_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case LORA_F32: return f(TypeTag<float>{});
+        case LORA_F16: return f(TypeTag<half_t>{});
+        case LORA_BF16: return f(TypeTag<bf16_t>{});
+        default: return LORA_E_BADARG;
+    }
+}
+template <typename F>
+int by_dtype(int dtype, F&& f) {
+    return status_by_dtype(dtype, [&](auto tag) {
+        f(tag);
+        return hipGetLastError() != hipSuccess ? LORA_E_LAUNCH : LORA_OK;
+    });
+}
+
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return static_cast<float>(v); }
 template <typename T> __device__ __forceinline__ T from_f32(float v) { return static_cast<T>(v); }
 // x as an fp32 value that has been rounded: where a kernel restates torch op by op, this keeps hipcc from folding the
@@ -49,7 +76,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // GEGLU gate arithmetic of diffusers GEGLU.forward (exact-erf gelu), shared by sandwich.hip and the GATE epilogue of
-// lora_gemm.hip.  fp32 tensors: erff / expf.  16-bit tensors: Φ(g) from the Abramowitz–Stegun 7.1.26 form
+// lora_gemm_kernel.h.  fp32 tensors: erff / expf.  16-bit tensors: Φ(g) from the Abramowitz–Stegun 7.1.26 form
 //     erfc(z) = t·(a1 + t·(a2 + t·(a3 + t·(a4 + t·a5))))·exp(−z²),  t = 1/(1 + p·z),  z = |g|/√2        (|ε| ≤ 1.5e-7)
 // used on the erfc side for g < 0 (no cancellation), one v_rcp_f32 + one v_exp_f32 + 8 VALU instead of erff's ~55: its error
 // is 3e-4 of a half-precision ulp for g > 0 and stays under a tenth of an ulp down to g = −3 (below that |gelu| < 4e-3·|g|),

@@ -69,24 +69,4 @@ inline unsigned posterior_blocks(int64_t n_total) {
     return (unsigned)(blocks > 2048 ? 2048 : blocks);
 }
 
-inline bool known_dtype(int dtype) { return dtype == LORA_F32 || dtype == LORA_F16 || dtype == LORA_BF16; }
-
-// Calls f with the tag of the element type `dtype` names (`using T = typename decltype(tag)::type`), then checks the launch f
-// made; LORA_E_BADARG, and no call, for a dtype that names none.
-template <typename T> struct TypeTag {
-    using type = T;
-};
-
-template <typename F>
-int by_dtype(int dtype, F&& f) {
-    switch (dtype) {
-        case LORA_F32: f(TypeTag<float>{}); break;
-        case LORA_F16: f(TypeTag<half_t>{}); break;
-        case LORA_BF16: f(TypeTag<bf16_t>{}); break;
-        default: return LORA_E_BADARG;
-    }
-    LORA_LAUNCH_CHECK();
-    return LORA_OK;
-}
-
 }  // namespace

@@ -22,7 +22,7 @@ from torch.autograd.function import once_differentiable
 from . import _native as nat
 from ._fastattr import factor_weights, frozen_linear
 
-RANK_PAD = 16  # rank slots of one packed factor (kRP in csrc/lora_gemm.hip)
+RANK_PAD = 16  # rank slots of one packed factor (kRP in csrc/common.h)
 
 
 def _cast_cat(weights: Sequence[torch.Tensor], cdtype: torch.dtype, transpose: bool) -> torch.Tensor:

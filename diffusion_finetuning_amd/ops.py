@@ -680,7 +680,7 @@ ROW_SCALES = "_dfa_row_scales"  # module.__dict__ key of an installed gate table
 
 
 def _lora_linear_rows(module, x, gate, table, cdtype, w_param, b_param, down, up):
-    """`lora_linear` while a gate table is installed: the `_rows` entries (csrc/lora_gemm.hip, RS kernels) — sample b of the
+    """`lora_linear` while a gate table is installed: the `_rows` entries (csrc/lora_gemm.hip; RS kernels of csrc/lora_gemm_kernel.h) — sample b of the
     batch multiplies rank slot j with module.scale · table[b, j].  No autograd node: the caller has checked that grad mode
     is off."""
     r = down.shape[0]

@@ -21,7 +21,7 @@ backward stay out: tests/test_gpu_groups.py and tests/test_gpu_geglu.py own thos
 import torch
 
 RING, FALLBACK, GENERIC, SPLIT = "ring", "fallback", "generic", "split"
-ROW_BYTES = 128       # kRowBytes: one K-step of one tile row
+ROW_BYTES = 128       # kRowBytes (csrc/lora_gemm_kernel.h): one K-step of one tile row
 TICKET_BYTES = 4096   # LORA_GEMM_WS_TICKET_BYTES
 ESIZE = {torch.float32: 4, torch.float16: 2, torch.bfloat16: 2}
 DTYPES = {2: (torch.float16, torch.bfloat16), 4: (torch.float32,)}

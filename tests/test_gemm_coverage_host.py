@@ -17,14 +17,19 @@ from oracle import lora_oracle as orc
 from tests.gemm_cases import (CASES, FALLBACK, GENERIC, RING, SKINNY_CASES, SPLIT, class_of, gate_tile_width,
                               gemm_launch_class, make_layer, plan_splitk, skinny_class_of, skinny_launch_class)
 
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "diffusion_finetuning_amd", "csrc",
-                   "lora_gemm.hip")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "diffusion_finetuning_amd", "csrc")
+SRC = os.path.join(CSRC, "lora_gemm.hip")  # plan_splitk, gate_tile_width, launch_tile, launch_pipe, launch_typed
+# ... followed by what it includes: kRowBytes lives with the kernel, kRP and kVec in common.h
+INCLUDED = ("lora_gemm_kernel.h", "common.h")
 TILE = re.compile(r"launch_tile<T,\s*(\d+),\s*(\d+),\s*(true|false),\s*(\d+)(?:,\s*\d+)*>")
 
 
 def _source():
-    with open(SRC) as f:
-        return f.read()
+    text = ""
+    for path in (SRC, *(os.path.join(CSRC, name) for name in INCLUDED)):
+        with open(path) as f:
+            text += f.read()
+    return text
 
 
 def _body(src, start, end):
@@ -213,7 +218,9 @@ def test_mirrors_match_the_cpp_they_copy():
     assert len(re.findall(r"static constexpr int kVec = 8;", common)) == 2 and "static constexpr int kVec = 4;" in common
     # the kernel kinds the GPU file tells apart
     tile = _body(src, "int launch_tile(GemmParams p", "int gate_tile_width(")
-    for line in ("LORA_LAUNCH(PK_GEMM_SPLITK, kern, dim3(p.tiles_m * p.tiles_n * p.splitk), dim3(NW * 64), lds, stream, p);",
+    for line in ("const int blocks = p.tiles_m * p.tiles_n * p.splitk;",
+                 "return launch_instance<lora_gemm_kernel<T, BM, BN, MAIN, STG, NW, WM, 0, true>, lds, PK_GEMM_SPLITK>(blocks, NW * 64, p, stream);",
+                 "if (rs) return launch_instance<lora_gemm_kernel<T, BM, BN, MAIN, STG, NW, WM, 0, true, 1, true>, lds, PK_GEMM_SPLITK>(blocks, NW * 64, p, stream);",
                  "constexpr int prof_id = MAIN ? (BM >= 256 ? PK_GEMM_256x128 : (BM == 128 ? PK_GEMM_128x128 : PK_GEMM_64x64))",
                  ": (BM == 128 ? PK_SKINNY_128 : PK_SKINNY_64);"):
         assert line in tile, line

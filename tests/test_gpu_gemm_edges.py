@@ -197,7 +197,7 @@ def test_every_class_in_both_roles_inside_guard_bands(close, relerr, key, shape,
     del Y, T, y_ref, ga_ref, gb_ref
     # ---- backward-input role: layer N = Kc, K = Nc, on the same Am (now dY) and Bm (now Wᵀ) -------------------------------
     down2, up2 = make_factors(Nc, Kc, r, dtype, seed=M + Kc + Nc + r + 1)  # A [r, K = Nc], B [N = Kc, r]
-    # dX = dY·W + s·(dY·B)·A is the forward formula on (dY, Wᵀ, Bᵀ, Aᵀ): the template's identity (csrc/lora_gemm.hip, top)
+    # dX = dY·W + s·(dY·B)·A is the forward formula on (dY, Wᵀ, Bᵀ, Aᵀ): the template's identity (csrc/lora_gemm_kernel.h, top)
     dx_ref = orc.lora_linear_forward(x.double(), w.double(), None, up2.double().t(), down2.double().t(), scale)
     u2_ref = x.double() @ up2.double()
     down2d, up2d = down2.to(DEV), up2.to(DEV)

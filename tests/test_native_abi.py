@@ -73,7 +73,7 @@ def test_no_mfma_result_is_read_early_across_a_branch(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_mfma_hazard as chk
 
-    srcs = [s for s in bn.SOURCES if s not in ("prof.hip", "optim.hip", "ddpm_loss.hip", "ddpm_prologue.hip", "ddpm_sample.hip", "embed.hip")]  # (kernels with MFMAs)
+    srcs = [s for s in bn.SOURCES if s not in ("prof.hip", "lora_pack.hip", "optim.hip", "ddpm_loss.hip", "ddpm_prologue.hip", "ddpm_sample.hip", "embed.hip")]  # (kernels with MFMAs)
 
     def to_isa(src):
         out = str(tmp_path / (src + ".s"))
